@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the 3D detection / PRM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload detect|backbone|prm|prm-nuclei|volume] [--stress-rois] [--no-subrecords]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload detect|backbone|prm|prm-nuclei|volume] [--stress-rois]
+                    [--dump-outputs DIR] [--full [--no-subrecords] [--no-cpu-baseline] [--interleaved] [--pipelined]]
 
 Default workload = BASELINE.json configs[2]: the full detection-mode pipeline of tools/infer_simple.py:249-265 /
 lib/core/test.py:54-177 on a batch of 4 synthetic 1x128x128x128 volumes per rank - at every N (weak scaling; `--vols-per-rank 8`
@@ -12,15 +13,21 @@ at N = 8 is configs[4]'s 64 volumes, which the N > 1 line also carries as `confi
 THREE distinct batches rotate through the loop (12 different volumes at N = 1: different RoI counts, different branches, nothing of the
 input resident in a cache from the step before).
 `value` (voxels/s, whole job) is SURVEY 8d's definition: host to host, the raw volumes in pinned host memory when the clock starts, the
-detections on the host when it stops (uploads on a copy stream, double-buffered).  `resident` on the same line is the same loop with the
-raw volumes already in HBM (the definition of rounds 1-3); `sustained` repeats that one for at least two seconds.
+detections on the host when it stops (uploads on a copy stream, double-buffered).
+A plain run (detect / backbone) does only that: set-up, W warm-up steps, the K timed steps, `--dump-outputs DIR` if given, and the
+compact line with the contract's keys.  Everything below is measured with `--full` only (also the full record, see emit()).
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as float32 .npy files: `detections.npy`, the gathered
+packed detections [N, volumes per rank, 301, 7] that reach the host (m3d.shard layout: a row is one detection's box + score, the
+trailer row holds the count), or `feat.npy` for --workload backbone.  Inputs and weights are seeded: the same arguments give the same inputs.
+`resident` on the `--full` line is the same loop with the raw volumes already in HBM (the definition of rounds 1-3); `sustained`
+repeats that one for at least two seconds.
 `roofline` is the metric's named quantity, the 3D-convolution family (dsn_body + RPN convs): `frac` = fp32 MFMA FLOPs ISSUED by all its
 launches over their summed live duration (HIP events on the launch stream inside the timed region) against the 157.3 TF peak - the
 hardware fraction; `frac_algorithmic` = the direct-convolution count 2*Cin*Cout*k^3 per voxel over the same time against the same peak
 (> 1 is possible and is NOT a hardware fraction: Winograd issues 1/3 of those multiplies).  `rooflines` has one entry per layer + fc1.
 `cpu_baseline` is the oracle's restatement of the same per-volume pipeline (torch-CPU convs + oracle C ops) on a bounded sample.
 
-Sub-records of the default N = 1 line (each with ms_per_step, roofline incl. PMC traffic, cpu_baseline; `--no-subrecords` skips them):
+Sub-records of the default N = 1 `--full` line (each with ms_per_step, roofline incl. PMC traffic, cpu_baseline; `--no-subrecords` skips them):
   configs1_backbone   BASELINE configs[1]: dsn_body forward alone on ONE 1x128^3 volume
   stress_rois         the default step with the RPN NMS off: RPN_POST_NMS_TOP_N = 1000 RoIs per volume reach the box head
   configs3_prm_soma   BASELINE configs[3]: PRM_ON soma tile 1x64x160x160 -> peak back-propagation -> 2D-Otsu -> instance labels
@@ -30,7 +37,7 @@ Sub-records of the default N = 1 line (each with ms_per_step, roofline incl. PMC
 
 N > 1: `python bench.py --gpus N` starts N fresh child processes itself (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in
 their environment, created before this process touches the GPU) unless a launcher (torch.distributed.run) already did.  The N > 1
-line also carries `without_exchange`, `single_gpu_same_batch` (rank 0's batch timed while the other ranks idle) and `exchange`
+`--full` line also carries `without_exchange`, `single_gpu_same_batch` (rank 0's batch timed while the other ranks idle) and `exchange`
 (the all_gather alone, microseconds, ranks, backend).  Sub-records are an N = 1 matter and are skipped.
 `--dry --backend gloo` runs the same launcher + exchange with a stub step on CPU (tests/test_host_logic.py).
 """
@@ -147,6 +154,23 @@ def sync_max_time(dt, dist, device):
     t = torch.tensor([dt], device=device, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: name -> tensor the timed path returned, written as out_dir/<name>.npy in float32.  An array beyond its share of
+    DUMP_MAX_BYTES is replaced by a fixed seeded sample of its flattened elements (in index order), so that runs compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        if a.nbytes > share:
+            a = a.ravel()[np.sort(np.random.RandomState(0).choice(a.size, share // 4, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 PROBE_STEPS = 3        # timed steps that carry per-kernel HIP-event spans (the rooflines' live durations); the rest run bare
@@ -707,6 +731,7 @@ def bench_detect(args, rank, world, dist):
         rk["i"] += 1
         packed = batch(raw_dev[b])
         if backbone_only:
+            last["feat"] = packed
             return packed
         last["packed"] = exchange(packed)
         return last["packed"]
@@ -778,21 +803,41 @@ def bench_detect(args, rank, world, dist):
     gc.freeze()
     # The host-to-host loop runs BARE: a probed step records ~40 timing events between its kernels (5.0 instead of 4.4 ms per step, and the
     # steps behind it stay slow for a while); the rooflines' live spans come from the first PROBE_STEPS steps of the `resident` timed loop
-    # below - the same K steps over the same batches.  (configs[1] has no resident loop: its headline loop carries the probe.)
+    # below - the same K steps over the same batches.  (configs[1] has no resident loop: with --full its headline loop carries the probe.)
     main_probe = Probe()
-    arm(main_probe, PROBE_STEPS if backbone_only else 0)
+    arm(main_probe, PROBE_STEPS if backbone_only and args.full else 0)
     del rois_seen[:]
     del hstamps[:]
     dt = timed_loop(headline, args.steps, 0, dist, torch.cuda.synchronize)
     step_ms_timed = [round((b_ - a_) * 1e3, 2) for a_, b_ in zip(hstamps[:-1], hstamps[1:])][:max(0, args.steps - 1)]
     dt = sync_max_time(dt, dist, "cpu" if via_host else "cuda")
     torch.cuda.synchronize()
+    outputs = {"feat": last["feat"]} if backbone_only else {"detections": last["packed"]}     # the last timed step's, for --dump-outputs
+    rois_per_step = float(np.mean(rois_seen)) if rois_seen else None
+    res = {"metric": METRIC, "value": n_items * args.steps * VOL ** 3 / dt, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32", "data": "synthetic",
+           "config": {"workload": ("dsn_body forward (7 conv3d + BN + ReLU + 3 maxpool; the volume normalised beforehand), 1x1x128x128x128 per rank [configs[1]]"
+                                   if backbone_only else
+                                   "detection-mode infer_simple, host to host: pinned raw u16 volumes -> H2D -> norm1 -> dsn_body -> RPN -> proposals "
+                                   "-> RoIAlign3D -> 2-MLP head -> decode -> NMS -> cross-tile NMS -> one all_gather of detections -> D2H; batch of "
+                                   "%d x (1x128^3) per rank, %d distinct batches rotating [%s]%s"
+                                   % (nvol, nb, "configs[2]" if (world == 1 and nvol == 4) else "%d volumes over %d GPUs%s" %
+                                      (n_items, world, " = configs[4]" if n_items == 64 and world == 8 else ""),
+                                      " STRESS: RPN NMS off, %d RoIs per volume (RPN_POST_NMS_TOP_N)" % cfg.post_nms_topN if args.stress_rois else "")),
+                      "volumes_per_step": n_items, "volumes_per_rank": nvol, "distinct_batches": nb,
+                      "backend": (args.backend if world > 1 else None), "net": "nuclei stride-8 dsn_body, 35 anchors, MLP 1024",
+                      "inputs": ("one normalised fp32 volume resident in HBM" if backbone_only else
+                                 "raw uint16 volumes in pinned host memory at the start of the timed region; detections on the host at its end"),
+                      "rois_per_volume": (rois_per_step / nvol if rois_per_step else None),
+                      "dets_per_volume": (float(last["packed"][..., cap, 0].float().mean().item()) if "packed" in last else None)}}
+    if not args.full:                            # a plain run: the headline alone
+        return (res, outputs) if rank == 0 else (None, None)
     kern_ms = main_probe.mean_ms()
     kern_med = main_probe.median_ms()
     main_probe.spans.clear()                     # hand the timing events back to torch's pool: creating fresh ones (hipEventCreate with timing)
     det.probe = None                             # costs ~0.4 ms each - 120 of them made the next probed loop 2 ms per step slower
     arm(None, 0)
-    rois_per_step = float(np.mean(rois_seen)) if rois_seen else None
     rois_probed = float(np.mean(rois_seen[:PROBE_STEPS])) if rois_seen else None
     rmed = None
 
@@ -1041,8 +1086,7 @@ def bench_detect(args, rank, world, dist):
                "roofline": fam_b, "rooflines": roofs_b}
 
     if rank != 0:
-        return None
-    voxels = n_items * args.steps * VOL ** 3
+        return None, None
     # ---- rooflines from the live HIP-event spans of the timed region.  `roofline` = the 3D-convolution family, the quantity the metric
     # names: MFMA FLOPs issued by all its launches over their summed duration; `rooflines` = one entry per conv layer + fc1
     wino = det.wino_mode
@@ -1128,23 +1172,7 @@ def bench_detect(args, rank, world, dist):
         r.update(pmc_traffic("roi_align3d_fwd_v3_kernel"))
         roofs["roi_align3d"] = r
     body_ms = sum(v for k, v in kern_ms.items() if k.startswith("conv")) / nvol      # spans cover the whole batch
-    res = {"metric": METRIC, "value": voxels / dt, "unit": "voxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-           "data": "synthetic",
-           "config": {"workload": ("dsn_body forward (7 conv3d + BN + ReLU + 3 maxpool; the volume normalised beforehand), 1x1x128x128x128 per rank [configs[1]]"
-                                   if backbone_only else
-                                   "detection-mode infer_simple, host to host: pinned raw u16 volumes -> H2D -> norm1 -> dsn_body -> RPN -> proposals "
-                                   "-> RoIAlign3D -> 2-MLP head -> decode -> NMS -> cross-tile NMS -> one all_gather of detections -> D2H; batch of "
-                                   "%d x (1x128^3) per rank, %d distinct batches rotating [%s]%s"
-                                   % (nvol, nb, "configs[2]" if (world == 1 and nvol == 4) else "%d volumes over %d GPUs%s" %
-                                      (n_items, world, " = configs[4]" if n_items == 64 and world == 8 else ""),
-                                      " STRESS: RPN NMS off, %d RoIs per volume (RPN_POST_NMS_TOP_N)" % cfg.post_nms_topN if args.stress_rois else "")),
-                      "volumes_per_step": n_items, "volumes_per_rank": nvol, "distinct_batches": nb,
-                      "backend": (args.backend if world > 1 else None), "net": "nuclei stride-8 dsn_body, 35 anchors, MLP 1024",
-                      "inputs": ("one normalised fp32 volume resident in HBM" if backbone_only else
-                                 "raw uint16 volumes in pinned host memory at the start of the timed region; detections on the host at its end"),
-                      "rois_per_volume": (rois_per_step / nvol if rois_per_step else None),
-                      "dets_per_volume": (float(last["packed"][..., cap, 0].float().mean().item()) if "packed" in last else None),
+    res["config"].update({
                       "backbone_gflop_per_volume": backbone_flops(VOL) / 1e9, "backbone_ms_per_volume": body_ms,
                       "backbone_algorithmic_tflops": backbone_flops(VOL) / (body_ms * 1e-3) / 1e12 if body_ms else None,
                       "kernel_ms_per_launch": kern,
@@ -1159,8 +1187,8 @@ def bench_detect(args, rank, world, dist):
                                             "(process start and model build leave it idle); with half a second of GPU load in front of the warm-up "
                                             "every timed step ran 4.3-4.45 ms and the loop 4.37 (measured, not done here: no hidden warm-up) - "
                                             "`warm_host_to_host` is the same loop on a chip that holds its clock, `sustained` the steady state of the resident steps",
-                      "kernel_ms_per_launch_median": {k: round(v, 4) for k, v in sorted(kern_med.items(), key=lambda kv: -kv[1])}},
-           "roofline": conv_family, "rooflines": roofs}
+                      "kernel_ms_per_launch_median": {k: round(v, 4) for k, v in sorted(kern_med.items(), key=lambda kv: -kv[1])}})
+    res.update(roofline=conv_family, rooflines=roofs)
     if getattr(det, "conv_f16", False) or (not backbone_only and getattr(det, "fc_split", None)):
         res["dtype_note"] = ("every operand, accumulator and result is fp32; " + ("the 3^3 conv layers with 16 | cin (conv2a .. conv4b, the RPN conv) and " if getattr(det, "conv_f16", False) else "") +
                              "fc1 / fc2 multiply on the f16 matrix cores after both fp32 operands are scaled "
@@ -1220,7 +1248,7 @@ def bench_detect(args, rank, world, dist):
         res["configs1_backbone"] = bb1
     if stress is not None:
         res["stress_rois"] = stress
-    return res
+    return res, outputs
 
 
 def condensed(r):
@@ -1364,8 +1392,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 5; 50 for --workload backbone)")
     ap.add_argument("--workload", default="detect", choices=["detect", "backbone", "prm", "prm-nuclei", "volume"])
     ap.add_argument("--vols-per-rank", type=int, default=0, help="volumes per rank per step (default 4 at every N; 8 = BASELINE configs[4]'s partition)")
-    ap.add_argument("--interleaved", action="store_true", help="also time the one-stream begin(k+1) / finish(k) loop (N = 1)")
-    ap.add_argument("--pipelined", action="store_true", help="also time the two-stream begin(k+1) / finish(k) loop (N = 1)")
+    ap.add_argument("--full", action="store_true", help="detect / backbone workloads: after the headline also measure everything else - resident, "
+                    "warm and sustained loops, rooflines, the N > 1 breakdown, the sub-records, CPU baselines - and write the full record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="detect / backbone workloads: write what the last timed step returned "
+                    "to DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--interleaved", action="store_true", help="with --full: also time the one-stream begin(k+1) / finish(k) loop (N = 1)")
+    ap.add_argument("--pipelined", action="store_true", help="with --full: also time the two-stream begin(k+1) / finish(k) loop (N = 1)")
     ap.add_argument("--stress-rois", action="store_true", help="RPN NMS threshold 1.0: every volume gives RPN_POST_NMS_TOP_N = 1000 RoIs to the box head")
     ap.add_argument("--prm-norm-stream", type=int, default=1, help="PRM workloads: 0 = norm convs queued on the tile's own stream instead of a second one (A/B)")
     ap.add_argument("--prm-rpn-logit-scale", type=float, default=0.25, help="PRM workloads: factor on the random-init RPN class logits of both nets (1.0 = the saturated sigmoids rounds 1-3 (nuclei) / 1-5 (soma) timed)")
@@ -1374,12 +1406,16 @@ def main():
     ap.add_argument("--prm-binarize-stream", type=int, default=1, help="PRM workloads: 0 = a tile's binarisation stage on the tile's stream instead of its own (where it runs beside the next tile's forward) (A/B)")
     ap.add_argument("--prm-backward-streams", type=int, default=1, help="PRM workloads: 2 = the peaks' back-propagation as two halves on two streams (A/B)")
     ap.add_argument("--prm-fused-prepare", type=int, default=1, help="PRM workloads: 0 = strip conv and the next layer's prepare as two launches (A/B)")
-    ap.add_argument("--no-subrecords", action="store_true", help="default workload at N = 1: skip configs1_backbone / stress_rois / configs3_prm_soma / prm_nuclei_tile / volume_pipeline")
+    ap.add_argument("--no-subrecords", action="store_true", help="with --full, default workload at N = 1: skip configs1_backbone / stress_rois / configs3_prm_soma / prm_nuclei_tile / volume_pipeline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--dry", action="store_true", help="launcher + exchange rehearsal without a GPU (stub step)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--upload-at", default="end", choices=["mid", "end"], help="host-to-host loop: where the next step's pinned upload is issued (A/B, measured equal: 3.944 / 3.940 ms; see step_host)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry or args.workload not in ("detect", "backbone")):
+        ap.error("--dump-outputs: the detect and backbone workloads only")
+    if (args.interleaved or args.pipelined) and not args.full:
+        ap.error("--interleaved / --pipelined are measured with --full")
     if args.steps is None:
         args.steps = 200 if args.workload == "backbone" else 20     # a timed region of ~0.1-0.2 s either way
     if args.warmup is None:
@@ -1414,13 +1450,14 @@ def main():
                 dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
             else:
                 dist.init_process_group("gloo", rank=rank, world_size=world)
+        outputs = None
         if args.workload in ("prm", "prm-nuclei"):
             res = bench_prm(args, rank, world, dist)
         elif args.workload == "volume":
             res = bench_volume(args, rank, world, dist)
         else:
-            res = bench_detect(args, rank, world, dist)
-            if res is not None and args.workload == "detect" and world == 1 and not args.stress_rois and not args.no_subrecords:
+            res, outputs = bench_detect(args, rank, world, dist)
+            if res is not None and args.full and args.workload == "detect" and world == 1 and not args.stress_rois and not args.no_subrecords:
                 # the reference's DEFAULT mode is PRM_ON (both shipped YAMLs): its tiles and whole volumes ride on the default line
                 import copy
                 torch.cuda.empty_cache()
@@ -1466,7 +1503,12 @@ def main():
                 except Exception as e:
                     res["volume_pipeline"] = {"error": "%s: %s" % (type(e).__name__, e)}
         if rank == 0 and res is not None:
-            emit(res, "%s_n%d%s" % (args.workload, world, "_stress" if args.stress_rois else ""))
+            if args.dump_outputs:                        # after every measurement: nothing extra runs between the timed loops
+                dump_outputs(args.dump_outputs, outputs)
+            if args.full or args.workload not in ("detect", "backbone"):
+                emit(res, "%s_n%d%s" % (args.workload, world, "_stress" if args.stress_rois else ""))
+            else:                                            # a plain run: the headline line alone, no full record
+                print(compact_line(res), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 

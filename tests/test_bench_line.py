@@ -1,10 +1,13 @@
 """bench.py's final stdout line must stay parseable by the driver, which keeps ~9 KB of stdout tail (round 4's 25.9 KB line left
-BENCH_r04.parsed null).  CPU only: the compaction on a committed full record, on a bloated synthetic one, and on the --dry path."""
+BENCH_r04.parsed null).  CPU: the compaction on a committed full record, on a bloated synthetic one, and on the --dry path; the
+--dump-outputs writer and option checks.  GPU: a plain run's line and the detections it dumps."""
 import importlib.util
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -99,3 +102,50 @@ def test_a_hardware_fraction_above_one_is_an_accounting_error():
         assert soma["peaks_back_propagated"] == soma["peaks_per_tile"], soma
     line = json.loads(b.compact_line(dict(r05, accounting_errors=["%s = %.3f > 1" % x for x in bad])))
     assert line["accounting_errors"]
+
+
+def _env():
+    return {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_of_an_array_beyond_its_share(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    b = _bench()
+    small = torch.arange(24, dtype=torch.int32).reshape(2, 3, 4)
+    big = torch.arange(4096, dtype=torch.float64)
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 2048)                     # 1 KB per array
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.numpy())
+    g = np.load(tmp_path / "a" / "big.npy")
+    assert g.dtype == np.float32 and g.shape == (256,) and np.all(np.diff(g) > 0)      # distinct elements in index order
+    assert np.array_equal(g, np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_options_outside_their_workload_are_refused():
+    bench = os.path.join(ROOT, "bench.py")
+    for extra in (["--dry", "--dump-outputs", "x"], ["--workload", "prm", "--dump-outputs", "x"], ["--interleaved"], ["--pipelined"]):
+        r = subprocess.run([sys.executable, bench, "--steps", "1"] + extra, capture_output=True, text=True, timeout=120, env=_env())
+        assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr[-500:])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_last_steps_detections(tmp_path):
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, env=_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.rstrip("\n").splitlines()[-1])
+    for k in CONTRACT:
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "voxels/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 4 * 128 ** 3 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert not set(d) & {"roofline", "cpu_baseline", "resident", "sustained", "configs1_backbone", "volume_pipeline", "full_record"}
+    det = np.load(out / "detections.npy")
+    assert det.dtype == np.float32 and det.shape == (1, 4, 301, 7)
+    counts = det[0, :, 300, 0]
+    assert np.all(counts == np.round(counts)) and np.all(counts >= 0) and np.all(counts <= 300) and counts.sum() > 0
+    assert abs(float(counts.mean()) - d["config"]["dets_per_volume"]) < 1e-6

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Check a bench.py stdout capture the way the driver reads it: the LAST line must be JSON, under 8000 bytes, and carry the
-contract's keys + roofline + cpu_baseline.   python tools/check_bench_line.py gpurun_out/bench_default.log"""
+"""Check a `bench.py --full` stdout capture: the LAST line must be JSON, under 8000 bytes, and carry the contract's keys + roofline +
+cpu_baseline.   python bench.py --full > bench_full.log; python tools/check_bench_line.py bench_full.log"""
 import json
 import sys
 
