@@ -40,7 +40,10 @@ constexpr int TX = 16, TY = 4, TZ = 4, HX = TX + 2, HY = TY + 2, HZ = TZ + 2, NH
 constexpr int TM = 64;                                  // output channels per workgroup
 constexpr int NT = 256;
 // NPL = pieces per operand: 3 (bf16x3: exact three-way bf16 cut, six products) or 2 (round 6, "f16x2": both operands scaled by a power of
-// two and cut into two fp16 numbers, 22 bits, three products - fc_gemm.hip; conv3d_x3_kernel<.., 1>)
+// two and cut into two fp16 numbers, 22 bits, three products - fc_gemm.hip; conv3d_x3_kernel<.., 1>).  The f16x2 form keeps the exact
+// zeros of the bf16x3 / fp32 kernels (non-negative operands: a zero product stays zero) but is not exact in the other direction: an operand
+// below its bound x 2^-39 cuts to 0, so a small positive N may come out 0 or below the `N < 1e-10` gate.  Its accuracy is the per-element
+// bound E of tests/f16x2_contract.py, not an exact-zero guarantee.
 constexpr int in_units(int npl) { return 2 * npl * NHV; }                 // [piece][k half 2][halo voxel]
 constexpr int w_units(int npl) { return 2 * npl * TM; }                  // one tap: [piece][k half 2][row 64]
 constexpr int IN_UNITS = in_units(3);

@@ -36,6 +36,17 @@ def _f32c(t):
     return t.contiguous().float() if (t.dtype != torch.float32 or not t.is_contiguous()) else t
 
 
+def _claim(out):
+    """A caller's `out=` tensor is about to be rewritten through ctypes, which does not bump its `_version`: drop the operand bounds an
+    earlier launch left on it (`_m3d_bound`, `_m3d_peak_max`, also on the tensor it is a view of), or the next f16x2 conv would scale the
+    new values by the old bound.  A launch that leaves a fresh bound sets it after this.  Other views of the same storage (siblings of
+    `out`, or views of `out`) keep theirs: no caller leaves a bound on such a view, and one that did would have to drop it itself."""
+    for t in (out, getattr(out, "_base", None)):
+        if t is not None:
+            t.__dict__.pop("_m3d_bound", None)
+            t.__dict__.pop("_m3d_peak_max", None)
+
+
 # ------------------------------------------------------------------ RoIAlign3D
 def roi_align3d_forward(features, rois, AS, AH, AW, spatial_scale, sampling_ratio, exact=False, ordered=True, feat_absmax=None):
     """exact=True: the reference kernel's fp32 operation order (bit-identical to the oracle); default: the
@@ -377,6 +388,7 @@ class PackedConv3d:
         B, Cin, D, H, W = x.shape
         if Cin != self.cin:
             raise ValueError("expected %d input channels, got %d" % (self.cin, Cin))
+        _claim(out)
         if out is None:
             out = torch.empty((B, self.cout, D, H, W), dtype=torch.float32, device=x.device)
         for t in (scale, shift):
@@ -436,6 +448,7 @@ class X3Conv3d:
             raise ValueError("expected %d input channels, got %d" % (self.cin, Cin))
         if self.f16 and in_max is None:
             raise ValueError("X3Conv3d(f16=True) needs in_max (ops.reduce_minmax_multi / ops.absmax)")
+        _claim(out)
         if out is None:
             out = torch.empty((B, self.cout, D, H, W), dtype=torch.float32, device=x.device)
         wsb = lib().m3d_conv3d_x3_workspace_bytes(B, Cin, self.cout, D, H, W)
@@ -537,6 +550,7 @@ def linear(x, weight, bias=None, relu=False, out=None):
     if bias is not None:
         bias = _f32c(bias)
         assert bias.numel() == N
+    _claim(out)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     if M == 0:
@@ -577,6 +591,7 @@ class SplitLinear:
         M, K = x.shape
         if K != self.K:
             raise ValueError("SplitLinear: x is [%d,%d] but the weight is [%d,%d]" % (M, K, self.N, self.K))
+        _claim(out)
         if out is None:
             out = torch.empty((M, self.N), dtype=torch.float32, device=x.device)
         if M == 0:
@@ -643,6 +658,7 @@ class SplitLinearF16:
         M, K = x.shape
         if K != self.K:
             raise ValueError("SplitLinearF16: x is [%d,%d] but the weight is [%d,%d]" % (M, K, self.N, self.K))
+        _claim(out)
         if out is None:
             out = torch.empty((M, self.N), dtype=torch.float32, device=x.device)
         if M == 0:
@@ -726,6 +742,7 @@ def norm1(vol, f32_arith=True, out=None, return_stats=False):
     vol = vol.contiguous()
     if vol.dtype not in (torch.uint16, torch.float32):
         raise TypeError("norm1 takes uint16 or float32 volumes")
+    _claim(out)
     if out is None:
         out = torch.empty(vol.shape, dtype=torch.float32, device=vol.device)
     wsb = lib().m3d_norm1_workspace_bytes()
@@ -744,6 +761,7 @@ def norm1_batched(vols, f32_arith=True, out=None):
         raise TypeError("norm1 takes uint16 or float32 volumes")
     B = vols.shape[0]
     n = vols[0].numel()
+    _claim(out)
     if out is None:
         out = torch.empty(vols.shape, dtype=torch.float32, device=vols.device)
     assert out.is_contiguous() and out.numel() == vols.numel() and out.dtype == torch.float32
@@ -790,6 +808,7 @@ class SmallWindowDgrad:
     """Backward-data of a 3^3 conv with relu(W) on batches of 3^3 / 5^3 / 7^3 windows, all peaks in one dense GEMM
     (csrc/prm_small.hip); weight = the forward conv's [cout, cin, 3, 3, 3], packed once."""
     SIZES = (3, 5, 7)
+    F16_MAX_PEAKS = 65535                                   # peaks per m3d_prm_small_dgrad_f16 launch (the library refuses more)
 
     def __init__(self, weight, f16=True):
         """f16 (round 6, default where the forward conv's cout is a multiple of 16): the f16x2 split on v_mfma_f32_32x32x16_f16 (csrc/
@@ -816,11 +835,16 @@ class SmallWindowDgrad:
         assert Cc == self.cout_fwd and n in self.SIZES and full.shape[0] == self.cin_fwd
         out = torch.empty((P, self.cin_fwd, n, n, n), dtype=torch.float32, device=gn.device)
         if self.f16:
-            wsb = lib().m3d_prm_small_dgrad_f16_workspace_bytes(P)
-            ws = torch.empty((wsb // 4,), dtype=torch.float32, device=gn.device)
-            check(lib().m3d_prm_small_dgrad_f16(_ptr(gn), _ptr(self.packed), P, self.cout_fwd, self.cin_fwd, n, _ptr(_f32c(full)), _ptr(full_off),
-                                                _ptr(origins), full.shape[1], full.shape[2], full.shape[3], _ptr(out), _ptr(ws), C.c_size_t(wsb),
-                                                _stream()), "prm_small_dgrad_f16")
+            # at most F16_MAX_PEAKS peaks per launch: a peak's rows depend only on its own window and scale, so a split batch computes the
+            # whole batch's values bit for bit
+            full = _f32c(full)
+            for p0 in range(0, P, self.F16_MAX_PEAKS):
+                p1 = min(P, p0 + self.F16_MAX_PEAKS)
+                wsb = lib().m3d_prm_small_dgrad_f16_workspace_bytes(p1 - p0)
+                ws = torch.empty((wsb // 4,), dtype=torch.float32, device=gn.device)
+                check(lib().m3d_prm_small_dgrad_f16(_ptr(gn[p0:p1]), _ptr(self.packed), p1 - p0, self.cout_fwd, self.cin_fwd, n, _ptr(full),
+                                                    _ptr(full_off), _ptr(origins[p0:p1]), full.shape[1], full.shape[2], full.shape[3],
+                                                    _ptr(out[p0:p1]), _ptr(ws), C.c_size_t(wsb), _stream()), "prm_small_dgrad_f16")
             return out
         check(lib().m3d_prm_small_dgrad(_ptr(gn), _ptr(self.packed), P, self.cout_fwd, self.cin_fwd, n, _ptr(_f32c(full)), _ptr(full_off),
                                         _ptr(origins), full.shape[1], full.shape[2], full.shape[3], _ptr(out), _stream()),
@@ -1151,6 +1175,7 @@ def prm_quantize_windows_compact_u8(windows, sums, origins, shape, out=None, ret
     windows = _f32c(windows)
     P, Wn = windows.shape[0], windows.shape[1]
     D, H, W = (int(v) for v in shape)
+    _claim(out)
     if out is None:
         out = torch.empty((P, Wn, Wn, Wn), dtype=torch.uint8, device=windows.device)
     ws = torch.empty((max(16 * P, 16),), dtype=torch.uint8, device=windows.device)
@@ -1238,13 +1263,22 @@ class ZwConv3d(object):
         if L < 24 or not self.supports((D, H, L)) or gn.numel() * 4 >= 0x7FFFFF00 or pitch % 4 or L % 4:
             return None
         bounds = self._strip_bounds(gn, pitch, P, bounds)
+        if bounds is None:
+            return None
+        _claim(out)
         if out is None:
             out = torch.empty((self.cout, D, H, L), dtype=torch.float32, device=gn.device)
         check(lib().m3d_conv3d_zw_forward_strip(_ptr(gn), _ptr(self.packed), _ptr(out), cin, self.cout, D, H, L, _ptr(bounds), int(P), int(pitch),
                                                 _stream()), "conv3d_zw_forward_strip")
         return out
 
+    STRIP_SWEEP_MAX_PEAKS = 12288                           # windows one m3d_prm_strip_absmax sweep takes (one LDS float per window)
+
     def _strip_bounds(self, gn, pitch, P, bounds):
+        """the per-window operand bounds [P, 32] of a strip conv, or None where they are not given and the strip has more windows than
+        the sweep takes (the caller then returns None: the fp32 strip kernels run instead)"""
+        if bounds is None and P > self.STRIP_SWEEP_MAX_PEAKS:
+            return None
         if bounds is None:                                  # (the producer did not leave them: one sweep of the strip)
             bounds = torch.empty((P, 32), dtype=torch.float32, device=gn.device)
             check(lib().m3d_prm_strip_absmax(_ptr(gn), C.c_longlong(gn.shape[0] * gn.shape[1] * gn.shape[2]), int(gn.shape[3]), int(pitch), int(P),
@@ -1265,6 +1299,8 @@ class ZwConv3d(object):
         if L < 24 or pitch % 4 or gn.numel() * 4 >= 0x7FFFFF00 or not self.supports((gn.shape[1], U, L)):
             return None
         bounds = self._strip_bounds(gn, pitch, P, bounds)
+        if bounds is None:
+            return None
         out = torch.empty((self.cout, MD if out_slab else U + 2, U + 2, strip_geometry(U + 2, 2, P)[2]), dtype=torch.float32, device=gn.device)
         oo = torch.empty((P, 3), dtype=torch.int32, device=gn.device)
         rc = lib().m3d_prm_strip_dgrad_prepare_zw(_ptr(gn), _ptr(self.packed), cin, self.cout, P, U, int(in_slab), _ptr(origin), _ptr(xnext),
@@ -1299,6 +1335,7 @@ class ZwConv3d(object):
         assert cin == self.cin and in_max.numel() == self.SLOTS and in_max.dtype == torch.float32
         assert x[0].numel() * 4 < 0x7FFFFFFF                  # one batch item is addressed with 32-bit buffer offsets
         oshape = (B, self.cout, D // 2, H // 2, W // 2) if pool else (B, self.cout, D, H, W)
+        _claim(out)
         if out is None:
             out = torch.empty(oshape, dtype=torch.float32, device=x.device)
         assert tuple(out.shape) == oshape and out.is_contiguous()
@@ -1355,6 +1392,7 @@ class WinoConv3d(object):
         x = _f32c(x)
         B, cin, D, H, W = x.shape
         assert cin == self.cin
+        _claim(out)
         if out is None:
             out = torch.empty((B, self.cout, D, H, W), dtype=torch.float32, device=x.device)
         if self.two_d:                                     # the library picks the tile; small / ragged maps may split K
@@ -1414,6 +1452,7 @@ class WinoConv3d(object):
         x = _f32c(x)
         B, cin, D, H, W = x.shape
         assert cin == self.cin
+        _claim(out)
         if out is None:
             out = torch.empty((B, self.cout, D // 2, H // 2, W // 2), dtype=torch.float32, device=x.device)
         if return_argmax:
@@ -1453,6 +1492,7 @@ class StemWinoConv3d(object):
         x = _f32c(x)
         B, cin, D, H, W = x.shape
         assert cin == 1
+        _claim(out)
         if out is None:
             shp = (B, self.cout, D // 2, H // 2, W // 2) if pool else (B, self.cout, D, H, W)
             out = torch.empty(shp, dtype=torch.float32, device=x.device)

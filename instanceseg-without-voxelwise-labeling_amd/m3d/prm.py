@@ -17,7 +17,7 @@ from .model import DetectorM3D, _NOSPAN
 class PRMEngine:
     def __init__(self, det: DetectorM3D, peak_chunk=None, window_budget=3 << 30, fused_stem=True, strip_wino=True, strip_min=16, wino_forward=True, small_gemm=True,
                  strip_f24=True, strip_f24_min=16, norm_stream=True, backward_streams=1, backward_split_min=8, slab_strips=True, x3_norm=True,
-                 fused_prepare=True, skip_dead_peaks=True, x3_f16=True, strip_zw=None):
+                 fused_prepare=True, skip_dead_peaks=True, x3_f16=False, strip_zw=None):
         self.det = det
         # skip_dead_peaks: a kept peak whose RPN sigmoid is exactly 1.0f has the derivative (1 - y) y == 0: its seed, every layer of its
         # back-propagation and its map are exactly zero (the reference then returns 0 / 0 = NaN for it, peak_response_mapping_3d.py:170-171).
@@ -50,7 +50,9 @@ class PRMEngine:
         self.x3_norm = bool(x3_norm)
         # x3_f16 (round 6): those norm convs with the f16x2 split (two scaled fp16 pieces per operand, three products instead of bf16x3's
         # six; ops.X3Conv3d(f16=True)): the operand X - min X is scaled by its largest value max X - min X, which the forward's two-launch
-        # sweep now delivers beside the minima (ops.reduce_minmax_multi); the exact zeros are the same (tests/test_gpu_ops.py)
+        # sweep delivers beside the minima (ops.reduce_minmax_multi).  Off by default: an exact zero of the fp32 kernel stays zero, but an
+        # operand below (max X - min X) 2^-39 cuts to 0, and at product weights and spans the contract's band E around N can be wider than
+        # the PostHook's 1e-10 gate, so N can land on the other side of it (tests/test_gpu_f16x2_range.py); the bf16x3 cut is exact
         self.x3_f16 = bool(x3_f16)
         # backward_streams = 2: the tile's peaks are back-propagated as two halves on two HIP streams - while one half's element-wise
         # `prepare` pass streams through HBM the other half's window convolution holds the matrix cores, and each launch's last,

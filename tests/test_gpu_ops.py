@@ -1286,9 +1286,10 @@ def test_bf16x3_direct_conv_has_fp32_accuracy_and_the_fp32_kernels_exact_zeros(c
     plain = ops.X3Conv3d(wc, ops.W_PLAIN)(xc).cpu()                          # signed weights, no offset
     ref2 = torch.nn.functional.conv3d(x.double(), w.double(), padding=1)
     assert float((plain.double() - ref2).abs().max()) / float(ref2.abs().max()) < 2e-6
-    # round 6: the f16x2 split (two scaled fp16 pieces per operand, three products): the same exact zeros (every product triple of a
-    # non-negative pair is >= 0 and zero only when x w is), error against fp64 within 3e-6 of the largest output, minima / maxima from the
-    # two-launch sweep, with and without the K split
+    # round 6: the f16x2 split (two scaled fp16 pieces per operand, three products): on these inputs (every operand >= 0.25 above the
+    # minimum or exactly at it) the same exact zeros - the fp32 kernel's zeros stay zero, and no operand is small enough to cut to 0 (in
+    # general one below its bound x 2^-39 does: tests/test_gpu_f16x2_range.py) - error against fp64 within 3e-6 of the largest output,
+    # minima / maxima from the two-launch sweep, with and without the K split
     mn, mx = ops.reduce_minmax_multi([xc, xc[:, :1].contiguous()])
     assert float(mn[0]) == float(x.min()) == 0.25 and float(mx[0]) == float(x.max()) and float(mx[1]) == float(x[:, :1].max())
     c16 = ops.X3Conv3d(wc, ops.W_RELU, f16=True)
