@@ -753,6 +753,38 @@ int m3d_paint_begin(uint32_t* d_volume, int64_t num_voxels, uint8_t* d_present, 
                     const int32_t* d_status_cc, const int32_t* d_map_stats, const int64_t* d_idx, int num_rois, int first_id,
                     int32_t* d_ids, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Evaluation of instance-label volumes (csrc/eval3d.hip).  Replaces the voxel work of tools/evaluation/
+ * eval_instance_segmentation_soma.py:186-199 (one bool mask per instance, then mask_iou.py:50-68 mask_iou_fast, a P x G x V loop)
+ * and of evaluation_nuclei_f1score_seg.py:88-133 (pixel sums of the TP boxes).
+ *   m3d_label_overlap   two label volumes d_a, d_b of num_voxels labels (label_bytes 2: uint16, 4: int32), labels in [0, max] with
+ *                       max_a, max_b < 2^24 -> d_count_a [max_a + 1] / d_count_b [max_b + 1] int64 voxel counts per label, and the
+ *                       pairs (a, b) with a > 0 and b > 0 that occur: d_pairs int32 [capacity, 2] sorted by (a, b), d_pair_counts
+ *                       int64 [capacity] their voxel counts.  d_status int64 [2]: [0] flags (1: a label above its maximum - never
+ *                       used as an index; 2: the hash table of `capacity` slots (a power of two) was full - re-launch with a larger
+ *                       one; min(V, (max_a + 1)(max_b + 1)) pairs can occur), [1] the number of pairs.  Workspace
+ *                       m3d_label_overlap_workspace_bytes(max_a, capacity).  Integer counts, sorted output: bit-identical run to run.
+ *   m3d_label_iou_best  per row r (d_row_ids int32 [num_rows]: pred ids in score order; ids may be absent or > max_a = empty mask):
+ *                       iou[r, c] = float32((double)inter / (double)(|a| + |b| - inter)) for GT column c = d_gt_col[b] (int32
+ *                       [max_b + 1], -1 = not a column) -> d_max_iou fp32 [num_rows], d_argmax int32 [num_rows] (the lowest column of
+ *                       the largest fp32 value; 0 for a row without overlap, as np.argmax of a zero row), d_iou fp32 [num_rows,
+ *                       num_cols] the dense matrix (or NULL).  Inputs are m3d_label_overlap's outputs.
+ *   m3d_box_union_overlap_counts  d_counts int64 [3] = Σ(pred > 0), Σ(gt > 0), Σ(pred > 0 & gt > 0 & inside at least one box) over
+ *                       the [depth, height, width] volumes; d_ranges int32 [num_boxes, 6] = half-open (z0, z1, y0, y1, x0, x1), as
+ *                       the host normalised them (clipped again here).  Boxes are painted into a coverage bit-mask (workspace
+ *                       m3d_box_union_overlap_workspace_bytes), then one pass counts.
+ * ------------------------------------------------------------------------------------------------------- */
+size_t m3d_label_overlap_workspace_bytes(int max_a, int64_t capacity);
+int m3d_label_overlap(const void* d_a, const void* d_b, int label_bytes, int64_t num_voxels, int max_a, int max_b, int64_t capacity,
+                      int64_t* d_count_a, int64_t* d_count_b, int32_t* d_pairs, int64_t* d_pair_counts, int64_t* d_status, void* d_ws,
+                      size_t ws_bytes, void* stream);
+int m3d_label_iou_best(const int32_t* d_pairs, const int64_t* d_pair_counts, int64_t num_pairs, const int64_t* d_count_a, int max_a,
+                       const int64_t* d_count_b, int max_b, const int32_t* d_gt_col, int num_cols, const int32_t* d_row_ids, int num_rows,
+                       float* d_max_iou, int32_t* d_argmax, float* d_iou, void* stream);
+size_t m3d_box_union_overlap_workspace_bytes(int64_t num_voxels);
+int m3d_box_union_overlap_counts(const void* d_pred, const void* d_gt, int label_bytes, int depth, int height, int width,
+                                 const int32_t* d_ranges, int num_boxes, int64_t* d_counts, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

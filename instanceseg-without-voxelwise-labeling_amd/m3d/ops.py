@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1649,3 +1649,169 @@ def paint_instances(mask, offsets, boxes, ids, shape):
     vol = torch.full(tuple(shape), -1, dtype=torch.int32, device=mask.device)      # 0xFFFFFFFF sentinel
     paint_instances_into(vol, mask, offsets, boxes, ids)
     return torch.where(vol == -1, torch.zeros_like(vol), vol)
+
+
+# ------------------------------------------------------------------ evaluation of label volumes (csrc/eval3d.hip)
+LABEL_LIMIT = 1 << 24            # labels must lie in [0, 2^24): (a, b) pairs are 48-bit hash keys
+_OVERLAP_DEFAULT_SLOTS = 1 << 16
+
+
+def _label_volume(x):
+    """A label volume as a contiguous CUDA tensor and its label width in bytes: uint16 (what the TIFFs hold) or int32 (what
+    m3d_paint_* produce).  NumPy arrays are uploaded; bool / uint8 widen to uint16, wider integers are range-checked into int32."""
+    if isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x)
+        if x.dtype in (np.bool_, np.uint8):
+            x = x.astype(np.uint16)
+        elif x.dtype not in (np.uint16, np.int32):
+            if x.dtype.kind not in "iu":
+                raise ValueError("label volumes hold integers, got %s" % x.dtype)
+            if x.size and (int(x.min()) < 0 or int(x.max()) >= LABEL_LIMIT):
+                raise M3DError("labels must lie in [0, 2^24)")
+            x = x.astype(np.int32)
+        x = torch.from_numpy(x).cuda()
+    _need_gpu(x)
+    x = x.contiguous()
+    if x.dtype in (torch.bool, torch.uint8):
+        x = x.to(torch.int16)
+    elif x.dtype not in (torch.uint16, torch.int16, torch.int32):
+        if x.numel() and (int(x.min()) < 0 or int(x.max()) >= LABEL_LIMIT):
+            raise M3DError("labels must lie in [0, 2^24)")
+        x = x.to(torch.int32)
+    return x, x.element_size()
+
+
+def _widen(x):
+    """2-byte labels (read as uint16) -> int32"""
+    return x if x.element_size() == 4 else (x.view(torch.int16).to(torch.int32) & 0xFFFF)
+
+
+def _label_max(x, nbytes):
+    """The default declared maximum: the dtype's for uint16 (no extra pass; 64 K counts), the volume's own for int32."""
+    if nbytes == 2:
+        return 65535
+    m = int(x.max()) if x.numel() else 0
+    if m >= LABEL_LIMIT:
+        raise M3DError("label %d >= 2^24" % m)
+    return max(m, 0)
+
+
+class Overlap(tuple):
+    """(count_a int64 [max_a + 1], count_b int64 [max_b + 1], pairs int32 [P, 2] sorted by (a, b), counts int64 [P]) on the device."""
+    __slots__ = ()
+
+    def __new__(cls, count_a, count_b, pairs, counts):
+        return tuple.__new__(cls, (count_a, count_b, pairs, counts))
+
+    count_a = property(lambda s: s[0])
+    count_b = property(lambda s: s[1])
+    pairs = property(lambda s: s[2])
+    counts = property(lambda s: s[3])
+
+
+def label_overlap(a, b, max_a=None, max_b=None, capacity=None):
+    """Contingency table of two label volumes of the same shape (m3d_label_overlap): voxel counts per label on each side and every
+    (a, b) pair with a > 0 and b > 0 that occurs, sorted by (a, b).  max_a / max_b: the declared label maxima (None: 65535 for uint16
+    labels, the volume's maximum for int32); a label above them raises M3DError.  capacity: hash-table slots (a power of two; default
+    64 K): when the pairs do not fit, the call re-launches once with the proven bound min(V, (max_a + 1)(max_b + 1)).
+    Synchronises (the number of pairs is data dependent).  Returns Overlap."""
+    a, na = _label_volume(a)
+    b, nb = _label_volume(b)
+    if a.shape != b.shape:
+        raise ValueError("label volumes differ in shape: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    if na != nb:
+        a, b, na, nb = _widen(a), _widen(b), 4, 4
+    max_a = _label_max(a, na) if max_a is None else int(max_a)
+    max_b = _label_max(b, nb) if max_b is None else int(max_b)
+    if not (0 <= max_a < LABEL_LIMIT and 0 <= max_b < LABEL_LIMIT):
+        raise M3DError("declared label maxima must lie in [0, 2^24)")
+    V = a.numel()
+    bound = max(1, min(V, (max_a + 1) * (max_b + 1)))
+    full = 1 << (2 * bound - 1).bit_length()
+    cap = min(full, _OVERLAP_DEFAULT_SLOTS) if capacity is None else int(capacity)
+    if cap <= 0 or cap & (cap - 1):
+        raise ValueError("capacity must be a power of two")
+    dev = a.device
+    count_a = torch.empty((max_a + 1,), dtype=torch.int64, device=dev)
+    count_b = torch.empty((max_b + 1,), dtype=torch.int64, device=dev)
+    status = torch.empty((2,), dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        wsb = int(lib().m3d_label_overlap_workspace_bytes(max_a, C.c_int64(cap)))
+        ws = torch.empty((max(wsb, 256),), dtype=torch.uint8, device=dev)
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        counts = torch.empty((cap,), dtype=torch.int64, device=dev)
+        check(lib().m3d_label_overlap(_ptr(a), _ptr(b), na, C.c_int64(V), max_a, max_b, C.c_int64(cap), _ptr(count_a), _ptr(count_b),
+                                      _ptr(pairs), _ptr(counts), _ptr(status), _ptr(ws), C.c_size_t(wsb), _stream()), "label_overlap")
+        flags, npairs = (int(v) for v in status.cpu())
+        if flags & 1:
+            raise M3DError("label_overlap: a label lies above the declared maximum (%d, %d) or outside [0, 2^24)" % (max_a, max_b))
+        if not flags & 2:
+            return Overlap(count_a, count_b, pairs[:npairs], counts[:npairs])
+        if attempt == 0:
+            cap = full          # the proven bound, once
+    raise M3DError("label_overlap: the hash table of %d slots was full at the proven bound" % cap)
+
+
+class IouBest(tuple):
+    """(max_iou fp32 [R], argmax int32 [R], iou fp32 [R, G] or None) on the device, gt_ids int64 ndarray [G] (column -> GT id)."""
+    __slots__ = ()
+
+    def __new__(cls, max_iou, argmax, iou, gt_ids):
+        return tuple.__new__(cls, (max_iou, argmax, iou, gt_ids))
+
+    max_iou = property(lambda s: s[0])
+    argmax = property(lambda s: s[1])
+    iou = property(lambda s: s[2])
+    gt_ids = property(lambda s: s[3])
+
+
+def label_iou_best(overlap, row_ids, gt_ids=None, dense=False):
+    """Per row (a pred id; rows in the caller's order, ids may be absent from the volume: an empty mask) the IoU with every GT column,
+    computed as mask_iou_fast does (fp64 counts, one fp32 rounding; m3d_label_iou_best): its largest fp32 value and the lowest column
+    holding it (0 for a row without overlap), and with dense=True the [R, G] matrix.  gt_ids: the column ids (default: the non-zero
+    labels present on the GT side, ascending - eval_instance_segmentation_soma.py:181-182)."""
+    count_a, count_b, pairs, counts = overlap
+    _need_gpu(count_a, count_b, pairs, counts)
+    dev = count_a.device
+    max_a, max_b = count_a.numel() - 1, count_b.numel() - 1
+    if gt_ids is None:
+        cb = count_b.cpu().numpy()
+        gt_ids = np.nonzero(cb[1:] > 0)[0].astype(np.int64) + 1
+    gt_ids = np.asarray(gt_ids, dtype=np.int64).reshape(-1)
+    if gt_ids.size and (gt_ids.min() < 1 or gt_ids.max() > max_b or np.unique(gt_ids).size != gt_ids.size):
+        raise ValueError("gt_ids must be distinct ids in [1, %d]" % max_b)
+    col = np.full((max_b + 1,), -1, dtype=np.int32)
+    col[gt_ids] = np.arange(gt_ids.size, dtype=np.int32)
+    rows = np.asarray(row_ids.cpu() if torch.is_tensor(row_ids) else row_ids).astype(np.int64).reshape(-1)
+    if rows.size and (rows.min() < 1 or rows.max() >= 2 ** 31):
+        raise ValueError("row ids must be positive pred ids")
+    R, G = rows.size, gt_ids.size
+    col_d, rows_d = upload_packed([col, rows.astype(np.int32)], dev)
+    max_iou = torch.empty((R,), dtype=torch.float32, device=dev)
+    argmax = torch.empty((R,), dtype=torch.int32, device=dev)
+    iou = torch.empty((R, G), dtype=torch.float32, device=dev) if dense else None
+    check(lib().m3d_label_iou_best(_ptr(pairs), _ptr(counts), C.c_int64(pairs.shape[0]), _ptr(count_a), max_a, _ptr(count_b), max_b,
+                                   _ptr(col_d), G, _ptr(rows_d), R, _ptr(max_iou), _ptr(argmax), _ptr(iou), _stream()), "label_iou_best")
+    return IouBest(max_iou, argmax, iou, gt_ids)
+
+
+def box_union_overlap_counts(a, b, ranges):
+    """(Σ(a > 0), Σ(b > 0), Σ(a > 0 & b > 0 & inside at least one box)) of two [D, H, W] volumes (m3d_box_union_overlap_counts);
+    ranges int [K, 6] = half-open (z0, z1, y0, y1, x0, x1), already normalised by the caller.  Synchronises; returns int64 ndarray [3]."""
+    a, na = _label_volume(a)
+    b, nb = _label_volume(b)
+    if a.dim() != 3 or a.shape != b.shape:
+        raise ValueError("box_union_overlap_counts needs two [D, H, W] volumes of one shape")
+    if na != nb:
+        a, b, na = _widen(a), _widen(b), 4
+    D, H, W = (int(v) for v in a.shape)
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 6))
+    K = r.shape[0]
+    dev = a.device
+    r_d = upload_packed([r.astype(np.int32)], dev)[0] if K else None
+    out = torch.empty((3,), dtype=torch.int64, device=dev)
+    wsb = int(lib().m3d_box_union_overlap_workspace_bytes(C.c_int64(D * H * W)))
+    ws = torch.empty((max(wsb, 256),), dtype=torch.uint8, device=dev)
+    check(lib().m3d_box_union_overlap_counts(_ptr(a), _ptr(b), na, D, H, W, _ptr(r_d), K, _ptr(out), _ptr(ws), C.c_size_t(wsb), _stream()),
+          "box_union_overlap_counts")
+    return out.cpu().numpy()

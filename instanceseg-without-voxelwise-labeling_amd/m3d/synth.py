@@ -70,3 +70,87 @@ def synth_volume(i, shape=(128, 128, 128)):
         d2 = (zz[z0:z1, y0:y1, x0:x1] - c[0]) ** 2 + (yy[z0:z1, y0:y1, x0:x1] - c[1]) ** 2 + (xx[z0:z1, y0:y1, x0:x1] - c[2]) ** 2
         v[z0:z1, y0:y1, x0:x1] += a * np.exp(-d2 / (2 * s * s))
     return np.clip(v, 0, 65535).astype(np.uint16)
+
+
+def _shifted(m, axis, d):
+    """m moved by d voxels along axis, zero-filled (no wrap)."""
+    out = np.zeros_like(m)
+    src = [slice(None)] * 3
+    dst = [slice(None)] * 3
+    src[axis] = slice(0, m.shape[axis] - d) if d > 0 else slice(-d, None)
+    dst[axis] = slice(d, None) if d > 0 else slice(0, m.shape[axis] + d)
+    out[tuple(dst)] = m[tuple(src)]
+    return out
+
+
+def synth_label_pair(shape, n_gt, seed):
+    """A GT / prediction pair of uint16 label volumes for the evaluation tests and tools/bench_eval.py, and the prediction's score
+    table float64 [P, 2] = [mask_id, score] (what m3d.io.save_segmentation writes for soma).
+    GT: n_gt seeded random spheres filling ~15 % of the volume, ids 1..n_gt, the first sphere winning where spheres overlap.
+    Prediction: per GT instance - dropped (10 %), split in two along z (10 %), shifted by one voxel (40 %), dilated by one voxel
+    (20 %) or copied; plus n_gt // 10 false-positive spheres; ids randomly permuted; distinct scores."""
+    rng = np.random.RandomState(seed)
+    S, H, W = (int(v) for v in shape)
+    r_mean = (0.15 * S * H * W / (max(n_gt, 1) * 4.19)) ** (1.0 / 3.0)
+
+    def spheres(n):
+        c = rng.uniform(0, 1, (n, 3)) * np.array([S, H, W])
+        r = rng.uniform(0.7, 1.3, n) * r_mean
+        return c, r
+
+    def crop(c, r, margin):
+        lo = np.maximum(np.floor(c - r).astype(int) - margin, 0)
+        hi = np.minimum(np.ceil(c + r).astype(int) + margin + 1, (S, H, W))
+        return tuple(slice(a, b) for a, b in zip(lo, hi))
+
+    def ball(c, r, sl):
+        zz, yy, xx = np.ogrid[sl[0], sl[1], sl[2]]
+        return (zz - c[0]) ** 2 + (yy - c[1]) ** 2 + (xx - c[2]) ** 2 <= r * r
+
+    gt = np.zeros((S, H, W), np.uint16)
+    cg, rg = spheres(n_gt)
+    for i in range(n_gt):
+        sl = crop(cg[i], rg[i], 0)
+        g = gt[sl]
+        g[ball(cg[i], rg[i], sl) & (g == 0)] = i + 1
+    pred = np.zeros_like(gt)
+    nxt = 1
+    for i in range(n_gt):
+        sl = crop(cg[i], rg[i], 2)
+        m = gt[sl] == i + 1
+        u = rng.uniform()
+        if u < 0.1 or not m.any():
+            continue
+        parts = [m]
+        if u < 0.2:
+            zc = int(np.round(np.nonzero(m)[0].mean()))
+            top = m.copy()
+            top[zc:] = False
+            parts = [top, m & ~top]
+        elif u < 0.6:
+            parts = [_shifted(m, int(rng.randint(3)), int(rng.choice((-1, 1))))]
+        elif u < 0.8:
+            d = m.copy()
+            for ax in range(3):
+                d |= _shifted(m, ax, 1) | _shifted(m, ax, -1)
+            parts = [d]
+        p = pred[sl]
+        for q in parts:
+            q = q & (p == 0)
+            if q.any():
+                p[q] = nxt
+                nxt += 1
+    cf, rf = spheres(n_gt // 10)
+    for i in range(len(rf)):
+        sl = crop(cf[i], rf[i], 0)
+        p = pred[sl]
+        q = ball(cf[i], rf[i], sl) & (p == 0)
+        if q.any():
+            p[q] = nxt
+            nxt += 1
+    n_pred = nxt - 1
+    perm = np.concatenate(([0], rng.permutation(n_pred) + 1)).astype(np.uint16)
+    pred = perm[pred]
+    ids = np.arange(1, n_pred + 1)
+    scores = (rng.permutation(n_pred) + rng.uniform(0.05, 0.95)) / n_pred
+    return gt, pred, np.stack([ids.astype(np.float64), scores], 1)
