@@ -785,6 +785,33 @@ size_t m3d_box_union_overlap_workspace_bytes(int64_t num_voxels);
 int m3d_box_union_overlap_counts(const void* d_pred, const void* d_gt, int label_bytes, int depth, int height, int width,
                                  const int32_t* d_ranges, int num_boxes, int64_t* d_counts, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Whole-volume connected-component labelling and sphere painting (csrc/label3d.hip): the voxel work of the two baselines of
+ * tools/evaluation/eval_instance_segmentation_soma_ngps.py (DSN :184-187 skimage.measure.label, NGPS :159-183 spheres).
+ *   m3d_label_components   d_in: a [depth, height, width] volume of in_bytes 1 (uint8), 2 (uint16) or 4 (int32); connectivity 6, 18
+ *                          or 26.  A component is a maximal connected set of voxels sharing one NON-ZERO value (skimage.measure.label
+ *                          defaults: equal values connect; 0 is background and gets label 0).  d_labels int32, same shape: 1..K in the
+ *                          raster order (z, y, x) of each component's first voxel, as skimage / cc3d / scipy.ndimage.label number them;
+ *                          *d_num = K (device).  The output is a function of the input alone: bit-identical run to run.  Workspace
+ *                          m3d_label_components_workspace_bytes(num_voxels).  depth * height * width >= 2^31: M3D_EUNSUPPORTED before
+ *                          any launch (parents are int32); an empty dimension, other in_bytes or connectivity: M3D_EINVAL.
+ *   m3d_label_counts       d_counts int64 [num_labels + 1] = voxels per label of an int32 label volume (zero-filled by the call;
+ *                          labels outside [0, num_labels] are not counted).  Runs of equal labels are folded before any atomic.
+ *   m3d_paint_spheres      d_spheres int32 [num_spheres, 4] = (x, y, z, r); sphere i (0-based) paints id i + 1 into the uint16
+ *                          [depth, height, width] volume over ix in [max(1, x - r), min(width, x + r + 1)), likewise y / height and
+ *                          z / depth, where (ix-x)^2 + (iy-y)^2 + (iz-z)^2 <= r^2, only when r >= 6.  Index 0 of every axis is never
+ *                          painted (the script's clamp).  Where spheres overlap the highest index wins (the script's overwrite order),
+ *                          whatever order the launches run in.  The volume is written whole.  num_spheres > 65535: M3D_EINVAL (the
+ *                          script would wrap in its uint16 array).  Workspace m3d_paint_spheres_workspace_bytes(num_voxels).
+ * ------------------------------------------------------------------------------------------------------- */
+size_t m3d_label_components_workspace_bytes(int64_t num_voxels);
+int m3d_label_components(const void* d_in, int in_bytes, int depth, int height, int width, int connectivity, int32_t* d_labels,
+                         int32_t* d_num, void* d_ws, size_t ws_bytes, void* stream);
+int m3d_label_counts(const int32_t* d_labels, int64_t num_voxels, int num_labels, int64_t* d_counts, void* stream);
+size_t m3d_paint_spheres_workspace_bytes(int64_t num_voxels);
+int m3d_paint_spheres(const int32_t* d_spheres, int num_spheres, int depth, int height, int width, uint16_t* d_volume, void* d_ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ SYMBOLS = [
     "m3d_gaussian_filter_u16", "m3d_median_filter3_u16",
     "m3d_cc_workspace_bytes", "m3d_cc_largest_batch", "m3d_binary_closing6_batch", "m3d_paint_instances", "m3d_paint_finish", "m3d_paint_begin",
     "m3d_label_overlap_workspace_bytes", "m3d_label_overlap", "m3d_label_iou_best", "m3d_box_union_overlap_workspace_bytes", "m3d_box_union_overlap_counts",
+    "m3d_label_components_workspace_bytes", "m3d_label_components", "m3d_label_counts", "m3d_paint_spheres_workspace_bytes", "m3d_paint_spheres",
 ]
 
 
@@ -59,7 +60,8 @@ def _load(path):
               "m3d_conv3d_packed_weight_bytes", "m3d_conv3d_x3_packed_bytes", "m3d_conv3d_x3f_packed_bytes", "m3d_conv3d_zw_packed_bytes", "m3d_reduce_minmax_multi_workspace_bytes", "m3d_conv3d_x3_workspace_bytes", "m3d_reduce_min_workspace_bytes", "m3d_reduce_min_multi_workspace_bytes", "m3d_norm1_workspace_bytes", "m3d_prm_small_dgrad_packed_bytes", "m3d_prm_small_dgrad_f16_packed_bytes", "m3d_prm_small_dgrad_f16_workspace_bytes", "m3d_linear_workspace_bytes", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_workspace_bytes", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_bf16x3_w32_workspace_bytes", "m3d_linear_bf16x3_roi_workspace_bytes", "m3d_mask_paste3d_workspace_bytes", "m3d_generate_proposals3d_batched_workspace_bytes",
               "m3d_box_results3d_batched_workspace_bytes", "m3d_nms3d_batched_workspace_bytes", "m3d_otsu2d_workspace_bytes",
               "m3d_cc_workspace_bytes", "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_stem_wino_packed_weight_bytes",
-              "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes"):
+              "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
+              "m3d_paint_spheres_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

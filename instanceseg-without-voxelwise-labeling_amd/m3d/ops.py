@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1815,3 +1815,87 @@ def box_union_overlap_counts(a, b, ranges):
     check(lib().m3d_box_union_overlap_counts(_ptr(a), _ptr(b), na, D, H, W, _ptr(r_d), K, _ptr(out), _ptr(ws), C.c_size_t(wsb), _stream()),
           "box_union_overlap_counts")
     return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------ whole-volume labelling, sphere painting (csrc/label3d.hip)
+_COMPONENT_DTYPES = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.int32): 4}
+
+
+def _component_volume(x):
+    """A [D, H, W] volume of uint8 / uint16 / int32 (bool counts as uint8) as a contiguous CUDA tensor and its element size.  Other
+    dtypes and other ranks raise ValueError: nothing is converted silently, since equal VALUES are what connects."""
+    if isinstance(x, np.ndarray):
+        if x.dtype == np.bool_:
+            x = x.view(np.uint8)
+        if x.dtype not in _COMPONENT_DTYPES:
+            raise ValueError("label_components takes bool, uint8, uint16 or int32 volumes, got %s" % x.dtype)
+        if x.ndim != 3:
+            raise ValueError("label_components takes a [D, H, W] volume, got %d dimensions" % x.ndim)
+        return torch.from_numpy(np.ascontiguousarray(x)).cuda(), _COMPONENT_DTYPES[x.dtype]
+    if not torch.is_tensor(x):
+        raise ValueError("label_components takes a NumPy array or a CUDA tensor")
+    if x.dtype == torch.bool:
+        x = x.to(torch.uint8)
+    if x.dtype not in (torch.uint8, torch.uint16, torch.int16, torch.int32):
+        raise ValueError("label_components takes bool, uint8, uint16 or int32 volumes, got %s" % x.dtype)
+    if x.dim() != 3:
+        raise ValueError("label_components takes a [D, H, W] volume, got %d dimensions" % x.dim())
+    _need_gpu(x)
+    return x.contiguous(), x.element_size()
+
+
+def label_counts(labels, num_labels):
+    """Voxels per label of an int32 CUDA label volume: int64 [num_labels + 1] on the device (m3d_label_counts).  No synchronisation."""
+    _need_gpu(labels)
+    if labels.dtype != torch.int32:
+        raise ValueError("label_counts takes int32 labels")
+    labels = labels.contiguous()
+    counts = torch.empty((int(num_labels) + 1,), dtype=torch.int64, device=labels.device)
+    check(lib().m3d_label_counts(_ptr(labels), C.c_int64(labels.numel()), int(num_labels), _ptr(counts), _stream()), "label_counts")
+    return counts
+
+
+def label_components(volume, connectivity=26, return_counts=False):
+    """Connected components of a whole [D, H, W] volume with skimage.measure.label's default semantics (m3d_label_components): a
+    component is a maximal `connectivity`-connected (6, 18 or 26) set of voxels sharing one non-zero value; 0 is background.  Labels
+    are 1..K in the raster order of each component's first voxel.  volume: NumPy or CUDA, bool / uint8 / uint16 / int32.
+    Returns (labels int32 CUDA [D, H, W], K) and, with return_counts, counts int64 CUDA [K + 1].  Synchronises once, for K."""
+    x, nbytes = _component_volume(volume)
+    D, H, W = (int(v) for v in x.shape)
+    return _label_components_raw(x, nbytes, D, H, W, connectivity, return_counts)
+
+
+def _label_components_raw(x, nbytes, D, H, W, connectivity, return_counts=False):
+    """The call itself; the argument checks are the library's (tests reach them with shape arguments alone)."""
+    V = D * H * W
+    dev = x.device
+    big = V >= 2 ** 31 or V <= 0                       # refused by the library before any launch: nothing of that size is allocated
+    labels = torch.empty((1,) if big else (D, H, W), dtype=torch.int32, device=dev)
+    num = torch.empty((1,), dtype=torch.int32, device=dev)
+    wsb = 256 if big else int(lib().m3d_label_components_workspace_bytes(C.c_int64(V)))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    check(lib().m3d_label_components(_ptr(x), int(nbytes), D, H, W, int(connectivity), _ptr(labels), _ptr(num), _ptr(ws), C.c_size_t(wsb),
+                                     _stream()), "label_components")
+    K = int(num.item())
+    if return_counts:
+        return labels, K, label_counts(labels, K)
+    return labels, K
+
+
+def paint_spheres(spheres, shape):
+    """NeuroGPS soma lists as a label volume (m3d_paint_spheres; eval_instance_segmentation_soma_ngps.py:160-183): spheres int [N, 4] =
+    (x, y, z, r), sphere i paints id i + 1 where r >= 6, never at index 0 of an axis, the highest index winning where spheres overlap.
+    Returns uint16 CUDA [S, H, W].  More than 65 535 spheres raise M3DError."""
+    sp = np.ascontiguousarray(np.asarray(spheres.cpu() if torch.is_tensor(spheres) else spheres, dtype=np.int64).reshape(-1, 4))
+    if sp.size and (sp.min() < -2 ** 31 or sp.max() >= 2 ** 31):
+        raise ValueError("sphere fields must fit int32")
+    S, H, W = (int(v) for v in shape)
+    N = sp.shape[0]
+    dev = torch.device("cuda")
+    sp_d = upload_packed([sp.astype(np.int32)], dev)[0] if N else None
+    V = S * H * W
+    out = torch.empty((S, H, W) if 0 < V < 2 ** 31 else (1,), dtype=torch.uint16, device=dev)
+    wsb = int(lib().m3d_paint_spheres_workspace_bytes(C.c_int64(V))) if 0 < V < 2 ** 31 else 256
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    check(lib().m3d_paint_spheres(_ptr(sp_d), N, S, H, W, _ptr(out), _ptr(ws), C.c_size_t(wsb), _stream()), "paint_spheres")
+    return out

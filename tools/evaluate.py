@@ -8,6 +8,11 @@
         evaluation_nuclei_f1score.py: {name}.pkl (or .npy) detections against {SRC_DIR}/{track}_GT/BBOX/bbox_NNN.txt
   python tools/evaluate.py nuclei-seg RES_DIR SRC_DIR TEST_TXT [--track 02] [--ovthresh 0.4] [--pkl]
         evaluation_nuclei_f1score_seg.py: {name}.tif + {name}.npy against {SRC_DIR}/{track}_GT/SEG/man_segNNN.tif
+  python tools/evaluate.py soma-dsn PRED_DIR GT_DIR [--iou-thresh 0.3] [--names a b ...]
+        eval_instance_segmentation_soma_ngps.py, flag DSN: the connected components of the voxelwise segmentation pred/{name}.tif as
+        instances, against gt/{name}/{name}.tif
+  python tools/evaluate.py soma-ngps SWC_DIR GT_DIR [--iou-thresh 0.3] [--names a b ...]
+        the same script, flag NGPS: the NeuroGPS soma list swc/{name}.swc painted as spheres
 Prints the figures the reference scripts print."""
 import argparse
 import os
@@ -20,11 +25,12 @@ sys.path.insert(0, os.path.join(ROOT, "instanceseg-without-voxelwise-labeling_am
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
-    s = sub.add_parser("soma")
-    s.add_argument("pred_dir")
-    s.add_argument("gt_dir")
-    s.add_argument("--iou-thresh", type=float, default=0.3)
-    s.add_argument("--names", nargs="*")
+    for name in ("soma", "soma-dsn", "soma-ngps"):
+        s = sub.add_parser(name)
+        s.add_argument("pred_dir")
+        s.add_argument("gt_dir")
+        s.add_argument("--iou-thresh", type=float, default=0.3)
+        s.add_argument("--names", nargs="*")
     for name in ("nuclei-det", "nuclei-seg"):
         n = sub.add_parser(name)
         n.add_argument("res_dir")
@@ -42,6 +48,14 @@ def main(argv=None):
     if a.cmd == "soma":
         names = a.names if a.names else sorted(os.listdir(a.gt_dir))
         res = E.eval_instance_segmentation_soma(a.pred_dir, a.gt_dir, names, iou_thresh=a.iou_thresh)
+        for name, v in zip(names, res["per_image_ap"]):
+            print("img {}: ap {}".format(name, v))
+        print("ap: {}".format(res["ap"]))
+    elif a.cmd in ("soma-dsn", "soma-ngps"):
+        from m3d import evaluate_baselines as EB
+        names = a.names if a.names else sorted(os.listdir(a.gt_dir))
+        res = EB.eval_instance_segmentation_soma("DSN" if a.cmd == "soma-dsn" else "NGPS", a.pred_dir, a.gt_dir, names,
+                                                 iou_thresh=a.iou_thresh)
         for name, v in zip(names, res["per_image_ap"]):
             print("img {}: ap {}".format(name, v))
         print("ap: {}".format(res["ap"]))
