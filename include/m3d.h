@@ -812,6 +812,59 @@ size_t m3d_paint_spheres_workspace_bytes(int64_t num_voxels);
 int m3d_paint_spheres(const int32_t* d_spheres, int num_spheres, int depth, int height, int width, uint16_t* d_volume, void* d_ws,
                       size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * RPN training step (csrc/rpn_train.hip): what lib/roi_data/rpn.py:120-279 (_get_rpn_blobs) does on the host per sample and
+ * lib/modeling/rpn_heads.py:140-170 (single_scale_rpn_losses, sigmoid branch) + lib/utils/net.py:15-32 (smooth L1, beta 1/9) do
+ * with its four dense blobs.  Single-scale (no FPN).  The anchor field is the wide cube of data_utils.py:50-102: field_size^3
+ * positions (z-major, x-minor), num_cell_anchors anchors each, anchor = fp64 cell anchor + position * stride, rounded to fp32;
+ * "flat field index" i = position * A + a.  A "wide index" addresses the [A, F, F, F] blob of rpn.py:260-261: a * F^3 + position.
+ * Limits: A <= 64, F^3 A < 2^32 - 1024, batch_per_im <= 4096 (M3D_EUNSUPPORTED beyond, before any launch).
+ *   m3d_rpn_targets   cell_anchors: HOST fp64 [A, 6].  d_gt fp32 [num_gt, 6], d_dc fp32 [num_dc, 6] ("don't care" boxes, may be NULL
+ *                     with num_dc 0).  Inside test of rpn.py:124-140 (straddle_thresh < 0: every anchor).  IoU as
+ *                     m3d_bbox_overlaps3d.  fg (rpn.py:169-177): IoU equal (fp32) to its box's maximum over the inside anchors - a
+ *                     box that overlaps no inside anchor has maximum 0 and so makes every inside anchor with IoU 0 fg, as in the
+ *                     reference - or maximum IoU >= positive_overlap.  Thresholds are compared as fp32 (NumPy 2 compares an fp32
+ *                     array with a Python scalar in fp32).  Sampling is a pure function of `seed`: with fin() the splitmix64
+ *                     finaliser (x * 0x9E3779B97F4A7C15, two xor-shift-multiplies, a last xor-shift), stream = fin(seed) and
+ *                     key(i) = upper 32 bits of fin(stream + i), so that consecutive seeds give unrelated draws.
+ *                     If more than num_fg anchors are fg, the num_fg with the smallest
+ *                     (key(flat field index), flat field index) stay (rpn.py:189-196).  bg candidates (rpn.py:202-203): inside,
+ *                     maximum IoU < negative_overlap against d_gt and against d_dc, n of them in ascending field order; only if
+ *                     n > num_bg = batch_per_im - #fg, draw j = 0 .. num_bg-1 labels candidate (key(2^40 + j) * n) >> 32 as bg
+ *                     (with replacement; a draw that hits a sampled fg anchor turns it into bg, rpn.py:204-206).  num_gt = 0 (the
+ *                     reference raises NameError): no fg, every inside anchor is a candidate unless a d_dc box excludes it.
+ *                     Outputs (device): d_fg_index int64 [num_fg] / d_bg_index int64 [batch_per_im]: wide indices of the anchors
+ *                     labelled 1 / 0, ascending, -1 beyond the count; d_target_index int64 [num_fg] + d_targets fp32 [num_fg, 6]:
+ *                     the fg set as sampled BEFORE the bg draws and its bbox_transform_inv_3d targets against the first-argmax box
+ *                     (boxes_3d.py:228-270, unit weights; dx,dy,dz fp32 in the reference's operation order, dw,dh,ds = fp32(log in
+ *                     fp64)), rows beyond the count -1 / 0; d_counts int64 [8] = #fg, #bg, #target rows, num_examples (rpn.py:229),
+ *                     inside anchors, fg before sampling, bg candidates, bg draws.  Integer atomics and value-ordered selection only:
+ *                     bit-identical run to run.  Workspace m3d_rpn_targets_workspace_bytes(A, F, num_gt, batch_per_im, num_fg).
+ *   m3d_rpn_targets_wide  expands one image's outputs into the reference's dense blobs (rpn.py:260-278): d_labels int32 [A,F,F,F]
+ *                     (-1 / 0 / 1), d_targets_wide, d_inside_wide, d_outside_wide fp32 [6A,F,F,F] (channel 6 a + component);
+ *                     outside weight = fp32(1.0 / num_examples) on labels 0 and 1, inside weight 1 on label 1 (rpn.py:219-231).
+ *   m3d_rpn_loss      d_cls_logits fp32 [B,A,s,h,w], d_bbox_pred fp32 [B,6A,s,h,w]; the targets of the B images stacked:
+ *                     d_fg_index [B,num_fg], d_bg_index [B,batch_per_im], d_target_index [B,num_fg], d_targets [B,num_fg,6],
+ *                     d_counts [B,8].  Only sampled anchors inside the crop [:s,:h,:w] of the field count (rpn_heads.py:145-150).
+ *                     d_losses fp32 [2] = loss_cls = sum bce_with_logits / W with W = labelled in-crop anchors over the batch (0 if
+ *                     W = 0, where the reference divides 0 by 0), loss_bbox = sum out * smoothL1(p - t) / B.  d_grad_logits /
+ *                     d_grad_pred (input shapes, written whole): (sigmoid(x) - y) / W and out * clamp((p - t) / beta, -1, 1) / B at
+ *                     those anchors, exactly 0 elsewhere.  One workgroup, fixed summation tree: bit-identical run to run.
+ * ------------------------------------------------------------------------------------------------------- */
+size_t m3d_rpn_targets_workspace_bytes(int num_cell_anchors, int field_size, int num_gt, int batch_per_im, int num_fg);
+int m3d_rpn_targets(const double* cell_anchors, int num_cell_anchors, int field_size, int stride, const float* d_gt, int num_gt,
+                    const float* d_dc, int num_dc, double im_slices, double im_height, double im_width, double straddle_thresh,
+                    double positive_overlap, double negative_overlap, int batch_per_im, int num_fg, uint64_t seed,
+                    int64_t* d_fg_index, int64_t* d_bg_index, int64_t* d_target_index, float* d_targets, int64_t* d_counts,
+                    void* d_ws, size_t ws_bytes, void* stream);
+int m3d_rpn_targets_wide(const int64_t* d_fg_index, const int64_t* d_bg_index, const int64_t* d_target_index, const float* d_targets,
+                         const int64_t* d_counts, int num_cell_anchors, int field_size, int num_fg, int batch_per_im,
+                         int32_t* d_labels, float* d_targets_wide, float* d_inside_wide, float* d_outside_wide, void* stream);
+int m3d_rpn_loss(const float* d_cls_logits, const float* d_bbox_pred, int batch, int num_cell_anchors, int slices, int height, int width,
+                 int field_size, const int64_t* d_fg_index, const int64_t* d_bg_index, const int64_t* d_target_index,
+                 const float* d_targets, const int64_t* d_counts, int num_fg, int batch_per_im, float* d_losses, float* d_grad_logits,
+                 float* d_grad_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

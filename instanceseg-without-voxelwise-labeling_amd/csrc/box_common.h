@@ -101,4 +101,28 @@ __device__ inline float det_volume(const float* d) {
   return ab * c;
 }
 
+// One entry of the IoU matrix (cython_bbox_3d.pyx:46-79): the arithmetic of box_ops.hip's overlaps_kernel, expression for expression
+// (fp32 intersection, fp64 union and divide, fp32 result; a pair that does not intersect is exactly +0.0 without a divide).
+// q_volume is the query box's volume as that kernel rounds it: iou_query_volume(q).
+__device__ inline float iou_query_volume(const float* q) {
+  return (float)((((double)(q[3] - q[0]) + 1.0) * ((double)(q[4] - q[1]) + 1.0)) * ((double)(q[5] - q[2]) + 1.0));   // pyx:52-56
+}
+__device__ inline float iou3d(const float* b, const float* q, float q_volume) {
+  float r = 0.f;                                                                        // pyx:46
+  const float iw = (float)((double)(fmin32(b[3], q[3]) - fmax32(b[0], q[0])) + 1.0);   // pyx:58-61
+  if (iw > 0) {
+    const float ih = (float)((double)(fmin32(b[4], q[4]) - fmax32(b[1], q[1])) + 1.0);
+    if (ih > 0) {
+      const float is = (float)((double)(fmin32(b[5], q[5]) - fmax32(b[2], q[2])) + 1.0);
+      if (is > 0) {
+        float inter = iw * ih; inter = inter * is;
+        const double uv = ((((double)(b[3] - b[0]) + 1.0) * ((double)(b[4] - b[1]) + 1.0)) * ((double)(b[5] - b[2]) + 1.0) +
+                           (double)q_volume) - (double)inter;                           // pyx:73-78
+        r = (float)((double)inter / uv);                                                // pyx:79
+      }
+    }
+  }
+  return r;
+}
+
 }  // namespace m3dbox

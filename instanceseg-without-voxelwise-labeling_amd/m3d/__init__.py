@@ -5,3 +5,4 @@ an op without the built library, or calling one without a GPU tensor, raises.
 """
 from . import _lib  # noqa: F401
 from .ops import *  # noqa: F401,F403
+from .train import RpnTrainCfg, RpnTargets, rpn_targets, rpn_losses  # noqa: E402,F401

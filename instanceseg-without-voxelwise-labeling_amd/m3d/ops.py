@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1899,3 +1899,61 @@ def paint_spheres(spheres, shape):
     ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
     check(lib().m3d_paint_spheres(_ptr(sp_d), N, S, H, W, _ptr(out), _ptr(ws), C.c_size_t(wsb), _stream()), "paint_spheres")
     return out
+
+
+# ------------------------------------------------------------------ RPN training step (csrc/rpn_train.hip)
+def rpn_target_sets(cell_anchors, field_size, stride, gt_boxes, dc_boxes, im_size, straddle_thresh, positive_overlap, negative_overlap,
+                batch_per_im, num_fg, seed):
+    """m3d_rpn_targets for one image: gt_boxes / dc_boxes CUDA fp32 [K,6] (dc_boxes may be None), im_size = (slices, height, width),
+    cell_anchors host fp64 [A,6].  -> (fg_index int64 [num_fg], bg_index int64 [batch_per_im], target_index int64 [num_fg],
+    targets fp32 [num_fg,6], counts int64 [8]), all on the device, no synchronisation."""
+    _need_gpu(gt_boxes, dc_boxes)
+    gt = _f32c(gt_boxes).reshape(-1, 6)
+    dc = _f32c(dc_boxes).reshape(-1, 6) if dc_boxes is not None else None
+    cell = np.ascontiguousarray(cell_anchors, np.float64).reshape(-1, 6)
+    A, F, dev = cell.shape[0], int(field_size), gt.device
+    fg = torch.empty((num_fg,), dtype=torch.int64, device=dev)
+    bg = torch.empty((batch_per_im,), dtype=torch.int64, device=dev)
+    tix = torch.empty((num_fg,), dtype=torch.int64, device=dev)
+    tg = torch.empty((num_fg, 6), dtype=torch.float32, device=dev)
+    counts = torch.empty((8,), dtype=torch.int64, device=dev)
+    L = lib()
+    nbytes = L.m3d_rpn_targets_workspace_bytes(A, F, gt.shape[0], int(batch_per_im), int(num_fg))
+    ws = _workspace(max(int(nbytes), 1), dev, "rpn_targets")
+    S, H, W = [float(v) for v in im_size]
+    check(L.m3d_rpn_targets(cell.ctypes.data_as(C.POINTER(C.c_double)), A, F, int(stride), _ptr(gt if gt.shape[0] else None), gt.shape[0],
+                            _ptr(dc if dc is not None and dc.shape[0] else None), 0 if dc is None else dc.shape[0], C.c_double(S),
+                            C.c_double(H), C.c_double(W), C.c_double(float(straddle_thresh)), C.c_double(float(positive_overlap)),
+                            C.c_double(float(negative_overlap)), int(batch_per_im), int(num_fg), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                            _ptr(fg), _ptr(bg), _ptr(tix), _ptr(tg), _ptr(counts), _ptr(ws), C.c_size_t(ws.numel()), _stream()),
+          "rpn_targets")
+    return fg, bg, tix, tg, counts
+
+
+def rpn_target_blobs(fg_index, bg_index, target_index, targets, counts, num_cell_anchors, field_size):
+    """The reference's four dense blobs (rpn.py:260-278): labels int32 [1,A,F,F,F], targets / inside / outside weights fp32 [1,6A,F,F,F]."""
+    _need_gpu(fg_index, bg_index, target_index, targets, counts)
+    A, F, dev = int(num_cell_anchors), int(field_size), bg_index.device
+    lab = torch.empty((1, A, F, F, F), dtype=torch.int32, device=dev)
+    tw, iw, ow = (torch.empty((1, 6 * A, F, F, F), dtype=torch.float32, device=dev) for _ in range(3))
+    check(lib().m3d_rpn_targets_wide(_ptr(fg_index), _ptr(bg_index), _ptr(target_index), _ptr(targets), _ptr(counts), A, F,
+                                     fg_index.shape[0], bg_index.shape[0], _ptr(lab), _ptr(tw), _ptr(iw), _ptr(ow), _stream()),
+          "rpn_targets_wide")
+    return lab, tw, iw, ow
+
+
+def rpn_loss_grad(cls_logits, bbox_pred, field_size, fg_index, bg_index, target_index, targets, counts):
+    """m3d_rpn_loss: cls_logits [B,A,s,h,w], bbox_pred [B,6A,s,h,w]; the per-image outputs of rpn_target_sets stacked along a leading B.
+    -> (losses fp32 [2] = (loss_cls, loss_bbox), d loss_cls / d cls_logits, d loss_bbox / d bbox_pred)."""
+    _need_gpu(cls_logits, bbox_pred, fg_index, bg_index, target_index, targets, counts)
+    x, p = _f32c(cls_logits), _f32c(bbox_pred)
+    B, A, s, h, w = x.shape
+    if tuple(p.shape) != (B, 6 * A, s, h, w) or fg_index.shape[0] != B or bg_index.shape[0] != B or counts.shape != (B, 8):
+        raise M3DError("rpn_loss_grad: bbox_pred must be [B,6A,s,h,w] and the targets stacked over the same B images")
+    fg_index, bg_index, target_index, targets, counts = (t.contiguous() for t in (fg_index, bg_index, target_index, targets, counts))
+    losses = torch.empty((2,), dtype=torch.float32, device=x.device)
+    gx, gp = torch.empty_like(x), torch.empty_like(p)
+    check(lib().m3d_rpn_loss(_ptr(x), _ptr(p), B, A, s, h, w, int(field_size), _ptr(fg_index), _ptr(bg_index), _ptr(target_index),
+                             _ptr(targets), _ptr(counts), fg_index.shape[1], bg_index.shape[1], _ptr(losses), _ptr(gx), _ptr(gp), _stream()),
+          "rpn_loss")
+    return losses, gx, gp

@@ -72,6 +72,22 @@ def synth_volume(i, shape=(128, 128, 128)):
     return np.clip(v, 0, 65535).astype(np.uint16)
 
 
+def synth_volume_boxes(i, shape=(128, 128, 128), k=2.0):
+    """Ground-truth boxes fp32 [40, 6] (x1, y1, z1, x2, y2, z2) of synth_volume(i, shape)'s blobs: centre -+ k sigma, rounded and clipped to
+    the volume (the same random sequence, replayed without painting)."""
+    rng = np.random.RandomState(1234 + i)
+    S, H, W = shape
+    rng.normal(100, 10, shape)
+    out = np.zeros((40, 6), np.float32)
+    for n in range(40):
+        c = rng.uniform(0, 1, 3) * np.array(shape)
+        s = rng.uniform(4, 8)
+        rng.uniform(300, 900)
+        lo, hi = np.round(c - k * s), np.round(c + k * s)
+        out[n] = [max(lo[2], 0), max(lo[1], 0), max(lo[0], 0), min(hi[2], W - 1), min(hi[1], H - 1), min(hi[0], S - 1)]
+    return out
+
+
 def _shifted(m, axis, d):
     """m moved by d voxels along axis, zero-filled (no wrap)."""
     out = np.zeros_like(m)

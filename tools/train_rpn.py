@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Demo: train an RPN from boxes only, on one synthetic tile.
+
+A tile of m3d.synth.synth_volume (Gaussian blobs; ground-truth boxes = centre -+ 2 sigma), the reference-shaped body
+(Conv3d + BatchNorm3d(eval) + ReLU + MaxPool3d, lib/modeling/DSN.py) and RPN head (rpn_heads.py:38-74) as plain torch.nn modules
+whose convolutions run on libm3d through m3d.compat.install(), m3d.rpn_targets + m3d.rpn_losses on the device, torch.optim.SGD.
+Prints both losses per step.  One fixed sample, so the loss must fall; this is not a training driver (no data loading, schedule or
+checkpoints)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "instanceseg-without-voxelwise-labeling_amd"))
+
+
+def build_model(num_anchors, width):
+    import torch.nn as nn
+
+    def block(cin, cout, k):
+        return [nn.Conv3d(cin, cout, k, 1, k // 2), nn.BatchNorm3d(cout), nn.ReLU(inplace=True)]
+    w = width
+    body = nn.Sequential(*block(1, w, 5), nn.MaxPool3d(2), *block(w, 2 * w, 3), *block(2 * w, 2 * w, 3), nn.MaxPool3d(2),
+                         *block(2 * w, 4 * w, 3), *block(4 * w, 4 * w, 3), nn.MaxPool3d(2), *block(4 * w, 8 * w, 3), *block(8 * w, 8 * w, 3))
+
+    class Head(nn.Module):
+        def __init__(self, dim):
+            super().__init__()
+            self.RPN_conv = nn.Conv3d(dim, dim, 3, 1, 1)
+            self.RPN_cls_score = nn.Conv3d(dim, num_anchors, 1, 1, 0)
+            self.RPN_bbox_pred = nn.Conv3d(dim, 6 * num_anchors, 1, 1, 0)
+            for m in (self.RPN_conv, self.RPN_cls_score, self.RPN_bbox_pred):   # rpn_heads.py:68-74
+                nn.init.normal_(m.weight, std=0.01)
+                nn.init.constant_(m.bias, 0)
+
+        def forward(self, x):
+            import torch.nn.functional as F
+            h = F.relu(self.RPN_conv(x))
+            return self.RPN_cls_score(h), self.RPN_bbox_pred(h)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.body, self.head = body, Head(8 * w)
+
+        def forward(self, x):
+            return self.head(self.body(x))
+    return Net()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--tile", type=int, nargs=3, default=(32, 64, 64), help="slices height width, multiples of 8")
+    ap.add_argument("--width", type=int, default=16, help="channels of the first conv (the reference has 32)")
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    import torch
+    import m3d
+    import m3d.compat
+    from m3d.synth import synth_volume, synth_volume_boxes
+    assert torch.cuda.is_available(), "train_rpn needs a GPU"
+    m3d.compat.install()
+    torch.manual_seed(a.seed)
+    tile = tuple(a.tile)
+    cfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile))
+    vol = synth_volume(0, tile).astype(np.float32)
+    x = torch.from_numpy((vol - vol.mean()) / vol.std())[None, None].cuda()
+    gt = torch.from_numpy(synth_volume_boxes(0, tile)).cuda()
+    net = build_model(cfg.num_anchors, a.width).cuda()
+    net.train()
+    for m in net.modules():                       # the reference trains with frozen BatchNorm statistics
+        if isinstance(m, torch.nn.BatchNorm3d):
+            m.eval()
+    opt = torch.optim.SGD(net.parameters(), lr=a.lr, momentum=0.9)
+    for step in range(a.steps):
+        targets = m3d.rpn_targets(gt, tile, cfg, seed=1000 * a.seed + step)       # one sampling seed per step
+        logits, pred = net(x)
+        loss_cls, loss_bbox = m3d.rpn_losses(logits, pred, targets)
+        opt.zero_grad()
+        (loss_cls + loss_bbox).backward()
+        opt.step()
+        print("step %d loss_cls %.6f loss_bbox %.6f total %.6f" % (step, loss_cls.item(), loss_bbox.item(), loss_cls.item() + loss_bbox.item()),
+              flush=True)
+
+
+if __name__ == "__main__":
+    main()
