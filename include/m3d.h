@@ -593,6 +593,10 @@ int m3d_conv3d_zw_supported(int cin, int cout, int depth, int height, int width,
 size_t m3d_conv3d_zw_packed_bytes(int cin, int cout);
 int m3d_conv3d_zw_pack(const float* d_weight, int cin, int cout, void* d_packed, void* stream);
 int m3d_conv3d_zw_slots(void);
+/* Workgroup units of an m3d_conv3d_zw_forward launch on this shape ((64 output channels) x (32 x 4 x 2 voxels, or 16 x 8 x 2 on maps
+ * narrower than 24) per unit): the library's own tile choice, for callers that choose between this kernel and the fp32 ones by how well a
+ * launch fills the chip (host only; says nothing about m3d_conv3d_zw_supported). */
+long long m3d_conv3d_zw_launch_units(int batch, int cin, int cout, int depth, int height, int width);
 int m3d_conv3d_zw_bound_of(const float* d_x, long long n, float* d_slots, void* stream);
 int m3d_conv3d_zw_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
                           int width, const float* d_scale, const float* d_shift, int relu, int pool, const float* d_in_max,

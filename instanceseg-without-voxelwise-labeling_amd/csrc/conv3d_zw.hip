@@ -637,6 +637,13 @@ int launch_zw(ZwArgs a, hipStream_t st) {
   return m3d::check_launch("conv3d_zw");
 }
 
+// workgroup units of a launch_zw<XB, ...> launch (what it computes as `units`), for m3d_conv3d_zw_launch_units
+template <int XB>
+long long zw_units(int batch, int cout, int depth, int height, int width) {
+  using C = ZwCfg<XB>;
+  return (long long)batch * ((cout + 63) / 64) * ((width + C::TX - 1) / C::TX) * ((height + C::TY - 1) / C::TY) * ((depth + C::TZ - 1) / C::TZ);
+}
+
 inline size_t zw_plane_bytes(int cin, int cout) { return (size_t)((cout + 63) / 64) * (cin / 16) * 9 * ZW_STEP_UNITS * 16; }
 
 }  // namespace
@@ -777,4 +784,10 @@ M3D_API int m3d_conv3d_zw_forward(const float* d_in, const void* d_packed, float
   if (pool) return launch_zw<32, true>(a, st);
   if (width >= 24) return launch_zw<32, false>(a, st);
   return launch_zw<16, false>(a, st);
+}
+
+/* host only: the same width rule as the dispatch above (the fused pool needs width >= 24, so it is the 32-wide tile too) */
+M3D_API long long m3d_conv3d_zw_launch_units(int batch, int cin, int cout, int depth, int height, int width) {
+  (void)cin;
+  return width >= 24 ? zw_units<32>(batch, cout, depth, height, width) : zw_units<16>(batch, cout, depth, height, width);
 }

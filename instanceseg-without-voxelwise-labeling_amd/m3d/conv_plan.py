@@ -1,0 +1,98 @@
+"""Which kernel runs a backbone / RPN convolution, decided in one place, and the per-layer object that runs the decision.
+
+`plan_conv` is the only place the order of the kernel families lives (DESIGN.md "Conv dispatch"): the detection path
+(DetectorM3D.body_layer / rpn), bench.py's roofline bookkeeping (DetectorM3D.conv_work) and the PRM forward
+(PRMEngine.forward_response) all ask it, each with its own needs, and run what it says by calling the layer's `LayerConv`."""
+import collections
+
+import torch
+
+from . import ops
+
+# The Winograd, stem and f16x2 kernels address one batch item with 32-bit buffer offsets: an item of this many bytes or more runs on
+# the direct kernel.
+ITEM_LIMIT = 0x7FFFFFFF
+# The f16x2 kernel runs one workgroup per (64 channels, 32 x 4 x 2 voxels): maps that give it less than ~0.8 of a round of the chip's
+# 256 CUs stay with the fp32 Winograd kernels (split-K over workgroups).
+ZW_MIN_UNITS = 200
+
+DIRECT, STEM, ZW = "direct", "winograd F(2,5)x stem", "f16x2 F(2,3)z"         # kinds: keys of DetectorM3D.ISSUED_FRACTION
+
+# kind: the kernel family; fused: the layer's max-pool runs in the conv launch (else ops.maxpool3d_2x follows); sweep: the kernel scales
+# its input by the input's operand bound (DetectorM3D._bound: left on the tensor by the launch that produced it, else one sweep)
+Plan = collections.namedtuple("Plan", "kind fused sweep")
+
+
+def plan_conv(layer, shape, argmax=False, f16=True, winograd=True):
+    """The kernel for `layer` (a LayerConv: cin, cout, k, pool and the packs the switches M3D_WINO / M3D_CONV_F16 gave it) on an input
+    [B, cin, D, H, W], shape = (B, D, H, W).  Host queries of the library only.  The caller's needs:
+    argmax    PRM mode: a pooled layer must deliver the pool's arg-max.  Only the direct kernels (fused, or ops.maxpool3d_2x behind the
+              conv) and the 2-D Winograd family's fused pool do: such a layer never runs on f16x2, on un-fused Winograd or on the F(2,5) stem
+    f16       the f16x2 kernel may run this layer (the PRM forward keeps the RPN conv off it)
+    winograd  False: direct kernels only (PRMEngine(wino_forward=False))"""
+    B, D, H, W = (int(v) for v in shape)
+    pool = layer.pool
+    if winograd and layer.cin * D * H * W * 4 < ITEM_LIMIT:
+        if layer.stem is not None and not argmax and layer.stem.supports(W):
+            return Plan(STEM, pool, False)
+        zw, wino = layer.zw, layer.wino
+        if zw is not None and f16 and not (argmax and pool) and zw.supports((D, H, W)) and zw.units((B, layer.cin, D, H, W)) >= ZW_MIN_UNITS:
+            return Plan(ZW, pool and zw.supports((D, H, W), pool=True), True)
+        if wino is not None and (not (argmax and pool) or (wino.two_d and wino.supports_pool(W))) and wino.supports(W, (B, D, H, W)):
+            return Plan(layer.wino_kind, pool and wino.supports_pool(W), False)
+    # conv + BN + ReLU + MaxPool in one direct kernel where its 32 x 4 x 4 tile still fills the chip
+    return Plan(DIRECT, pool and layer.conv.supports_pool(W, B * D * H * W), False)
+
+
+class LayerConv:
+    """One conv (+ eval-BN scale / shift + ReLU [+ MaxPool3d(2,2)]) layer: its weight packs - direct always; Winograd (3^3: F(2x2,3x3) /
+    F(2x4,3x3) on (y,x), 4/9 or 1/3 of the MFMA work, wino_mode 2; F(2,3) along x, 2/3, wino_mode 1), the F(2,5)-along-x stem (5^3, one
+    input channel) and f16x2 F(2,3)z (cin % 16 == 0, conv_f16) where the switches allow them - and the execution of a plan.
+    The only writer of the tensor attribute `_m3d_bound` (read by DetectorM3D._bound)."""
+
+    def __init__(self, weight, scale, shift, pool, wino_mode, conv_f16):
+        self.cout, self.cin, self.k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[-1])
+        self.scale, self.shift, self.pool, self.conv_f16 = scale, shift, bool(pool), bool(conv_f16)
+        self.conv = ops.PackedConv3d(weight)
+        self.wino = ops.WinoConv3d(weight, two_d=(wino_mode == 2)) if (wino_mode and self.k == 3) else None
+        self.stem = ops.StemWinoConv3d(weight) if (wino_mode and tuple(weight.shape[1:]) == (1, 5, 5, 5)) else None
+        self.zw = ops.ZwConv3d(weight) if (conv_f16 and ops.ZwConv3d.supported(weight)) else None
+        self.wino_kind = None if self.wino is None else "winograd F(2,3)x" if wino_mode != 2 else \
+            "winograd F(2x4,3x3)" if ops.lib().m3d_conv3d_wino2_family() == 4 else "winograd F(2x2,3x3)"
+        self._plans = {}
+
+    def plan(self, shape, argmax=False, f16=True, winograd=True):
+        """plan_conv, asked once per input shape and set of needs (a running pipeline pays no library query per layer per step)"""
+        key = (tuple(int(v) for v in shape), argmax, f16, winograd)
+        p = self._plans.get(key)
+        if p is None:
+            p = self._plans[key] = plan_conv(self, *key)
+        return p
+
+    def __call__(self, x, bound_of, out_max=None, argmax=False, **needs):
+        """The layer on x, on the kernel plan_conv picks for the caller's needs -> y, or (y, pool arg-max or None) with argmax.
+        bound_of(x): x's operand bound, asked where the plan says sweep (DetectorM3D._bound).  out_max: a ZEROED [ZwConv3d.SLOTS] tensor
+        for y's bound (None: a fresh one; False: nobody needs it); y carries the bound it got as `_m3d_bound`."""
+        p = self.plan((x.shape[0],) + tuple(x.shape[2:]), argmax=argmax, **needs)
+        kw = dict(scale=self.scale, shift=self.shift, relu=True)
+        want_am = dict(return_argmax=True) if argmax else {}
+        in_max = bound_of(x) if p.sweep else None
+        bound = None
+        if p.kind == STEM:
+            if self.conv_f16:
+                bound = out_max if out_max is not None else torch.zeros((ops.ZwConv3d.SLOTS,), dtype=torch.float32, device=x.device)
+            y = (self.stem.pooled if p.fused else self.stem)(x, bound=bound if bound is not None else False, **kw)
+        elif p.kind == ZW:
+            y, bound = self.zw(x, in_max, pool=p.fused, out_max=out_max, **kw)
+        elif p.kind == DIRECT:
+            y = self.conv.pooled(x, **kw, **want_am) if p.fused else self.conv(x, **kw)
+        else:
+            y = self.wino.pooled(x, **kw, **want_am) if p.fused else self.wino(x, **kw)
+        if self.pool and not p.fused:
+            y = ops.maxpool3d_2x(y, **want_am)
+        y, am = y if (argmax and self.pool) else (y, None)
+        if bound is not None:
+            # valid for this version of y.  A fused pool's epilogue takes the maximum over the pooled values; behind an un-fused pool the
+            # bound is the un-pooled map's, which bounds the pooled map too
+            y._m3d_bound = (bound, y._version)
+        return (y, am) if argmax else y

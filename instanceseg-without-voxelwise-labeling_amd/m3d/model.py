@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .conv_plan import LayerConv
 
 BN_EPS = 1e-5   # nn.BatchNorm3d default, DSN.py:20
 
@@ -83,37 +84,23 @@ class DetectorM3D:
         self.P = params
         self.probe = None
         self.anchors = np.ascontiguousarray(cfg.anchors, dtype=np.float64)
-        self.body = []
-        for cname, bname, pool in dsn_layers(cfg.stride):
-            c, b = "Conv_Body." + cname, "Conv_Body." + bname
-            conv = ops.PackedConv3d(params[c + ".weight"])
-            scale = (params[b + ".weight"] / torch.sqrt(params[b + ".running_var"] + BN_EPS)).contiguous()
-            shift = ((params[c + ".bias"] - params[b + ".running_mean"]) * scale + params[b + ".bias"]).contiguous()
-            self.body.append((conv, scale, shift, pool))
-        # plain-forward 3x3x3 layers also get Winograd weights: F(2x2,3x3) on (y,x) (4/9 of the MFMA work; M3D_WINO=2,
-        # default) or F(2,3) along x (2/3; M3D_WINO=1); maps >= 24 voxels wide.  M3D_WINO=0: direct kernels only.
-        # The PRM engine keeps using the direct kernels in self.body (its masks test exact zeros).
+        # M3D_WINO: the plain-forward 3x3x3 layers (and the 5^3 stem) also get Winograd weights - 2 (default): F(2x2,3x3) / F(2x4,3x3) on (y,x);
+        # 1: F(2,3) along x; 0: direct kernels only.  Round 6, M3D_CONV_F16 (default 1; needs M3D_WINO != 0): the 3^3 layers with cin % 16 == 0
+        # on the f16 matrix cores at fp32 accuracy (csrc/conv3d_zw.hip: f16x2 split + F(2,3) along z; 1.5 x the fp32 F(2x4,3x3) kernel on the
+        # step's layers); the operand bound travels with the activations (tensor attribute `_m3d_bound`, filled by the producing launch's
+        # epilogue); 0 keeps the fp32 Winograd kernels (A/B).  Which kernel then runs a layer: m3d/conv_plan.py.
         self.wino_mode = int(os.environ.get("M3D_WINO", "2"))
         self.use_wino = self.wino_mode != 0
-        self.body_wino = [ops.WinoConv3d(params["Conv_Body." + cname + ".weight"], two_d=(self.wino_mode == 2))
-                          if (self.use_wino and params["Conv_Body." + cname + ".weight"].shape[-1] == 3) else None
-                          for cname, _, _ in dsn_layers(cfg.stride)]
-        self.stem_wino = None                                      # conv1a: F(2,5) along x
-        w1 = params["Conv_Body.conv1a.weight"]
-        if self.use_wino and tuple(w1.shape[1:]) == (1, 5, 5, 5):
-            self.stem_wino = ops.StemWinoConv3d(w1)
-        # Round 6: the 3^3 layers with cin % 16 == 0 on the f16 matrix cores at fp32 accuracy (csrc/conv3d_zw.hip: f16x2 split + F(2,3)
-        # along z; 1.5 x the fp32 F(2x4,3x3) kernel on the step's layers).  The operand bound travels with the activations (tensor
-        # attribute `_m3d_bound`, filled by the producing launch's epilogue); M3D_CONV_F16=0 keeps the fp32 Winograd kernels (A/B).
         self.conv_f16 = self.use_wino and os.environ.get("M3D_CONV_F16", "1") == "1"
-        self.body_zw = [ops.ZwConv3d(params["Conv_Body." + cname + ".weight"])
-                        if (self.conv_f16 and ops.ZwConv3d.supported(params["Conv_Body." + cname + ".weight"])) else None
-                        for cname, _, _ in dsn_layers(cfg.stride)]
-        self.rpn_conv_zw = ops.ZwConv3d(params["RPN.RPN_conv.weight"]) \
-            if (self.conv_f16 and ops.ZwConv3d.supported(params["RPN.RPN_conv.weight"])) else None
-        self.rpn_conv = ops.PackedConv3d(params["RPN.RPN_conv.weight"])
-        self.rpn_conv_wino = ops.WinoConv3d(params["RPN.RPN_conv.weight"], two_d=(self.wino_mode == 2)) if self.use_wino else None
+        self.body, self.convs = [], []                 # body[li] = (direct conv, scale, shift, pool); convs[li]: the layer's LayerConv
+        for cname, bname, pool in dsn_layers(cfg.stride):
+            c, b = "Conv_Body." + cname, "Conv_Body." + bname
+            scale = (params[b + ".weight"] / torch.sqrt(params[b + ".running_var"] + BN_EPS)).contiguous()
+            shift = ((params[c + ".bias"] - params[b + ".running_mean"]) * scale + params[b + ".bias"]).contiguous()
+            self.convs.append(LayerConv(params[c + ".weight"], scale, shift, pool, self.wino_mode, self.conv_f16))
+            self.body.append((self.convs[-1].conv, scale, shift, pool))   # (the PRM norm / backward convs and the tests read this tuple)
         self.rpn_conv_bias = params["RPN.RPN_conv.bias"].contiguous()
+        self.rpn_conv = LayerConv(params["RPN.RPN_conv.weight"], None, self.rpn_conv_bias, False, self.wino_mode, self.conv_f16)
         self.A = params["RPN.RPN_cls_score.weight"].shape[0]
         # the two 1x1x1 heads share their input: one conv with A + 6A output channels (rpn_heads.py:96-98)
         w = torch.cat([params["RPN.RPN_cls_score.weight"], params["RPN.RPN_bbox_pred.weight"]], 0).contiguous()
@@ -141,35 +128,9 @@ class DetectorM3D:
 
     # ---- lib/modeling/DSN.py:57-68
     def body_layer(self, li, x, bound_slot=None):
-        """conv + eval-BN + ReLU (+ MaxPool) of body layer li: Winograd-x kernel where it has a tile configuration,
-        otherwise the direct MFMA kernel; the pool is fused into the conv launch when the map is large enough."""
-        conv, scale, shift, pool = self.body[li]
-        wino = self.body_wino[li]
-        width = x.shape[-1]
-        small = x[0].numel() * 4 < 0x7FFFFFFF          # the Winograd kernels address one batch item with 32-bit buffer offsets
-        if not small:
-            wino = None
-        if li == 0 and small and self.stem_wino is not None and self.stem_wino.supports(width):
-            sb = (bound_slot if bound_slot is not None else True) if self.conv_f16 else False
-            return self.stem_wino.pooled(x, scale=scale, shift=shift, relu=True, bound=sb) if pool else \
-                self.stem_wino(x, scale=scale, shift=shift, relu=True, bound=sb)
-        zw = self.body_zw[li]
-        if zw is not None and small and self._zw_ok(zw, x):
-            fused = pool and zw.supports(x.shape, pool=True)
-            y, ym = zw(x, self._bound(x), scale=scale, shift=shift, relu=True, pool=fused, out_max=bound_slot)
-            if pool and not fused:
-                y = ops.maxpool3d_2x(y)
-            y._m3d_bound = (ym, y._version)                   # (a pooled map's bound is its un-pooled map's)
-            return y
-        if wino is not None and wino.supports(width, (x.shape[0],) + tuple(x.shape[2:])):
-            if pool and wino.supports_pool(width):
-                return wino.pooled(x, scale=scale, shift=shift, relu=True)
-            x = wino(x, scale=scale, shift=shift, relu=True)
-            return ops.maxpool3d_2x(x) if pool else x
-        if pool and conv.supports_pool(width, x.shape[0] * x.shape[2] * x.shape[3] * x.shape[4]):
-            return conv.pooled(x, scale=scale, shift=shift, relu=True)          # conv+BN+ReLU+MaxPool in one kernel
-        x = conv(x, scale=scale, shift=shift, relu=True)
-        return ops.maxpool3d_2x(x) if pool else x
+        """conv + eval-BN + ReLU (+ MaxPool) of body layer li on the kernel conv_plan.plan_conv picks; bound_slot: a zeroed
+        [ZwConv3d.SLOTS] tensor for the output's operand bound (None: a fresh one where one is needed)."""
+        return self.convs[li](x, self._bound, bound_slot)
 
     @staticmethod
     def _bound(x):
@@ -179,12 +140,6 @@ class DetectorM3D:
         if b is not None and b[1] == x._version:           # (an in-place write since the producing launch makes the bound stale: sweep again)
             return b[0]
         return ops.ZwConv3d.bound_of(x)
-
-    @staticmethod
-    def _zw_ok(zw, x):
-        """the f16x2 kernel runs one workgroup per (64 channels, 32 x 4 x 2 voxels): maps that give it less than ~0.8 of a round of the
-        chip's 256 CUs stay with the fp32 Winograd kernels (split-K over workgroups)"""
-        return zw.supports(x.shape) and zw.units(x.shape) >= 200
 
     def span(self, name):
         return self.probe(name) if self.probe is not None else _NOSPAN
@@ -200,48 +155,27 @@ class DetectorM3D:
     def conv_work(self, batch, size):
         """Per probe span of the convolution family (conv1a .. conv4b, rpn): algorithmic FLOPs (2*Cin*Cout*k^3 per output voxel), the
         FLOPs the chosen kernel issues on the matrix cores (Winograd fraction, output channels padded to blocks of 32) and the
-        kernel kind, for a batch of `batch` volumes of `size` = (S, H, W) - the same decisions as body_layer() / rpn()."""
+        kernel kind, for a batch of `batch` volumes of `size` = (S, H, W) - from the plans body_layer() / rpn() execute."""
         out = {}
         S, H, W = size
-        names = dsn_layers(self.cfg.stride)
-        two_d = "winograd F(2x4,3x3)" if ops.lib().m3d_conv3d_wino2_family() == 4 else "winograd F(2x2,3x3)"
 
-        def pad32(c):
-            return (c + 31) // 32 * 32 / float(c)
-
-        def pad64(c):
-            return (c + 63) // 64 * 64 / float(c)
-        for li, (cname, _, pool) in enumerate(names):
-            w = self.P["Conv_Body." + cname + ".weight"]
-            cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
-            small = cin * S * H * W * 4 < 0x7FFFFFFF
-            kind = "direct"
-            if li == 0 and small and self.stem_wino is not None and self.stem_wino.supports(W):
-                kind = "winograd F(2,5)x stem"
-            elif small and self.body_zw[li] is not None and self.body_zw[li].supports((S, H, W)) and self.body_zw[li].units((batch, cin, S, H, W)) >= 200:
-                kind = "f16x2 F(2,3)z"
-            elif small and self.body_wino[li] is not None and self.body_wino[li].supports(W, (batch, S, H, W)):
-                kind = two_d if self.wino_mode == 2 else "winograd F(2,3)x"
-            alg = 2.0 * cin * cout * k ** 3 * S * H * W * batch
-            out[cname] = dict(algorithmic_flop=alg, issued_flop=alg * self.ISSUED_FRACTION[kind] * (pad64(cout) if kind in self.F16_KINDS else pad32(cout)),
-                              kernel=kind, shape="%d->%d k%d @ %dx%dx%d" % (cin, cout, k, S, H, W), dtype="f16" if kind in self.F16_KINDS else "f32")
+        def record(layer):
+            kind = layer.plan((batch, S, H, W)).kind
+            f16 = kind in self.F16_KINDS
+            pad = (layer.cout + 63) // 64 * 64 / float(layer.cout) if f16 else (layer.cout + 31) // 32 * 32 / float(layer.cout)
+            alg = 2.0 * layer.cin * layer.cout * layer.k ** 3 * S * H * W * batch
+            return dict(algorithmic_flop=alg, issued_flop=alg * self.ISSUED_FRACTION[kind] * pad, kernel=kind,
+                        shape="%d->%d k%d @ %dx%dx%d" % (layer.cin, layer.cout, layer.k, S, H, W), dtype="f16" if f16 else "f32")
+        for (cname, _, pool), layer in zip(dsn_layers(self.cfg.stride), self.convs):
+            out[cname] = record(layer)
             if pool:
                 S, H, W = S // 2, H // 2, W // 2
-        w = self.P["RPN.RPN_conv.weight"]
-        cout, cin = int(w.shape[0]), int(w.shape[1])
-        kind = "direct"
-        if self.rpn_conv_zw is not None and cin * S * H * W * 4 < 0x7FFFFFFF and self.rpn_conv_zw.supports((S, H, W)) \
-                and self.rpn_conv_zw.units((batch, cin, S, H, W)) >= 200:
-            kind = "f16x2 F(2,3)z"
-        elif self.rpn_conv_wino is not None and self.rpn_conv_wino.supports(W, (batch, S, H, W)) and cin * S * H * W * 4 < 0x7FFFFFFF:
-            kind = two_d if self.wino_mode == 2 else "winograd F(2,3)x"
-        alg = 2.0 * cin * cout * 27 * S * H * W * batch
-        nh = 7 * self.A
+        r = record(self.rpn_conv)
+        cout, nh = self.rpn_conv.cout, 7 * self.A
         alg_h = 2.0 * cout * nh * S * H * W * batch
-        out["rpn"] = dict(algorithmic_flop=alg + alg_h, issued_flop=alg * self.ISSUED_FRACTION[kind] * pad32(cout) + alg_h * pad32(nh),
-                          dtype="f16" if kind in self.F16_KINDS else "f32",
-                          kernel=kind + " (3^3 conv) + direct (the two 1^3 heads as one conv)",
-                          shape="%d->%d k3, %d->%d k1 @ %dx%dx%d" % (cin, cout, cout, nh, S, H, W))
+        out["rpn"] = dict(algorithmic_flop=r["algorithmic_flop"] + alg_h, issued_flop=r["issued_flop"] + alg_h * ((nh + 31) // 32 * 32 / float(nh)),
+                          dtype=r["dtype"], kernel=r["kernel"] + " (3^3 conv) + direct (the two 1^3 heads as one conv)",
+                          shape="%d->%d k3, %d->%d k1 @ %dx%dx%d" % (self.rpn_conv.cin, cout, cout, nh, S, H, W))
         return out
 
     def conv_body(self, x, first=0, last=None):
@@ -271,14 +205,7 @@ class DetectorM3D:
 
     # ---- lib/modeling/rpn_heads.py:94-116
     def rpn(self, feat):
-        rc = self.rpn_conv_wino if (self.rpn_conv_wino is not None and self.rpn_conv_wino.supports(feat.shape[-1], (feat.shape[0],) + tuple(feat.shape[2:]))
-                                    and feat[0].numel() * 4 < 0x7FFFFFFF) else self.rpn_conv
-        zw = self.rpn_conv_zw
-        if zw is not None and feat[0].numel() * 4 < 0x7FFFFFFF and self._zw_ok(zw, feat):
-            h, _ = zw(feat, self._bound(feat), shift=self.rpn_conv_bias, relu=True, out_max=False)
-        else:
-            h = rc(feat, shift=self.rpn_conv_bias, relu=True)
-        return self.rpn_outputs(h)
+        return self.rpn_outputs(self.rpn_conv(feat, self._bound, out_max=False))
 
     def rpn_outputs(self, h):
         """The two 1x1x1 heads as one conv + sigmoid (rpn_heads.py:96-98,116): (prob [B,A,s,h,w], deltas [B,6A,s,h,w])."""

@@ -1312,11 +1312,10 @@ class ZwConv3d(object):
         return out, oo
 
     def units(self, shape):
-        """workgroups of a launch on an input [B, cin, D, H, W] (or (D, H, W): one item): (64 channels) x (32 x 4 x 2 or 16 x 8 x 2 voxels)"""
+        """workgroups of a launch on an input [B, cin, D, H, W] (or (D, H, W): one item): the library's own count, (64 channels) x (its tile)"""
         B = int(shape[0]) if len(shape) == 5 else 1
         D, H, W = (int(v) for v in shape[-3:])
-        xb, ty = (32, 4) if W >= 24 else (16, 8)
-        return B * ((self.cout + 63) // 64) * ((W + xb - 1) // xb) * ((H + ty - 1) // ty) * ((D + 1) // 2)
+        return int(lib().m3d_conv3d_zw_launch_units(B, self.cin, self.cout, D, H, W))
 
     @staticmethod
     def bound_of(x):
@@ -1496,16 +1495,12 @@ class StemWinoConv3d(object):
         if out is None:
             shp = (B, self.cout, D // 2, H // 2, W // 2) if pool else (B, self.cout, D, H, W)
             out = torch.empty(shp, dtype=torch.float32, device=x.device)
-        # bound: True (a fresh zeroed slot array) or a ZEROED [SLOTS] float tensor of the caller's
-        om = None if bound is False or bound is None else \
-            (torch.zeros((ZwConv3d.SLOTS,), dtype=torch.float32, device=x.device) if bound is True else bound)
-        bound = om is not None
+        # bound: False / None, or a ZEROED [ZwConv3d.SLOTS] float tensor of the caller's that the epilogue fills with the output's operand bound
+        om = None if bound is False else bound
         check(lib().m3d_conv3d_stem_wino_forward_bound(_ptr(x), _ptr(self.packed), _ptr(out), B, self.cout, D, H, W,
                                                        _ptr(scale) if scale is not None else None,
                                                        _ptr(shift) if shift is not None else None, int(bool(relu)), int(bool(pool)),
-                                                       _ptr(om) if bound else None, _stream()), "conv3d_stem_wino_forward")
-        if bound:
-            out._m3d_bound = (om, out._version)            # the operand bound of the f16x2 conv that reads `out` (ZwConv3d), valid for this version of `out`
+                                                       _ptr(om) if om is not None else None, _stream()), "conv3d_stem_wino_forward")
         return out
 
     def __call__(self, x, scale=None, shift=None, relu=False, out=None, bound=False):

@@ -151,39 +151,18 @@ class PRMEngine:
         det = self.det
         saved = []
         x = data
-        for li, L in enumerate(self.layers):
-            wnp = det.body_wino[li] if (self.wino_forward and L["pool"] and L["k"] == 3) else None
-            if wnp is not None and wnp.two_d and wnp.supports_pool(x.shape[-1]) and x[0].numel() * 4 < 0x7FFFFFFF and \
-                    wnp.supports(x.shape[-1], (x.shape[0],) + tuple(x.shape[2:])):
-                xn, am = wnp.pooled(x, scale=L["scale"], shift=L["shift"], relu=True, return_argmax=True)     # F(2x4,3x3) + pool + argmax
-            elif L["pool"] and L["conv"].supports_pool(x.shape[-1], x.shape[0] * x.shape[2] * x.shape[3] * x.shape[4]):
-                xn, am = L["conv"].pooled(x, scale=L["scale"], shift=L["shift"], relu=True, return_argmax=True)
-            else:
-                wn = det.body_wino[li] if self.wino_forward else None
-                zw = det.body_zw[li] if (self.wino_forward and det.conv_f16) else None
-                if zw is not None and not L["pool"] and x[0].numel() * 4 < 0x7FFFFFFF and det._zw_ok(zw, x):
-                    # response conv on the f16 matrix cores as in detection mode (csrc/conv3d_zw.hip; the input's bound: left by the
-                    # launch that produced x, else one sweep)
-                    y, ym = zw(x, det._bound(x), scale=L["scale"], shift=L["shift"], relu=True)
-                    y._m3d_bound = (ym, y._version)
-                elif wn is not None and not L["pool"] and wn.supports(x.shape[-1], (x.shape[0],) + tuple(x.shape[2:])):
-                    y = wn(x, scale=L["scale"], shift=L["shift"], relu=True)        # response conv: Winograd as in detection mode
-                else:
-                    y = L["conv"](x, scale=L["scale"], shift=L["shift"], relu=True)
-                if L["pool"]:
-                    xn, am = ops.maxpool3d_2x(y, return_argmax=True)
-                else:
-                    xn, am = y, None
+        # the response convs run on the detection path's kernels (values differ from the direct kernel's by ~1e-6 relative) where those
+        # deliver what the backward needs: conv_plan.plan_conv with argmax (a pooled layer gives its pool's arg-max).  An f16x2 response
+        # conv takes its input's bound from the launch that produced x, else one sweep, and a fresh bound array for its output
+        needs = dict(argmax=True, winograd=self.wino_forward)
+        for L, layer in zip(self.layers, det.convs):
+            xn, am = layer(x, det._bound, **needs)
             saved.append(dict(name=L["name"], x=x[0], off=None, n=None, scale=L["scale"], pool=L["pool"], argmax=None if am is None else am[0],
                               xnext=xn[0], k=L["k"], dgrad=L["dgrad"], dgrad_wino=L["dgrad_wino"], dgrad_wino24=L["dgrad_wino24"], dgrad_zw=L["dgrad_zw"], dgrad_small=L["dgrad_small"],
                               weight=L["weight"], norm_conv=L["norm_conv"]))
             x = xn
         feat = x
-        wn = det.rpn_conv_wino if self.wino_forward else None
-        if wn is not None and wn.supports(feat.shape[-1], (feat.shape[0],) + tuple(feat.shape[2:])):
-            h = wn(feat, shift=det.rpn_conv_bias, relu=True)
-        else:
-            h = det.rpn_conv(feat, shift=det.rpn_conv_bias, relu=True)
+        h, _ = det.rpn_conv(feat, det._bound, f16=False, **needs)                 # (the RPN conv stays off f16x2 here)
         saved.append(dict(name="RPN_conv", x=feat[0], off=None, n=None, scale=None, pool=False, argmax=None, xnext=h[0], k=3,
                           dgrad=self.rpn["dgrad"], dgrad_small=self.rpn["dgrad_small"], norm_conv=self.rpn["norm_conv"]))
         prob, deltas = det.rpn_outputs(h)
