@@ -869,6 +869,58 @@ int m3d_rpn_loss(const float* d_cls_logits, const float* d_bbox_pred, int batch,
                  const float* d_targets, const int64_t* d_counts, int num_fg, int batch_per_im, float* d_losses, float* d_grad_logits,
                  float* d_grad_pred, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Box-head training step (csrc/box_head_train.hip): what GenerateProposalLabelsOp_3d does on the host in the middle of every
+ * training step - add_proposals (lib/datasets/nuclei_dataset.py:429-547), _sample_rois (lib/roi_data/fast_rcnn.py:129-248) - and
+ * fast_rcnn_losses (lib/modeling/fast_rcnn_heads.py:50-66, smooth L1 with beta 1, lib/utils/net.py:15-32) do with its five blobs.
+ * Image scale 1, no FPN.  The "roidb rows" of image b are r = 0 .. K_b-1 for its ground-truth boxes in the given order, then
+ * r = K_b .. for its proposals in order.
+ * Limits (M3D_EUNSUPPORTED, before any launch): num_classes <= 64, batch_per_im <= 4096, num_images <= 64, max K_b + rows < 2^31 - 256,
+ * cls_agnostic_bbox_reg != 0 (not implemented: in the reference it also clips the classification labels, fast_rcnn.py:217).
+ *   m3d_box_head_targets  all num_images images in one launch pair.  d_gt fp32 [sum K_b, 6]: the images' boxes one after another,
+ *                     gt_offsets HOST int32 [num_images + 1] (gt_offsets[0] = 0; image b owns [gt_offsets[b], gt_offsets[b+1])),
+ *                     d_gt_classes int32 [sum K_b] in 1 .. num_classes-1 (NULL: all 1), d_gt_crowd uint8 [sum K_b] (NULL: none).
+ *                     d_rois fp32 [num_images, rows, 7] and d_num int32 [num_images] exactly as m3d_generate_proposals3d_batched
+ *                     leaves them: image b's proposals are d_rois[b, :num[b], 1:7], column 0 is ignored.  Labelling: a non-crowd
+ *                     gt row has overlap 1, its own class and is assigned to itself; a crowd gt row has overlap -1; a proposal row
+ *                     takes the IoU (as m3d_bbox_overlaps3d) against the non-crowd boxes, is assigned to the FIRST arg-max and has
+ *                     that box's class if the maximum is > 0, else overlap 0, class 0, no assignment.  fg candidates: overlap >=
+ *                     fg_thresh; bg candidates: bg_thresh_lo <= overlap < bg_thresh_hi (compared as fp32).  Sampling (stream =
+ *                     fin(seeds[b]), key(i) = upper 32 bits of fin(stream + i), fin = the splitmix64 finaliser as for
+ *                     m3d_rpn_targets; seeds HOST uint64 [num_images]): the min(fg_per_im, #fg candidates) candidates with the
+ *                     smallest (key(r), r) stay, then the min(batch_per_im - #fg kept, #bg candidates) bg candidates with the
+ *                     smallest (key(2^40 + r), r); both without replacement.  Outputs (device, per image padded to batch_per_im,
+ *                     fg rows ascending in r, then bg rows ascending in r): d_rows int64 [num_images, batch] (-1 beyond the count),
+ *                     d_labels int32 (class of an fg row, 0 for bg, -1 beyond), d_out_rois fp32 [.., 6] (0 beyond), d_targets fp32
+ *                     [.., 6]: bbox_transform_inv_3d (boxes_3d.py:228-268) of an fg row against its assigned box with
+ *                     bbox_reg_weights (HOST fp64 [6]): dx,dy,dz fp32 in the reference's operation order, dw,dh,ds =
+ *                     fp32(weight * log in fp64 of the fp32 ratio); 0 on bg rows and beyond.  d_counts int64 [num_images, 8] = rows
+ *                     sampled, fg sampled, bg sampled, fg candidates, bg candidates, crowd gt rows, non-crowd gt boxes, proposals.
+ *                     Integer atomics and value-ordered selection only: bit-identical run to run.
+ *                     Workspace m3d_box_head_targets_workspace_bytes(num_images, max K_b, rows).
+ *   m3d_box_head_target_blobs  _expand_bbox_targets (fast_rcnn.py:222-248): d_labels [num_rows], d_targets [num_rows, 6] (any number
+ *                     of stacked images) -> d_bbox_targets, d_inside_weights, d_outside_weights fp32 [num_rows, 6 num_classes]:
+ *                     the row's targets / 1 / 1 in slots 6 label .. 6 label + 5 of rows with label > 0, 0 elsewhere.
+ *   m3d_box_head_loss  d_cls_score fp32 [B batch, C], d_bbox_pred fp32 [B batch, 6 C]; d_labels, d_targets, d_counts of the B images
+ *                     stacked.  R = sum of the sampled-row counts (device side).  d_losses fp32 [3] = loss_cls = sum softmax cross
+ *                     entropy / R, loss_bbox = sum over fg rows and slots 6 label + j of smoothL1(p - t) / R, accuracy_cls = rows
+ *                     whose first arg-max is the label / R; zeros if R = 0.  Row terms in fp64 from the fp32 inputs, one workgroup,
+ *                     fixed summation tree, each result rounded once.  d_grad_score / d_grad_pred (input shapes, written whole):
+ *                     (softmax - onehot) / R at labelled rows, clamp(p - t, -1, 1) / R at the six slots of fg rows, exactly 0
+ *                     elsewhere.
+ * ------------------------------------------------------------------------------------------------------- */
+size_t m3d_box_head_targets_workspace_bytes(int num_images, int max_gt, int rows);
+int m3d_box_head_targets(const float* d_gt, const int32_t* d_gt_classes, const uint8_t* d_gt_crowd, const int32_t* gt_offsets,
+                         int num_images, const float* d_rois, const int32_t* d_num, int rows, int batch_per_im, int fg_per_im,
+                         double fg_thresh, double bg_thresh_hi, double bg_thresh_lo, const double* bbox_reg_weights, int num_classes,
+                         int cls_agnostic_bbox_reg, const uint64_t* seeds, int64_t* d_rows, int32_t* d_labels, float* d_out_rois,
+                         float* d_targets, int64_t* d_counts, void* d_ws, size_t ws_bytes, void* stream);
+int m3d_box_head_target_blobs(const int32_t* d_labels, const float* d_targets, int64_t num_rows, int num_classes,
+                              float* d_bbox_targets, float* d_inside_weights, float* d_outside_weights, void* stream);
+int m3d_box_head_loss(const float* d_cls_score, const float* d_bbox_pred, const int32_t* d_labels, const float* d_targets,
+                      const int64_t* d_counts, int num_images, int batch_per_im, int num_classes, float* d_losses,
+                      float* d_grad_score, float* d_grad_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,15 +14,16 @@
 //                     fg anchors a draw hit, regression targets, counts.
 //   wide_kernel       scatter into the four dense blobs;  loss_kernel: both losses and both gradients, O(batch) work.
 #include "box_common.h"
+#include "train_common.h"
 
 namespace {
 using namespace m3dbox;
+using namespace m3dtrain;
 
 constexpr int kMaxA = 64;          // cell anchors per position (PropParams has the same limit)
 constexpr int kChunk = 256;        // ground-truth boxes per LDS chunk
 constexpr int kTPB = 256;          // threads per workgroup of the two field passes
 constexpr int kPerThread = 4;      // anchors per thread there: one workgroup covers 1024 consecutive anchors = 16 candidate words
-constexpr int kOne = 1024;         // threads of the single-workgroup kernels
 constexpr int kMaxBatch = 4096;    // RPN_BATCH_SIZE_PER_IM limit: the finalize kernel's rank sorts are quadratic in it (shipped: 64 / 128)
 enum { C_FG = 0, C_INSIDE, C_CAND, C_COUNT = 8 };
 
@@ -66,22 +67,7 @@ inline Ws carve(void* base, unsigned int N, int K, int num_fg, int batch) {
   return w;
 }
 
-// The sampling contract (DESIGN, "RPN training targets"): key(i) = upper 32 bits of the splitmix64 finaliser of stream + i, where
-// stream = the 64-bit finaliser of the caller's seed.  Without that first scramble a key would depend on seed + i only, and draw j of
-// seed s would be draw j - 1 of seed s + 1: callers that count their seeds up would replay shifted draws.
-inline unsigned long long seed_stream(unsigned long long seed) {
-  unsigned long long z = seed * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ inline unsigned int mix_key(unsigned long long seed, unsigned long long i) {
-  unsigned long long z = (seed + i) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (unsigned int)(z >> 32);
-}
+// The sampling contract (DESIGN, "RPN training targets"): seed_stream / mix_key of train_common.h
 __device__ inline unsigned long long fg_order(unsigned long long seed, unsigned int i) {
   return ((unsigned long long)mix_key(seed, i) << 32) | i;
 }
@@ -229,23 +215,6 @@ __global__ __launch_bounds__(kTPB) void label_kernel(Geom g, const float* __rest
       if (fg) fglist[base + (unsigned int)__popcll(mf & ((1ull << lane) - 1ull))] = idx[u];
     }
   }
-}
-
-// exclusive prefix of one value per thread over a workgroup of kOne threads; *total = the sum
-__device__ inline unsigned int block_exscan(unsigned int v, unsigned int* sh, unsigned int* total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int off = 1; off < kOne; off <<= 1) {
-    const unsigned int add = t >= off ? sh[t - off] : 0u;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  *total = sh[kOne - 1];
-  const unsigned int ex = sh[t] - v;
-  __syncthreads();
-  return ex;
 }
 
 __global__ __launch_bounds__(kOne) void scan_kernel(const unsigned long long* __restrict__ bits, unsigned int nwords,
@@ -492,20 +461,6 @@ __global__ __launch_bounds__(kTPB) void wide_kernel(const int64_t* __restrict__ 
       for (int c = 0; c < 6; ++c) ow[base + (size_t)c * F3] = o;
     }
   }
-}
-
-template <typename T>
-__device__ inline T block_sum(T v, T* sh) {   // fixed tree: the same bits every run
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int off = kOne / 2; off > 0; off >>= 1) {
-    if (t < off) sh[t] += sh[t + off];
-    __syncthreads();
-  }
-  const T r = sh[0];
-  __syncthreads();
-  return r;
 }
 
 struct LossGeom { int B, A, s, h, w, F, cap_fg, cap_bg; };

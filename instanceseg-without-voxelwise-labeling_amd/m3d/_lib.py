@@ -32,6 +32,7 @@ SYMBOLS = [
     "m3d_label_overlap_workspace_bytes", "m3d_label_overlap", "m3d_label_iou_best", "m3d_box_union_overlap_workspace_bytes", "m3d_box_union_overlap_counts",
     "m3d_label_components_workspace_bytes", "m3d_label_components", "m3d_label_counts", "m3d_paint_spheres_workspace_bytes", "m3d_paint_spheres",
     "m3d_rpn_targets_workspace_bytes", "m3d_rpn_targets", "m3d_rpn_targets_wide", "m3d_rpn_loss",
+    "m3d_box_head_targets_workspace_bytes", "m3d_box_head_targets", "m3d_box_head_target_blobs", "m3d_box_head_loss",
 ]
 
 
@@ -63,7 +64,7 @@ def _load(path):
               "m3d_box_results3d_batched_workspace_bytes", "m3d_nms3d_batched_workspace_bytes", "m3d_otsu2d_workspace_bytes",
               "m3d_cc_workspace_bytes", "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_stem_wino_packed_weight_bytes",
               "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
-              "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes"):
+              "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1951,4 +1951,81 @@ def rpn_loss_grad(cls_logits, bbox_pred, field_size, fg_index, bg_index, target_
     check(lib().m3d_rpn_loss(_ptr(x), _ptr(p), B, A, s, h, w, int(field_size), _ptr(fg_index), _ptr(bg_index), _ptr(target_index),
                              _ptr(targets), _ptr(counts), fg_index.shape[1], bg_index.shape[1], _ptr(losses), _ptr(gx), _ptr(gp), _stream()),
           "rpn_loss")
+    return losses, gx, gp
+
+
+# ------------------------------------------------------------------ box-head training step (csrc/box_head_train.hip)
+def box_head_target_sets(rois, num, gt, gt_offsets, gt_classes, gt_crowd, batch_per_im, fg_per_im, fg_thresh, bg_thresh_hi, bg_thresh_lo,
+                         bbox_reg_weights, num_classes, seeds, cls_agnostic_bbox_reg=False):
+    """m3d_box_head_targets for the B images of a minibatch: rois fp32 [B,rows,7] and num int32 [B] as generate_proposals3d_batched
+    returns them, gt CUDA fp32 [sum K,6] with host offsets [B+1], gt_classes int32 / gt_crowd uint8 [sum K] or None, seeds: B host
+    integers.  -> (rows int64 [B,batch], labels int32 [B,batch], rois fp32 [B,batch,6], targets fp32 [B,batch,6], counts int64 [B,8]),
+    all on the device, no synchronisation."""
+    _need_gpu(rois, num, gt, gt_classes, gt_crowd)
+    rois, gt = _f32c(rois), _f32c(gt).reshape(-1, 6)
+    if rois.dim() != 3 or rois.shape[2] != 7 or num.dtype != torch.int32 or tuple(num.shape) != (rois.shape[0],):
+        raise M3DError("box_head_target_sets: rois must be [B,rows,7] and num int32 [B]")
+    B, R, dev = rois.shape[0], rois.shape[1], rois.device
+    off = np.ascontiguousarray(gt_offsets, np.int32)
+    sd = np.array([int(s) & (2 ** 64 - 1) for s in seeds], np.uint64)
+    if off.shape != (B + 1,) or sd.shape != (B,) or int(off[-1]) != gt.shape[0]:
+        raise M3DError("box_head_target_sets: %d images need %d box offsets ending at %d and %d seeds" % (B, B + 1, gt.shape[0], B))
+    for name, t, dt in (("gt_classes", gt_classes, torch.int32), ("gt_crowd", gt_crowd, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.numel() != gt.shape[0] or not t.is_contiguous()):
+            raise M3DError("box_head_target_sets: %s must be a contiguous %s tensor with one entry per box" % (name, dt))
+    wt = np.ascontiguousarray(bbox_reg_weights, np.float64)
+    if wt.shape != (6,):
+        raise M3DError("box_head_target_sets: six bbox_reg_weights")
+    num = num.contiguous()
+    batch = int(batch_per_im)
+    rows = torch.empty((B, batch), dtype=torch.int64, device=dev)
+    labels = torch.empty((B, batch), dtype=torch.int32, device=dev)
+    out_rois = torch.empty((B, batch, 6), dtype=torch.float32, device=dev)
+    targets = torch.empty((B, batch, 6), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, 8), dtype=torch.int64, device=dev)
+    L = lib()
+    max_gt = int(np.diff(off).max()) if B else 0
+    nbytes = L.m3d_box_head_targets_workspace_bytes(B, max_gt, R)
+    ws = _workspace(max(int(nbytes), 1), dev, "box_head_targets")
+    check(L.m3d_box_head_targets(_ptr(gt if gt.shape[0] else None), _ptr(gt_classes), _ptr(gt_crowd), off.ctypes.data_as(C.c_void_p), B,
+                                 _ptr(rois if R else None), _ptr(num), R, batch, int(fg_per_im), C.c_double(float(fg_thresh)),
+                                 C.c_double(float(bg_thresh_hi)), C.c_double(float(bg_thresh_lo)), wt.ctypes.data_as(C.c_void_p),
+                                 int(num_classes), int(bool(cls_agnostic_bbox_reg)), sd.ctypes.data_as(C.c_void_p), _ptr(rows),
+                                 _ptr(labels), _ptr(out_rois), _ptr(targets), _ptr(counts), _ptr(ws), C.c_size_t(ws.numel()), _stream()),
+          "box_head_targets")
+    return rows, labels, out_rois, targets, counts
+
+
+def box_head_target_blobs(labels, targets, num_classes):
+    """_expand_bbox_targets on the device: labels int32 [...], targets fp32 [...,6] -> bbox_targets, bbox_inside_weights,
+    bbox_outside_weights fp32 [N, 6 num_classes] with N = labels.numel()."""
+    _need_gpu(labels, targets)
+    labels, targets = labels.contiguous(), _f32c(targets)
+    N = labels.numel()
+    if labels.dtype != torch.int32 or targets.numel() != 6 * N:
+        raise M3DError("box_head_target_blobs: labels int32 [N] and targets [N,6]")
+    bt, iw, ow = (torch.empty((N, 6 * int(num_classes)), dtype=torch.float32, device=labels.device) for _ in range(3))
+    check(lib().m3d_box_head_target_blobs(_ptr(labels), _ptr(targets), C.c_int64(N), int(num_classes), _ptr(bt), _ptr(iw), _ptr(ow),
+                                          _stream()), "box_head_target_blobs")
+    return bt, iw, ow
+
+
+def box_head_loss_grad(cls_score, bbox_pred, labels, targets, counts):
+    """m3d_box_head_loss: cls_score [B batch, C], bbox_pred [B batch, 6 C]; labels [B,batch], targets [B,batch,6], counts [B,8] of
+    box_head_target_sets.  -> (losses fp32 [3] = (loss_cls, loss_bbox, accuracy_cls), d loss_cls / d cls_score, d loss_bbox / d bbox_pred)."""
+    _need_gpu(cls_score, bbox_pred, labels, targets, counts)
+    x, p = _f32c(cls_score), _f32c(bbox_pred)
+    if labels.dim() != 2 or x.dim() != 2 or p.dim() != 2:
+        raise M3DError("box_head_loss_grad: cls_score [B batch, C], bbox_pred [B batch, 6 C], labels [B, batch]")
+    B, batch = labels.shape
+    N, Cn = x.shape
+    if N != B * batch or tuple(p.shape) != (N, 6 * Cn) or tuple(targets.shape) != (B, batch, 6) or tuple(counts.shape) != (B, 8):
+        raise M3DError("box_head_loss_grad: %s scores and %s predictions for %d x %d sampled rows" % (tuple(x.shape), tuple(p.shape), B, batch))
+    if labels.dtype != torch.int32 or counts.dtype != torch.int64 or targets.dtype != torch.float32:
+        raise M3DError("box_head_loss_grad: labels int32, targets fp32, counts int64")
+    labels, targets, counts = labels.contiguous(), targets.contiguous(), counts.contiguous()
+    losses = torch.empty((3,), dtype=torch.float32, device=x.device)
+    gx, gp = torch.empty_like(x), torch.empty_like(p)
+    check(lib().m3d_box_head_loss(_ptr(x), _ptr(p), _ptr(labels), _ptr(targets), _ptr(counts), B, batch, Cn, _ptr(losses), _ptr(gx), _ptr(gp),
+                                  _stream()), "box_head_loss")
     return losses, gx, gp

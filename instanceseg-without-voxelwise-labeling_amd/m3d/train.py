@@ -2,7 +2,11 @@
 
 Reference: lib/roi_data/rpn.py:120-279 (_get_rpn_blobs, a host step per sample there) and lib/modeling/rpn_heads.py:140-170
 (single_scale_rpn_losses, sigmoid branch) with lib/utils/net.py:15-32.  Single-scale RPN only; DESIGN ("RPN training targets") lists
-the quirks kept, the sampling contract and what is not here."""
+the quirks kept, the sampling contract and what is not here.
+
+Box head from proposals and boxes (csrc/box_head_train.hip): proposal labelling, fg / bg sampling, regression targets and the softmax /
+smooth-L1 losses.  Reference: lib/modeling/generate_proposal_labels_3d.py, lib/datasets/nuclei_dataset.py:429-547,
+lib/roi_data/fast_rcnn.py:129-248, lib/modeling/fast_rcnn_heads.py:50-66; DESIGN ("Box-head training targets")."""
 import math
 
 import numpy as np
@@ -11,7 +15,7 @@ import torch
 from . import ops
 from .config import generate_anchors_3d
 
-__all__ = ["RpnTrainCfg", "RpnTargets", "rpn_targets", "rpn_losses"]
+__all__ = ["RpnTrainCfg", "RpnTargets", "rpn_targets", "rpn_losses", "BoxHeadTrainCfg", "BoxHeadTargets", "box_head_targets", "box_head_losses"]
 
 
 class RpnTrainCfg:
@@ -144,3 +148,133 @@ def rpn_losses(rpn_cls_logits, rpn_bbox_pred, targets):
         return torch.stack([r if r.shape[0] == cap else torch.cat([r, r.new_full((cap - r.shape[0],) + tuple(r.shape[1:]), fill)]) for r in rows])
     return _RpnLoss.apply(rpn_cls_logits, rpn_bbox_pred, ts[0].field_size, stack("fg_index", cap_fg, -1), stack("bg_index", cap_bg, -1),
                           stack("target_index", cap_fg, -1), stack("targets", cap_fg, 0), torch.stack([t.counts for t in ts]))
+
+
+class BoxHeadTrainCfg:
+    """The TRAIN / MODEL keys the box-head step reads; defaults = the nuclei YAML merged over lib/core/config.py."""
+
+    def __init__(self, **kw):
+        self.batch_per_im = 64                              # TRAIN.BATCH_SIZE_PER_IM
+        self.fg_fraction = 0.25                             # TRAIN.FG_FRACTION (config.py:65)
+        self.fg_thresh = 0.4                                # TRAIN.FG_THRESH
+        self.bg_thresh_hi = 0.4                             # TRAIN.BG_THRESH_HI
+        self.bg_thresh_lo = 0.0                             # TRAIN.BG_THRESH_LO (config.py:73)
+        self.num_classes = 2                                # MODEL.NUM_CLASSES
+        self.bbox_reg_weights = (10., 10., 10., 5., 5., 5.)   # MODEL.BBOX_REG_WEIGHTS
+        self.cls_agnostic_bbox_reg = False                  # MODEL.CLS_AGNOSTIC_BBOX_REG: True is refused (DESIGN)
+        unknown = sorted(set(kw) - set(self.__dict__))
+        if unknown:
+            raise TypeError("BoxHeadTrainCfg: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(sorted(self.__dict__))))
+        self.__dict__.update(kw)
+
+    @staticmethod
+    def nuclei(**kw):
+        return BoxHeadTrainCfg(**kw)
+
+    @staticmethod
+    def soma(**kw):
+        d = dict(batch_per_im=128)
+        d.update(kw)
+        return BoxHeadTrainCfg(**d)
+
+    @property
+    def fg_per_im(self):                                    # fast_rcnn.py:134
+        return int(np.round(self.fg_fraction * int(self.batch_per_im)))
+
+
+class BoxHeadTargets:
+    """The sampled box-head rows of B images, on the device, each image padded to batch = BATCH_SIZE_PER_IM (fg rows ascending in
+    roidb row, then bg rows ascending; roidb row r < K = ground-truth box r, r >= K = proposal r - K):
+      rows int64 [B,batch] (-1 beyond the count), labels int32 [B,batch] (class / 0 / -1), rois fp32 [B,batch,6], targets fp32 [B,batch,6]
+      counts int64 [B,8]   rows, fg, bg sampled; fg, bg candidates; crowd gt rows; non-crowd gt boxes; proposals"""
+
+    def __init__(self, rows, labels, rois, targets, counts, cfg):
+        self.rows, self.labels, self.rois, self.targets, self.counts, self.cfg = rows, labels, rois, targets, counts, cfg
+
+    @property
+    def rois7(self):
+        """fp32 [B batch, 7] for RoIAlign: the batch index in column 0; a padding row is a zero box on image 0."""
+        B, batch = self.labels.shape
+        index = torch.arange(B, device=self.labels.device, dtype=torch.float32)[:, None] * (self.labels >= 0).float()
+        return torch.cat([index[:, :, None], self.rois], 2).reshape(B * batch, 7)
+
+    def blobs(self):
+        """The reference's five blobs over the padded rows (fast_rcnn.py:186-191): labels_int32 [N], rois [N,7], bbox_targets,
+        bbox_inside_weights, bbox_outside_weights [N, 6 NUM_CLASSES], N = B batch; a padding row is label -1 and zeros."""
+        bt, iw, ow = ops.box_head_target_blobs(self.labels, self.targets, self.cfg.num_classes)
+        return dict(labels_int32=self.labels.reshape(-1), rois=self.rois7, bbox_targets=bt, bbox_inside_weights=iw, bbox_outside_weights=ow)
+
+    def numpy(self):
+        """Host copies trimmed to their counts (synchronises): one dict of rows, labels, rois, targets, counts per image."""
+        c = self.counts.cpu().numpy()
+        rows, labels, rois, targets = (t.cpu().numpy() for t in (self.rows, self.labels, self.rois, self.targets))
+        return [dict(rows=rows[b, :c[b, 0]], labels=labels[b, :c[b, 0]], rois=rois[b, :c[b, 0]], targets=targets[b, :c[b, 0]], counts=c[b])
+                for b in range(len(c))]
+
+
+def _per_image(values, gt_list, dtype, device, name):
+    """per-image class / crowd arrays -> one device tensor over the concatenated boxes; an image given as None takes the default"""
+    if values is None:
+        return None
+    if len(values) != len(gt_list):
+        raise ops.M3DError("box_head_targets: %s needs one entry per image" % name)
+    parts = []
+    for v, g in zip(values, gt_list):
+        if v is None:
+            v = torch.full((g.shape[0],), 1 if name == "gt_classes" else 0, dtype=dtype, device=device)
+        elif not torch.is_tensor(v):
+            v = torch.from_numpy(np.ascontiguousarray(v).astype(np.int64).reshape(-1)).to(device)
+        if v.numel() != g.shape[0]:
+            raise ops.M3DError("box_head_targets: %s has %d entries for %d boxes" % (name, v.numel(), g.shape[0]))
+        parts.append(v.reshape(-1).to(device=device, dtype=dtype))
+    return torch.cat(parts).contiguous()
+
+
+def box_head_targets(rois, num, gt_boxes, cfg, seed, gt_classes=None, gt_crowd=None):
+    """Labels the proposals of B images against their ground-truth boxes, samples BATCH_SIZE_PER_IM rows per image and computes their
+    regression targets, on the device and without a host round trip.
+
+    rois fp32 [B,rows,7] and num int32 [B]: as ops.generate_proposals3d_batched returns them (CUDA).  gt_boxes: one NumPy or CUDA fp32
+    [K_b,6] array per image; gt_classes / gt_crowd: None, or per image an array of K_b classes (1 .. NUM_CLASSES-1) / crowd flags (or
+    None for "all 1" / "none").  seed: one 64-bit seed per image, or one base seed (image b then samples with seed + b).  The result is
+    a pure function of the inputs and the seeds, bit-identical run to run.
+
+    An image without (non-crowd) boxes: the reference raises IndexError in _sample_rois; here every proposal has overlap 0, so there is
+    no fg row and the batch fills with bg rows."""
+    if not torch.is_tensor(rois) or not torch.is_tensor(num) or not rois.is_cuda or not num.is_cuda:
+        raise ops.M3DError("box_head_targets: rois and num must be CUDA (ROCm) tensors; there is no CPU path")
+    dev = rois.device
+    gts = [_boxes(g, dev) for g in gt_boxes]
+    if len(gts) != rois.shape[0]:
+        raise ops.M3DError("box_head_targets: %d box arrays for %d images" % (len(gts), rois.shape[0]))
+    ops._need_gpu(*gts)
+    off = np.concatenate([[0], np.cumsum([g.shape[0] for g in gts])]).astype(np.int32)
+    gt = torch.cat([g.float() for g in gts]) if gts else torch.zeros((0, 6), device=dev)
+    seeds = [int(s) for s in seed] if np.ndim(seed) else [int(seed) + b for b in range(len(gts))]
+    out = ops.box_head_target_sets(rois, num, gt, off, _per_image(gt_classes, gts, torch.int32, dev, "gt_classes"),
+                                   _per_image(gt_crowd, gts, torch.uint8, dev, "gt_crowd"), cfg.batch_per_im, cfg.fg_per_im, cfg.fg_thresh,
+                                   cfg.bg_thresh_hi, cfg.bg_thresh_lo, cfg.bbox_reg_weights, cfg.num_classes, seeds,
+                                   cfg.cls_agnostic_bbox_reg)
+    return BoxHeadTargets(*out, cfg=cfg)
+
+
+class _BoxHeadLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, score, pred, labels, targets, counts):
+        losses, gs, gp = ops.box_head_loss_grad(score, pred, labels, targets, counts)
+        ctx.save_for_backward(gs, gp)
+        accuracy = losses[2]
+        ctx.mark_non_differentiable(accuracy)
+        return losses[0], losses[1], accuracy
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box, g_acc):
+        gs, gp = ctx.saved_tensors
+        return gs * g_cls, gp * g_box, None, None, None
+
+
+def box_head_losses(cls_score, bbox_pred, targets):
+    """(loss_cls, loss_bbox, accuracy_cls) of fast_rcnn_losses for cls_score [B batch, C] and bbox_pred [B batch, 6 C] computed on
+    `targets.rois7`; `targets`: the BoxHeadTargets of the minibatch.  The mean runs over the sampled rows (padding rows count nowhere and
+    get zero gradients).  One launch computes the losses and both gradients; backward scales the stored gradients."""
+    return _BoxHeadLoss.apply(cls_score, bbox_pred, targets.labels, targets.targets, targets.counts)

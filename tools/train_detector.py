@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Demo: the joint RPN + box-head training step on one synthetic tile, without leaving the device between the RPN and the box-head loss.
+
+What tools/train_rpn.py does, extended by the box head: body -> RPN head -> m3d.rpn_targets / m3d.rpn_losses;
+m3d.generate_proposals3d_batched under no_grad with the TRAIN top-N settings (RPN_PRE_NMS_TOP_N 1000, RPN_POST_NMS_TOP_N 2000,
+RPN_NMS_THRESH 0.7); m3d.box_head_targets on those proposals and the ground-truth boxes; RoIAlign (7^3, sampling ratio 2) -> two FC
+layers -> cls_score / bbox_pred (lib/modeling/fast_rcnn_heads.py:12-47, 74-117) as plain torch.nn modules whose convolutions, linear
+layers and RoIAlign run on libm3d through m3d.compat; m3d.box_head_losses; torch.optim.SGD on the sum of the four losses.
+Prints all four losses per step.  One fixed sample; this is not a training driver (no data loading, schedule or checkpoints)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "instanceseg-without-voxelwise-labeling_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_box_head(dim_in, hidden, num_classes, stride):
+    import torch.nn as nn
+    import torch.nn.functional as F
+    from m3d.compat import RoIAlign_3d
+
+    class BoxHead(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.roi_align = RoIAlign_3d(7, 7, 7, 1.0 / stride, 2)
+            self.fc1, self.fc2 = nn.Linear(dim_in * 7 ** 3, hidden), nn.Linear(hidden, hidden)
+            self.cls_score, self.bbox_pred = nn.Linear(hidden, num_classes), nn.Linear(hidden, 6 * num_classes)
+            for m in (self.fc1, self.fc2):
+                nn.init.xavier_uniform_(m.weight)
+                nn.init.constant_(m.bias, 0)
+            nn.init.normal_(self.cls_score.weight, std=0.01)          # fast_rcnn_heads.py:23-27
+            nn.init.normal_(self.bbox_pred.weight, std=0.001)
+            nn.init.constant_(self.cls_score.bias, 0)
+            nn.init.constant_(self.bbox_pred.bias, 0)
+
+        def forward(self, feat, rois7):
+            x = self.roi_align(feat, rois7)
+            x = F.relu(self.fc1(x.reshape(x.shape[0], -1)))
+            x = F.relu(self.fc2(x))
+            return self.cls_score(x), self.bbox_pred(x)
+    return BoxHead()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--tile", type=int, nargs=3, default=(32, 64, 64), help="slices height width, multiples of 8")
+    ap.add_argument("--width", type=int, default=16, help="channels of the first conv (the reference has 32)")
+    ap.add_argument("--hidden", type=int, default=256, help="width of the two FC layers (the reference has 1024)")
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    import torch
+    import m3d
+    import m3d.compat
+    from m3d.synth import synth_volume, synth_volume_boxes
+    from train_rpn import build_model
+    assert torch.cuda.is_available(), "train_detector needs a GPU"
+    m3d.compat.install()
+    torch.manual_seed(a.seed)
+    tile = tuple(a.tile)
+    rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
+    vol = synth_volume(0, tile).astype(np.float32)
+    x = torch.from_numpy((vol - vol.mean()) / vol.std())[None, None].cuda()
+    gt = torch.from_numpy(synth_volume_boxes(0, tile)).cuda()
+    net = build_model(rcfg.num_anchors, a.width).cuda()
+    head = build_box_head(8 * a.width, a.hidden, bcfg.num_classes, rcfg.stride).cuda()
+    net.train()
+    for m in net.modules():                       # the reference trains with frozen BatchNorm statistics
+        if isinstance(m, torch.nn.BatchNorm3d):
+            m.eval()
+    opt = torch.optim.SGD(list(net.parameters()) + list(head.parameters()), lr=a.lr, momentum=0.9)
+    im_info = np.array([tile[0], tile[1], tile[2], 1.0])
+    for step in range(a.steps):
+        seed = 1000 * a.seed + step                                                # one sampling seed per step
+        feat = net.body(x)
+        logits, pred = net.head(feat)
+        loss_rpn_cls, loss_rpn_bbox = m3d.rpn_losses(logits, pred, m3d.rpn_targets(gt, tile, rcfg, seed=seed))
+        with torch.no_grad():                                                      # generate_proposals_3d.py: no gradient through the proposals
+            rois, _, _, num = m3d.generate_proposals3d_batched(torch.sigmoid(logits), pred, rcfg.cell_anchors, float(rcfg.stride), im_info,
+                                                               1000, 2000, 0.7)
+        targets = m3d.box_head_targets(rois, num, [gt], bcfg, seed=seed)
+        cls_score, bbox_pred = head(feat, targets.rois7)
+        loss_cls, loss_bbox, accuracy = m3d.box_head_losses(cls_score, bbox_pred, targets)
+        total = loss_rpn_cls + loss_rpn_bbox + loss_cls + loss_bbox
+        opt.zero_grad()
+        total.backward()
+        opt.step()
+        print("step %d loss_rpn_cls %.6f loss_rpn_bbox %.6f loss_cls %.6f loss_bbox %.6f accuracy_cls %.4f total %.6f" % (
+            step, loss_rpn_cls.item(), loss_rpn_bbox.item(), loss_cls.item(), loss_bbox.item(), accuracy.item(), total.item()), flush=True)
+
+
+if __name__ == "__main__":
+    main()
