@@ -35,10 +35,12 @@ const char* m3d_last_hip_error(void);
  * m3d_set_option returns M3D_EUNSUPPORTED for every known name and m3d_get_option reports the built-in defaults.  The knobs are live only
  * in libm3d_tune.so (same objects, m3d_core built with -DM3D_TUNING; m3d_tuning_build() == 1), which the scripts under tools/ and the kernel-family tests load
  * beside the release library.  Names: "xcd_map" (1: XCD-aware workgroup->tile order, default; 0: plain order), "tune_k3", "tune_wino",
- * "tune_wino2", "tune_wino2_xt" (tile-variant overrides of the conv dispatchers, -1 = library chooses), "tune_fc_slices" /
+ * "tune_wino2_xt" (tile-variant overrides of the conv dispatchers, -1 = library chooses), "tune_wino2" (the 2-D Winograd family behind
+ * the default entry points: -1 or 499 = F(2x4,3x3), the library's choice; 299 = F(2x2,3x3); with any other value the
+ * m3d_conv3d_wino2_* launches and m3d_conv3d_wino2_plan return M3D_EUNSUPPORTED, the scores and workspace sizes are 0), "tune_fc_slices" /
  * "tune_fc_slices_tail" (split-K factors of m3d_linear_forward), "tune_fc_x3_rows" (128 / 256: tile height of m3d_linear_bf16x3_forward),
  * "tune_fc_x_alias" (> 0: m3d_linear_bf16x3_forward reads row m of x from row m % value - a cache-resident operand, WRONG results:
- * the GEMM's cost with a free operand, tools/f1_ab.py), "tune_stem" (1: the round-2 one-row stem kernel; 4 / 8: the rows kernel with that many planes per workgroup; -1: rows kernel, planes by
+ * the GEMM's cost with a free operand, tools/f1_ab.py), "tune_stem" (4 / 8: the stem's rows kernel with that many planes per workgroup; any other value: planes by
  * grid size), "tune_fc_x3_rows" = 512 (the 256 x 256 tiles of m3d_linear_f16x2_forward), "tune_roi_xcd" (1: RoIAlign3D's XCD-aware
  * channel split - every XCD one eighth of every RoI's channels; an A/B that removed the L2 misses and not the time, round 6).
  * Unknown name -> M3D_EINVAL. */
@@ -201,9 +203,9 @@ size_t m3d_conv3d_wino2_workspace_bytes(int batch, int cin, int cout, int depth,
 double m3d_conv3d_wino2_score(int batch, int cin, int cout, int depth, int height, int width);
 /* ... and for the exactly-local F(2x2,3x3) family of m3d_conv3d_wino2_local_forward_ws (other tiles, hence its own score) */
 double m3d_conv3d_wino2_local_score(int batch, int cin, int cout, int depth, int height, int width);
-/* the 2-D Winograd kernel family in use: 1-3 = F(2x2,3x3) variants (4/9 of the direct convolution's multiplies), 4 = F(2x4,3x3)
- * (F(2,3) along y, F(4,3) along x: 1/3; the default), 5 = F(2x4,3x3) with 64 output channels per 4-wave workgroup (A/B only; layers
- * whose cout is not a multiple of 64 run family 4); option "tune_wino2" / 100 selects one for A/B runs */
+/* the 2-D Winograd kernel family behind the default entry points: 4 = F(2x4,3x3) (F(2,3) along y, F(4,3) along x: 1/3 of the direct
+ * convolution's multiplies; the release library always), 2 = F(2x2,3x3) (4/9; the family of the "_local" entry points, here only
+ * under option "tune_wino2" = 299 of the tuning build), 0 = that option holds a value that names no family */
 int m3d_conv3d_wino2_family(void);
 /* What m3d_conv3d_wino2_forward_ws (local = 0) / m3d_conv3d_wino2_local_forward_ws (local = 1) would launch for this shape: kernel
  * family, tile id (32 / 16 / 8; 0: none) and K split (1: one accumulation chain per output over the input channels; s > 1: s partial

@@ -1,6 +1,6 @@
 // Internal interface of the Winograd F(2x4, 3x3) kernel family (conv3d_wino24.hip) used by conv3d_wino2.hip's entry points.
 #pragma once
-#include "conv3d_wino2q.h"
+#include "conv3d_wino2_common.h"
 
 namespace m3d_w24 {
 
@@ -28,9 +28,9 @@ size_t packed_floats(int cin, int cout);                       // its own weight
 int pack(const float* d_weight, int cin, int cout, float* d_packed, hipStream_t st);
 // xt = tile id of the shared tile choice: 32 -> 64 x 4 x 2 outputs per workgroup, 16 -> 32 x 8 x 2, 8 -> 16 x 16 x 2 (no fused pool)
 int launch(int xt, bool pool, bool argmax, const float* in, const float* wp, float* out, int B, int cin, int cout, int D, int H, int W,
-           m3d_w2q::Epi ep, hipStream_t st);
+           m3d_w2::Epi ep, hipStream_t st);
 // the non-pooled launch with the fused prepare epilogue: `out` is the B strip (already zero), D / H / W are the A strip's dimensions
-int launch_prep(int xt, const float* in, const float* wp, float* out, int cin, int cout, int D, int H, int W, m3d_w2q::Epi ep, const PrepEpi& pe,
+int launch_prep(int xt, const float* in, const float* wp, float* out, int cin, int cout, int D, int H, int W, m3d_w2::Epi ep, const PrepEpi& pe,
                 hipStream_t st);
 
 }  // namespace m3d_w24

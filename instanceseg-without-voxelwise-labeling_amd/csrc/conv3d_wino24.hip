@@ -131,7 +131,7 @@ struct Cfg24 {
 template <int CC, int XQ, int WZ, int WY, bool POOL, bool AM, bool PREP = false>
 __global__ __launch_bounds__(512, 2) void conv3d_wino24_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                                                               float* __restrict__ out, int cin, int cout, int D, int H, int W,
-                                                              int tiles_x, int tiles_y, int tiles_z, int ncb_total, m3d_w2q::Epi ep,
+                                                              int tiles_x, int tiles_y, int tiles_z, int ncb_total, m3d_w2::Epi ep,
                                                               m3d_w24::PrepEpi pe) {
   using C = Cfg24<CC, XQ, WZ, WY, POOL>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -658,7 +658,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_wino24_kernel(const float* __re
 }
 
 template <int XQ, int WZ, int WY, bool POOL, bool AM, bool PREP = false>
-int launch24(const float* in, const float* wp, float* out, int B, int cin, int cout, int D, int H, int W, m3d_w2q::Epi ep, hipStream_t st,
+int launch24(const float* in, const float* wp, float* out, int B, int cin, int cout, int D, int H, int W, m3d_w2::Epi ep, hipStream_t st,
              const m3d_w24::PrepEpi& pe = m3d_w24::PrepEpi{}) {
   using C = Cfg24<4, XQ, WZ, WY, POOL>;
   const int tiles_x = (W + C::TX - 1) / C::TX, tiles_y = (H + C::TY - 1) / C::TY, tiles_z = (D + C::TZ - 1) / C::TZ;
@@ -695,7 +695,7 @@ int pack(const float* d_weight, int cin, int cout, float* d_packed, hipStream_t 
 
 // xt = the tile id of conv3d_wino2.hip's tile choice: 32 -> 64 x 4 x 2 outputs, 16 -> 32 x 8 x 2, 8 -> 16 x 16 x 2
 int launch(int xt, bool pool, bool argmax, const float* in, const float* wp, float* out, int B, int cin, int cout, int D, int H, int W,
-           m3d_w2q::Epi ep, hipStream_t st) {
+           m3d_w2::Epi ep, hipStream_t st) {
   if (argmax && !pool) return M3D_EINVAL;
   if (xt == 32) {
     if (!pool) return launch24<16, 2, 1, false, false>(in, wp, out, B, cin, cout, D, H, W, ep, st);
@@ -711,7 +711,7 @@ int launch(int xt, bool pool, bool argmax, const float* in, const float* wp, flo
   return M3D_EUNSUPPORTED;
 }
 
-int launch_prep(int xt, const float* in, const float* wp, float* out, int cin, int cout, int D, int H, int W, m3d_w2q::Epi ep, const PrepEpi& pe,
+int launch_prep(int xt, const float* in, const float* wp, float* out, int cin, int cout, int D, int H, int W, m3d_w2::Epi ep, const PrepEpi& pe,
                 hipStream_t st) {
   if (ep.ksplit > 1 || ep.scale || ep.shift || ep.relu) return M3D_EINVAL;       // the fused epilogue is the whole epilogue
   if (xt == 32) return launch24<16, 2, 1, false, false, true>(in, wp, out, 1, cin, cout, D, H, W, ep, st, pe);

@@ -32,6 +32,15 @@ HUGE = (512, 512, 512)          # conv2a's batch item is 2 GiB: batch 1, detecti
 GUARD = 0x7FFFFFFF              # bytes of one batch item from which the Winograd / f16x2 kernels' 32-bit offsets no longer reach
 ZW_LAYERS = ((32, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256))      # (cin, cout) of the 3^3 convs of both nets
 
+# the 2-D Winograd plan table (tests/golden/wino2_plan.json.gz, written by tests/golden/gen_wino2_plan.py): every host query of
+# conv3d_wino2.hip over batch x layer x depth x (height = width), and the bytes of the stem's rows pack
+PLAN_FIXTURE = os.path.join(ROOT, "tests", "golden", "wino2_plan.json.gz")
+PLAN_LAYERS = ZW_LAYERS + ((4, 8), (64, 35))
+PLAN_DEPTHS = (4, 9, 16, 64)
+PLAN_WIDTHS = (8, 11, 12, 23, 24, 40, 47, 48, 64, 70, 128)
+STEM_COUTS = (8, 32, 35, 40, 64, 128, 256)
+M3D_EUNSUPPORTED = -4
+
 DETECTION_ENTRIES = ("m3d_conv3d_forward", "m3d_conv3d_forward_pool2", "m3d_conv3d_wino_forward", "m3d_conv3d_wino_forward_pool2",
                      "m3d_conv3d_wino2_forward_ws", "m3d_conv3d_wino2_forward_pool2", "m3d_conv3d_zw_forward pool=0",
                      "m3d_conv3d_zw_forward pool=1", "m3d_conv3d_stem_wino_forward_bound", "m3d_maxpool3d_2x_forward",
@@ -259,3 +268,72 @@ def test_prm_forward_keeps_32bit_kernels_below_the_guard():
                     seen += big
                     assert not (big and ("wino" in launch[0] or "zw" in launch[0])), (net, env, launch)
         assert seen >= len(NETS) * len(ENVS)
+
+
+def wino2_plan(L, local, batch, cin, cout, d, h, w):
+    """(return code, [family, tile id, K split]) of m3d_conv3d_wino2_plan"""
+    fam, tile, ks = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    rc = L.m3d_conv3d_wino2_plan(local, batch, cin, cout, d, h, w, C.byref(fam), C.byref(tile), C.byref(ks))
+    return rc, [fam.value, tile.value, ks.value]
+
+
+def wino2_plan_table(L, stem_pack_bytes=None):
+    """what the library `L` answers over the plan grid: {"plans": [[batch, cin, cout, D, H = W, plan, local plan, score, local score,
+    workspace bytes, local workspace bytes], ...], "stem_pack_bytes": [[cout, bytes], ...]}; scores are the library's doubles"""
+    rows = []
+    for batch, (cin, cout), d, hw in itertools.product(BATCHES, PLAN_LAYERS, PLAN_DEPTHS, PLAN_WIDTHS):
+        a = (batch, cin, cout, d, hw, hw)
+        plans = []
+        for local in (0, 1):
+            rc, plan = wino2_plan(L, local, *a)
+            assert rc == 0, (local, a, rc)
+            plans.append(plan)
+        rows.append([batch, cin, cout, d, hw] + plans + [L.m3d_conv3d_wino2_score(*a), L.m3d_conv3d_wino2_local_score(*a),
+                                                        L.m3d_conv3d_wino2_workspace_bytes(*a), L.m3d_conv3d_wino2_local_workspace_bytes(*a)])
+    stem = stem_pack_bytes or L.m3d_conv3d_stem_wino_packed_weight_bytes
+    return json.loads(json.dumps({"plans": rows, "stem_pack_bytes": [[c, stem(c)] for c in STEM_COUTS]}))
+
+
+def test_wino2_plan_table_matches_the_record():
+    """tile choice, split-K plan, scores (exactly: the same double arithmetic) and workspace sizes of both 2-D Winograd families, and
+    the size of the stem's weight pack, as recorded before the A/B-only families and the one-row stem kernel were retired"""
+    import __graft_entry__ as g
+    g.build()
+    from m3d import _lib
+    with gzip.open(PLAN_FIXTURE, "rt") as f:
+        want = json.load(f)
+    assert len(want["plans"]) == len(BATCHES) * len(PLAN_LAYERS) * len(PLAN_DEPTHS) * len(PLAN_WIDTHS)
+    L = _lib.lib()
+    assert not L.m3d_tuning_build()
+    got = wino2_plan_table(L)
+    for g_row, w_row in zip(got["plans"], want["plans"]):
+        assert g_row == w_row
+    assert got == want
+
+
+def test_wino2_option_names_family_2_or_4_and_nothing_else():
+    """tune_wino2 of the tuning build: 299 runs the F(2x2) family behind the default entry points, 499 and -1 the default F(2x4); any
+    other value is refused by the plan and scores / sizes 0.  No device call."""
+    import __graft_entry__ as g
+    g.build()
+    from m3d import _lib
+    a = (1, 64, 64, 32, 32, 32)
+    with _lib.tuning():
+        L = _lib.lib()
+        assert L.m3d_tuning_build()
+        default, local = wino2_plan(L, 0, *a), wino2_plan(L, 1, *a)
+        assert default[0] == 0 and local[0] == 0 and default[1][0] == 4 and local[1][0] == 2
+        assert L.m3d_conv3d_wino2_score(*a) > 0 and L.m3d_conv3d_wino2_local_score(*a) > 0
+        for bad in (0, 3, 199, 399, 599):
+            _lib.set_option("tune_wino2", bad)
+            for loc in (0, 1):
+                assert L.m3d_conv3d_wino2_plan(loc, *a, None, None, None) == M3D_EUNSUPPORTED, (bad, loc)
+            assert L.m3d_conv3d_wino2_score(*a) == 0.0 and L.m3d_conv3d_wino2_workspace_bytes(*a) == 0, bad
+            assert L.m3d_conv3d_wino2_family() == 0, bad
+        _lib.set_option("tune_wino2", 299)
+        assert wino2_plan(L, 0, *a) == local and L.m3d_conv3d_wino2_family() == 2
+        assert L.m3d_conv3d_wino2_score(*a) == L.m3d_conv3d_wino2_local_score(*a)
+        for same in (499, -1):
+            _lib.set_option("tune_wino2", same)
+            assert wino2_plan(L, 0, *a) == default and wino2_plan(L, 1, *a) == local and L.m3d_conv3d_wino2_family() == 4
+    assert _lib.get_option("tune_wino2") == -1

@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
-"""Where a workgroup of the eta-split Winograd kernel spends its cycles: prologue / K loop / eta exchange / epilogue.
+"""Where a workgroup of the 2-D Winograd kernels spends its cycles: prologue / K loop / eta exchange / epilogue.
 
 Needs the diagnostic library (make -C instanceseg-without-voxelwise-labeling_amd/csrc w2_stamps) and a GPU:
     M3D_LIB_PATH=.../csrc/libm3d_w2stamps.so python tools/w2_stamps.py [layer ...]
 One wave per workgroup stamps s_memtime at kernel entry, after the prologue barrier, after the K loop, after the exchange barrier
-and after its last store (+ s_memrealtime at both ends for the clock).  Ideal K-loop cycles per chunk = 96 MFMAs per SIMD x 64 (eta-split kernel: two
-waves of ONE workgroup per SIMD; quad kernel, M3D_TUNE_WINO2=399 or the default: a wave shares its SIMD with a wave of another workgroup, so
-its 48 MFMAs per chunk take 6144 cycles when both workgroups are in their K loops)."""
+and after its last store (+ s_memrealtime at both ends for the clock).  Ideal K-loop cycles per chunk = MFMAs per SIMD x 64: 72 for the
+default F(2x4,3x3) family, 96 for the eta-split F(2x2,3x3) kernel (M3D_TUNE_WINO2=299; two waves of ONE workgroup per SIMD)."""
 import os, sys, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "instanceseg-without-voxelwise-labeling_amd"))
@@ -31,11 +30,11 @@ for name in (sys.argv[1:] or ["conv2b", "conv2a", "conv3b", "conv4b"]):
     for _ in range(3):
         run()
     torch.cuda.synchronize()
-    for f in ("m3d_debug_set_stamp_buffer", "m3d_debug_set_stamp_buffer_q", "m3d_debug_set_stamp_buffer_24", "m3d_debug_set_stamp_buffer_24w"):   # every 2-D Winograd family
+    for f in ("m3d_debug_set_stamp_buffer", "m3d_debug_set_stamp_buffer_24"):   # both 2-D Winograd families
         getattr(L, f)(ctypes.c_void_p(buf.data_ptr()))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); run(); e1.record(); torch.cuda.synchronize()
-    for f in ("m3d_debug_set_stamp_buffer", "m3d_debug_set_stamp_buffer_q", "m3d_debug_set_stamp_buffer_24", "m3d_debug_set_stamp_buffer_24w"):
+    for f in ("m3d_debug_set_stamp_buffer", "m3d_debug_set_stamp_buffer_24"):
         getattr(L, f)(ctypes.c_void_p(0))
     ms = e0.elapsed_time(e1)
     st = buf.view(-1, 8).cpu()
@@ -46,8 +45,8 @@ for name in (sys.argv[1:] or ["conv2b", "conv2a", "conv3b", "conv4b"]):
     tot = t[:, 4] - t[:, 0]
     clk = (tot / (st[:, 6] - st[:, 5]).double().clamp(min=1) * 0.1).median().item()     # GHz: cycles per 10 ns tick
     fam = L.m3d_conv3d_wino2_family()
-    nchunk = cin // 2 if fam == 5 else cin // 4                    # family 5 stages one channel pair per chunk
-    IDEAL = 2304 if fam == 5 else 4608 if fam == 4 else 6144        # MFMA cycles per chunk and SIMD: 36 / 72 (F(2x4)) or 96 (F(2x2)) x 64
+    nchunk = cin // 4
+    IDEAL = 4608 if fam == 4 else 6144        # MFMA cycles per chunk and SIMD: 72 (F(2x4)) or 96 (F(2x2)) x 64
     med = [x_.median().item() for x_ in seg]
     span = (t[:, 4].max() - t[:, 0].min()).item()
     print("%-7s batch %d: %d workgroups, kernel %.3f ms (with stamps), clock %.2f GHz" % (name, BATCH, n, ms, clk))
