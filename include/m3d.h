@@ -170,6 +170,15 @@ int m3d_conv3d_forward_dilated(const float* d_in, const float* d_packed, float* 
                                int height, int width, int k, int dilation, const float* d_scale, const float* d_shift, int relu,
                                void* stream);
 
+/* Which instantiation of the direct kernel m3d_conv3d_forward (pool = 0; also _windowed and _split_sigmoid) or m3d_conv3d_forward_pool2
+ * (pool = 1) launches for this shape: a dense id in [0, m3d_conv3d_direct_plan_count()), the input channels it stages per chunk (1 for the
+ * 5^3 stem, whose K index is the tap), its voxel tile, the 32-channel output blocks per workgroup and its in-workgroup K split (1 or 2).
+ * Host only, no device call; returns exactly what the launch would return before launching (M3D_EUNSUPPORTED / M3D_EINVAL, outputs then
+ * untouched); any output pointer may be NULL.  The "tune_k3" option of the tuning build overrides the launch, not this answer. */
+int m3d_conv3d_direct_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int pool, int* variant, int* cc,
+                           int* tile_x, int* tile_y, int* tile_z, int* ncb, int* ksplit);
+int m3d_conv3d_direct_plan_count(void);
+
 /* 3x3x3 forward convolution with the Winograd F(2,3) transform along x (csrc/conv3d_wino.hip): the same operation as
  * m3d_conv3d_forward for k = 3, plain weights, no input offset / PRM multiply, at 2/3 of the MFMA work.  Results
  * agree with the direct kernel to a few fp32 ulp (tolerance of this path: 1e-4 relative, north_star), not bit for

@@ -614,49 +614,121 @@ M3D_API int m3d_conv3d_pack_weights(const float* d_weight, int cin, int cout, in
   return m3d::check_launch("pack_weights");
 }
 
-static int conv_dispatch(const float* d_in, const float* d_packed, float* d_out, int batch, int cin, int cout, int depth,
-                         int height, int width, int k, Epilogue ep, hipStream_t st, bool pool = false) {
-  if (!d_in || !d_packed || !d_out || batch <= 0 || cin <= 0 || cout <= 0 || depth <= 0 || height <= 0 || width <= 0)
-    return M3D_EINVAL;
-  const size_t DHW = (size_t)depth * height * width;
-  if (DHW * 32 >= 0x7FFFFFFFull) return M3D_EUNSUPPORTED;   // int offsets inside a channel chunk
+// ------------------------------------------------------------------------------------------------------
+// The tile choice.  Every production instantiation of the two kernels above has a dense id; direct_plan() is the ONE place that
+// maps a shape to an id (and to that instantiation's tile), conv_dispatch() launches what it names and m3d_conv3d_direct_plan
+// exports it, so a test can say which instantiation a shape runs.  The tune_k3 list in conv_dispatch holds A/B-only instantiations,
+// which have no id.
+//   X(id, K, CC, XB, ROWS, NCB, WZ, WY, POOL, KS)
+// ------------------------------------------------------------------------------------------------------
+#define M3D_DIRECT_CFGS(X)                                                                                                \
+  X(0, 3, 4, 32, 4, 1, 4, 1, false, 1)   /* <= 32 output channels, 32-wide x blocks */                                    \
+  X(1, 3, 4, 16, 2, 1, 4, 1, false, 1)   /* <= 32 output channels, 16-wide */                                             \
+  X(2, 3, 4, 8, 2, 1, 4, 1, false, 1)    /* <= 32 output channels, 8-wide */                                              \
+  X(3, 3, 2, 32, 4, 2, 4, 1, false, 1)   /* the 32 x 4 x 4 tile: >= 512 workgroups of it (every >= 64^3 layer) */          \
+  X(4, 3, 8, 32, 2, 2, 4, 1, false, 2)   /* 32^3-class maps, K split over two groups of 4 waves */                        \
+  X(5, 3, 8, 32, 1, 2, 4, 1, false, 2)   /* fewer than one such workgroup per CU: half the voxel tile */                  \
+  X(6, 3, 2, 32, 2, 2, 4, 1, false, 1)   /* 32 x 2 x 4 without the K split (cin < 16, or >= 1024 workgroups) */            \
+  X(7, 3, 4, 32, 1, 2, 4, 1, false, 1)   /* small 32-wide maps */                                                         \
+  X(8, 3, 4, 16, 2, 2, 4, 1, false, 1)   /* 16-wide, >= 1024 workgroups */                                                \
+  X(9, 3, 4, 16, 1, 1, 4, 1, false, 1)   /* 16-wide, the quarter-size tile */                                             \
+  X(10, 3, 8, 16, 1, 1, 4, 1, false, 2)  /* 16^3-class maps, K split */                                                   \
+  X(11, 3, 4, 8, 2, 2, 4, 1, false, 1)   /* 8-wide, >= 512 workgroups */                                                  \
+  X(12, 3, 4, 8, 1, 1, 4, 1, false, 1)   /* 8-wide, small */                                                              \
+  X(13, 3, 2, 32, 4, 2, 2, 2, true, 1)   /* k = 3 fused with the 2x2x2 max-pool */                                        \
+  X(14, 1, 32, 32, 1, 2, 4, 1, false, 1) /* k = 1, width >= 24 */                                                         \
+  X(15, 1, 32, 16, 1, 2, 4, 1, false, 1) /* k = 1, width 12..23 */                                                        \
+  X(16, 1, 32, 8, 1, 2, 4, 1, false, 1)  /* k = 1, width < 12 */
+enum { DV_STEM_POOL = 17, DV_STEM_32 = 18, DV_STEM_64 = 19, DV_COUNT = 20 };   // conv3d_stem5_kernel: 32 x 4 x 4 tiles (32 x ROWS x 4)
+
+struct DirectPlan { int variant, cc, tile_x, tile_y, tile_z, ncb, ksplit; };
+
+// the id for a shape, or a (negative) M3D_E* code
+static int direct_choose(int batch, int cin, int cout, int depth, int height, int width, int k, bool pool) {
   if (k == 5) {
-    ep.xcd_map = xcd_map_enabled();
     if (cin != 1 || cout > 64) return M3D_EUNSUPPORTED;
-    const int tiles_x = (width + 31) / 32;
-    if (batch > 65535) return M3D_EUNSUPPORTED;
-    auto lds_bytes = [](int ty, int tz, int ncb) { return sizeof(float) * ((36 * (ty + 4) * (tz + 4) + 8 + 3) / 4 * 4 + ncb * 63 * 64); };
-    if (pool) {      // tile 32 x 4 x 4, waves 2(z) x 2(y), each wave = one 2x2 (z,y) pooling footprint
-      if (cout > 32) return M3D_EUNSUPPORTED;
-      const int ty = (height + 3) / 4, tz = (depth + 3) / 4;
-      hipLaunchKernelGGL((conv3d_stem5_kernel<4, 1, 2, 2, true>), dim3((unsigned)(tiles_x * ty * tz), batch), dim3(256),
-                         lds_bytes(4, 4, 1), st, d_in, d_packed, d_out, cout, depth, height, width, tiles_x, ty, ep);
-    } else if (cout <= 32) {
-      constexpr int ROWS = M3D_STEM_ROWS;
-      const int ty = (height + ROWS - 1) / ROWS, tz = (depth + 3) / 4;
-      hipLaunchKernelGGL((conv3d_stem5_kernel<ROWS, 1, 4, 1, false>), dim3((unsigned)(tiles_x * ty * tz), batch), dim3(256),
-                         lds_bytes(ROWS, 4, 1), st, d_in, d_packed, d_out, cout, depth, height, width, tiles_x, ty, ep);
-    } else {
-      const int ty = (height + 3) / 4, tz = (depth + 3) / 4;
-      hipLaunchKernelGGL((conv3d_stem5_kernel<4, 2, 4, 1, false>), dim3((unsigned)(tiles_x * ty * tz), batch), dim3(256),
-                         lds_bytes(4, 4, 2), st, d_in, d_packed, d_out, cout, depth, height, width, tiles_x, ty, ep);
-    }
-    return m3d::check_launch("conv3d_stem5");
+    if (pool) return cout > 32 ? M3D_EUNSUPPORTED : DV_STEM_POOL;   // tile 32 x 4 x 4, waves 2(z) x 2(y), each wave = one 2x2 (z,y) pooling footprint
+    return cout <= 32 ? DV_STEM_32 : DV_STEM_64;
   }
   if (k == 3) {
     // Tile choice: keep >= ~2 workgroups per CU in flight; prefer big tiles (more MFMAs per staged byte);
     // pick the x-block (32/16/8) that wastes the fewest lanes on this width.
-    const long long vox = (long long)batch * DHW;
+    const long long vox = (long long)batch * depth * height * width;
     const int ncb_total = (cout + 31) / 32;
     auto waste = [&](int xb) { return (double)((width + xb - 1) / xb * xb) / width; };
     int xb = 32;
     if (waste(16) < waste(xb) - 0.05) xb = 16;
     if (waste(8) < waste(xb) - 0.05) xb = 8;
-    if (pool) {
-      if (width < 24) return M3D_EUNSUPPORTED;
-      return launch_cfg<3, 2, 32, 4, 2, 2, 2, true>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
+    if (pool) return width < 24 ? M3D_EUNSUPPORTED : 13;
+    if (ncb_total == 1)   // <= 32 output channels (e.g. the dgrad of conv2a): never pad to a second, empty cout block
+      return xb == 32 ? 0 : xb == 16 ? 1 : 2;
+    if (xb == 32) {
+      const long long wg_big = (vox / 512) * ((ncb_total + 1) / 2);
+      if (wg_big >= 512) return 3;
+      const long long wg_mid = (vox / 256) * ((ncb_total + 1) / 2);
+      // 32^3-class maps: one workgroup per CU -> split K over two groups of 4 waves (2 waves/SIMD)
+      if (wg_mid >= 256 && wg_mid < 1024 && cin >= 16) return 4;
+      // fewer than one such workgroup per CU (e.g. 128 -> 64 channels on 32^3, the dgrad of conv3a): halve the voxel tile
+      if (wg_mid >= 64 && wg_mid < 256 && cin >= 16) return 5;
+      if (wg_mid >= 256) return 6;
+      return 7;
     }
-    // tuning override (tools/bench_layers.py only): m3d_set_option("tune_k3", <variant index>)
+    if (xb == 16) {
+      const long long wg = (vox / 256) * ((ncb_total + 1) / 2);
+      if (wg >= 1024) return 8;
+      // one to two rounds of the big tile (the soma tile's 32 x 80 x 80 maps: 800 workgroups on 512 slots) leave a ragged second round:
+      // the quarter-size tile (tools/tune_k3_prm.py, round 4: conv2a 0.256 -> 0.202 ms, conv2b 0.438 -> 0.382 ms; equal from 1250 up)
+      if (wg >= 512) return 9;
+      // 16^3-class maps: exactly one 32x32 output block per SIMD -> split K in the workgroup for 2 waves/SIMD
+      return cin >= 16 ? 10 : 9;
+    }
+    const long long wg = (vox / 256) * ((ncb_total + 1) / 2);
+    return wg >= 512 ? 11 : 12;
+  }
+  if (pool) return M3D_EUNSUPPORTED;
+  if (k == 1) return width >= 24 ? 14 : width >= 12 ? 15 : 16;
+  return M3D_EUNSUPPORTED;
+}
+
+// Fills `p` and returns 0, or the code conv_dispatch returns for this shape.  p.variant >= 0 says the shape itself was accepted even
+// when a launch limit (grid size, batch) then refuses it.
+static int direct_plan(int batch, int cin, int cout, int depth, int height, int width, int k, bool pool, DirectPlan& p) {
+  p = DirectPlan{-1, 0, 0, 0, 0, 0, 0};
+  if (batch <= 0 || cin <= 0 || cout <= 0 || depth <= 0 || height <= 0 || width <= 0) return M3D_EINVAL;
+  const size_t DHW = (size_t)depth * height * width;
+  if (DHW * 32 >= 0x7FFFFFFFull) return M3D_EUNSUPPORTED;   // int offsets inside a channel chunk
+  const int v = direct_choose(batch, cin, cout, depth, height, width, k, pool);
+  if (v < 0) return v;
+  switch (v) {
+#define M3D_X(id, K, CC, XB, ROWS, NCB, WZ, WY, POOL, KS)                 \
+  case id: {                                                              \
+    using C = Cfg<K, CC, XB, ROWS, NCB, WZ, WY, POOL, KS>;                \
+    p = DirectPlan{id, CC, C::TX, C::TY, C::TZ, NCB, KS};                 \
+    break;                                                                \
+  }
+    M3D_DIRECT_CFGS(M3D_X)
+#undef M3D_X
+    case DV_STEM_POOL: p = DirectPlan{v, 1, 32, 4, 4, 1, 1}; break;
+    case DV_STEM_32: p = DirectPlan{v, 1, 32, M3D_STEM_ROWS, 4, 1, 1}; break;
+    default: p = DirectPlan{v, 1, 32, 4, 4, 2, 1}; break;
+  }
+  if (batch > 65535) return M3D_EUNSUPPORTED;
+  if (k != 5) {
+    const int co_tiles = ((cout + 31) / 32 + p.ncb - 1) / p.ncb;
+    const long long blocks = (long long)((width + p.tile_x - 1) / p.tile_x) * ((height + p.tile_y - 1) / p.tile_y) *
+                             ((depth + p.tile_z - 1) / p.tile_z) * co_tiles;
+    if (blocks > 0x7FFFFFFFll) return M3D_EUNSUPPORTED;
+  }
+  return M3D_OK;
+}
+
+static int conv_dispatch(const float* d_in, const float* d_packed, float* d_out, int batch, int cin, int cout, int depth,
+                         int height, int width, int k, Epilogue ep, hipStream_t st, bool pool = false) {
+  if (!d_in || !d_packed || !d_out) return M3D_EINVAL;
+  DirectPlan p;
+  const int rc = direct_plan(batch, cin, cout, depth, height, width, k, pool, p);
+  // tuning override (tools/bench_layers.py only): m3d_set_option("tune_k3", <variant index>)
+  if (k == 3 && !pool && p.variant >= 0) {
     if (const int v = m3d::opt(m3d::OPT_TUNE_K3); v >= 0) {
 #define M3D_V(i, ...) if (v == i) return launch_cfg<__VA_ARGS__>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
       M3D_V(0, 3, 2, 32, 4, 2, 4, 1)
@@ -688,47 +760,47 @@ static int conv_dispatch(const float* d_in, const float* d_packed, float* d_out,
       M3D_V(24, 3, 8, 16, 2, 1, 4, 1, false, 2)
 #undef M3D_V
     }
-    if (ncb_total == 1) {   // <= 32 output channels (e.g. the dgrad of conv2a): never pad to a second, empty cout block
-      if (xb == 32) return launch_cfg<3, 4, 32, 4, 1, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      if (xb == 16) return launch_cfg<3, 4, 16, 2, 1, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      return launch_cfg<3, 4, 8, 2, 1, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-    }
-    if (xb == 32) {
-      const long long wg_big = (vox / 512) * ((ncb_total + 1) / 2);
-      if (wg_big >= 512) return launch_cfg<3, 2, 32, 4, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      const long long wg_mid = (vox / 256) * ((ncb_total + 1) / 2);
-      // 32^3-class maps: one workgroup per CU -> split K over two groups of 4 waves (2 waves/SIMD)
-      if (wg_mid >= 256 && wg_mid < 1024 && cin >= 16)
-        return launch_cfg<3, 8, 32, 2, 2, 4, 1, false, 2>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      // fewer than one such workgroup per CU (e.g. 128 -> 64 channels on 32^3, the dgrad of conv3a): halve the voxel tile
-      if (wg_mid >= 64 && wg_mid < 256 && cin >= 16)
-        return launch_cfg<3, 8, 32, 1, 2, 4, 1, false, 2>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      if (wg_mid >= 256) return launch_cfg<3, 2, 32, 2, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      return launch_cfg<3, 4, 32, 1, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-    }
-    if (xb == 16) {
-      const long long wg = (vox / 256) * ((ncb_total + 1) / 2);
-      if (wg >= 1024) return launch_cfg<3, 4, 16, 2, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      // one to two rounds of the big tile (the soma tile's 32 x 80 x 80 maps: 800 workgroups on 512 slots) leave a ragged second round:
-      // the quarter-size tile (tools/tune_k3_prm.py, round 4: conv2a 0.256 -> 0.202 ms, conv2b 0.438 -> 0.382 ms; equal from 1250 up)
-      if (wg >= 512) return launch_cfg<3, 4, 16, 1, 1, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      // 16^3-class maps: exactly one 32x32 output block per SIMD -> split K in the workgroup for 2 waves/SIMD
-      if (cin >= 16) return launch_cfg<3, 8, 16, 1, 1, 4, 1, false, 2>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      return launch_cfg<3, 4, 16, 1, 1, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-    }
-    {
-      const long long wg = (vox / 256) * ((ncb_total + 1) / 2);
-      if (wg >= 512) return launch_cfg<3, 4, 8, 2, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-      return launch_cfg<3, 4, 8, 1, 1, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-    }
   }
-  if (pool) return M3D_EUNSUPPORTED;
-  if (k == 1) {
-    if (width >= 24) return launch_cfg<1, 32, 32, 1, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-    if (width >= 12) return launch_cfg<1, 32, 16, 1, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
-    return launch_cfg<1, 32, 8, 1, 2, 4, 1>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
+  if (rc != M3D_OK) return rc;
+  switch (p.variant) {
+#define M3D_X(id, K, CC, XB, ROWS, NCB, WZ, WY, POOL, KS) \
+  case id: return launch_cfg<K, CC, XB, ROWS, NCB, WZ, WY, POOL, KS>(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, ep, st);
+    M3D_DIRECT_CFGS(M3D_X)
+#undef M3D_X
+    default: break;
   }
-  return M3D_EUNSUPPORTED;
+  // the 5^3 stem
+  ep.xcd_map = xcd_map_enabled();
+  const int tiles_x = (width + p.tile_x - 1) / p.tile_x, ty = (height + p.tile_y - 1) / p.tile_y, tz = (depth + p.tile_z - 1) / p.tile_z;
+  const dim3 grid((unsigned)(tiles_x * ty * tz), batch);
+  auto lds_bytes = [](int ty, int tz, int ncb) { return sizeof(float) * ((36 * (ty + 4) * (tz + 4) + 8 + 3) / 4 * 4 + ncb * 63 * 64); };
+  if (p.variant == DV_STEM_POOL)
+    hipLaunchKernelGGL((conv3d_stem5_kernel<4, 1, 2, 2, true>), grid, dim3(256), lds_bytes(4, 4, 1), st, d_in, d_packed, d_out, cout, depth,
+                       height, width, tiles_x, ty, ep);
+  else if (p.variant == DV_STEM_32)
+    hipLaunchKernelGGL((conv3d_stem5_kernel<M3D_STEM_ROWS, 1, 4, 1, false>), grid, dim3(256), lds_bytes(M3D_STEM_ROWS, 4, 1), st, d_in, d_packed,
+                       d_out, cout, depth, height, width, tiles_x, ty, ep);
+  else
+    hipLaunchKernelGGL((conv3d_stem5_kernel<4, 2, 4, 1, false>), grid, dim3(256), lds_bytes(4, 4, 2), st, d_in, d_packed, d_out, cout, depth,
+                       height, width, tiles_x, ty, ep);
+  return m3d::check_launch("conv3d_stem5");
+}
+
+M3D_API int m3d_conv3d_direct_plan_count(void) { return DV_COUNT; }
+
+M3D_API int m3d_conv3d_direct_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int pool, int* variant, int* cc,
+                                   int* tile_x, int* tile_y, int* tile_z, int* ncb, int* ksplit) {
+  DirectPlan p;
+  const int rc = direct_plan(batch, cin, cout, depth, height, width, k, pool != 0, p);
+  if (rc != M3D_OK) return rc;
+  if (variant) *variant = p.variant;
+  if (cc) *cc = p.cc;
+  if (tile_x) *tile_x = p.tile_x;
+  if (tile_y) *tile_y = p.tile_y;
+  if (tile_z) *tile_z = p.tile_z;
+  if (ncb) *ncb = p.ncb;
+  if (ksplit) *ksplit = p.ksplit;
+  return M3D_OK;
 }
 
 M3D_API int m3d_conv3d_forward(const float* d_in, const float* d_packed, float* d_out, int batch, int cin, int cout, int depth,
