@@ -969,6 +969,33 @@ int m3d_bn_backward(const float* d_x, const float* d_mean, const float* d_invstd
                     int relu, int pool, int training, float* d_grad_x, float* d_grad_gamma, float* d_grad_beta, void* d_ws,
                     size_t* ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The solver's parameter update (csrc/sgd.hip): torch.optim.SGD with momentum and weight decay as tools/train_net_step.py:316-331 builds
+ * it, over a whole parameter list in one launch, with the momentum-buffer scale of _CorrectMomentum (lib/utils/net.py:86-99) folded in.
+ * `tensors` is a HOST array of `count` descriptors: p, g, m device fp32 [n], each tensor with its own lr and wd.  Per element, in fp32,
+ * every operation rounded once and nothing contracted:
+ *     c = mscale m ;  d = (wd == 0) ? g : g + wd p ;  m' = momentum c + d ;  p' = p - lr m'
+ * p and m are updated in place, g is never written.  m == NULL is allowed only with momentum == 0: p' = p - lr d.  A zero-filled m on the
+ * first step gives torch's "first step: buf = grad"; mscale == 1 is exact.  The descriptors travel as kernel arguments (64 per launch; a
+ * longer list takes several launches): a step makes no host-to-device copy, no allocation and no host synchronisation.  Work is cut into
+ * chunks of m3d_sgd_chunk() elements of one tensor, a function of the sizes and their order only.  16-byte accesses from the first common
+ * 16-byte boundary of a chunk; a tensor whose pointers differ modulo 16 is updated element by element.
+ * d_stats (NULL, or device fp64 [2], 8-byte aligned): d_stats[0] = sum of g^2 over the raw gradients of the call in fp64 (the fp64 square
+ * of an fp32 value is exact), d_stats[1] = the number of non-finite gradient elements.  One partial and one count per chunk go to the
+ * workspace (16 bytes per chunk); a finish kernel adds them in a fixed order (thread t of 256 the partials t, t + 256, ... ascending in
+ * the call's chunk order, then a fixed tree): no floating-point atomics, bit-identical run to run for the same sizes, order, values and
+ * pointer residues modulo 16, however many launches the call takes.
+ * Workspace: ws_bytes != NULL with d_ws == NULL stores the bytes the call needs in *ws_bytes (0 with d_stats == NULL) and launches
+ * nothing; otherwise *ws_bytes is the capacity of d_ws (8-byte aligned; M3D_EWORKSPACE if too small).  Without d_stats both may be NULL.
+ * Limits, checked before any device pointer is followed or anything is launched: count < 0, n < 0, m == NULL with momentum != 0, a
+ * NULL or not 4-byte aligned pointer, overlapping p / g / m ranges of one tensor: M3D_EINVAL; count > 65536, n >= 2^40:
+ * M3D_EUNSUPPORTED.  count == 0 and tensors with n == 0 (whose pointers are not looked at) are legal and do nothing.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct { float* p; const float* g; float* m; long long n; float lr; float wd; } m3d_sgd_tensor;
+int m3d_sgd_chunk(void);
+int m3d_sgd_step(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, double* d_stats, void* d_ws, size_t* ws_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

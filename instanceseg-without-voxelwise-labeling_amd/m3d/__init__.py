@@ -7,3 +7,4 @@ from . import _lib  # noqa: F401
 from .ops import *  # noqa: F401,F403
 from .train import (RpnTrainCfg, RpnTargets, rpn_targets, rpn_losses, BoxHeadTrainCfg, BoxHeadTargets, box_head_targets,  # noqa: E402,F401
                     box_head_losses, bn_stats, batch_norm_relu, DsnBody)
+from .solver import SolverCfg, Solver, save_ckpt, load_ckpt  # noqa: E402,F401

@@ -34,7 +34,13 @@ SYMBOLS = [
     "m3d_rpn_targets_workspace_bytes", "m3d_rpn_targets", "m3d_rpn_targets_wide", "m3d_rpn_loss",
     "m3d_box_head_targets_workspace_bytes", "m3d_box_head_targets", "m3d_box_head_target_blobs", "m3d_box_head_loss",
     "m3d_bn_stats", "m3d_bn_invstd", "m3d_bn_apply", "m3d_bn_backward",
+    "m3d_sgd_chunk", "m3d_sgd_step",
 ]
+
+
+class SgdTensor(C.Structure):
+    """m3d_sgd_tensor of include/m3d.h: one parameter of an m3d_sgd_step call"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("n", C.c_longlong), ("lr", C.c_float), ("wd", C.c_float)]
 
 
 class M3DError(RuntimeError):

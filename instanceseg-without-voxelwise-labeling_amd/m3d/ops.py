@@ -7,13 +7,13 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import lib, check, M3DError
+from ._lib import lib, check, M3DError, SgdTensor
 
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -2128,3 +2128,45 @@ def bn_backward(x, mean, invstd, weight, bias, grad_out, argmax=None, relu=True,
                                             _ptr(argmax if pool else None), N, Cn, D, H, W, int(bool(relu)), int(bool(pool)),
                                             int(bool(training)), _ptr(gx), _ptr(gw), _ptr(gb), ws, nb, st), x.device, "bn_backward")
     return gx, gw, gb
+
+
+# ------------------------------------------------------------------ the solver's parameter update (csrc/sgd.hip)
+def sgd_chunk():
+    """elements of one tensor that one workgroup of m3d_sgd_step updates (the partition of its statistics)"""
+    return int(lib().m3d_sgd_chunk())
+
+
+def sgd_step(params, grads, bufs, lrs, wds, momentum, mscale=1.0, stats=None):
+    """m3d_sgd_step: one fused SGD update of a whole parameter list, in place and on the current stream.
+
+    params, grads: lists of contiguous CUDA fp32 tensors of equal sizes; bufs: the momentum buffers (same sizes), or None with momentum
+    == 0; lrs, wds: one float per tensor.  Per element c = mscale m, d = g + wd p (g where wd == 0), m' = momentum c + d, p' = p - lr m',
+    every fp32 operation rounded once.  stats: None, or a CUDA fp64 [2] tensor that receives (sum of g^2, number of non-finite gradient
+    elements).  The update goes through raw pointers and does not bump the tensors' `_version`: the caller drops what it cached on them
+    (m3d.compat.invalidate_packs(); m3d.Solver.step does)."""
+    n = len(params)
+    if bufs is None:
+        bufs = [None] * n
+    if not (len(grads) == len(bufs) == len(lrs) == len(wds) == n):
+        raise M3DError("sgd_step: params, grads, bufs, lrs and wds must have one entry per tensor")
+    arr = (SgdTensor * max(n, 1))()
+    for i in range(n):
+        p, g, m = params[i], grads[i], bufs[i]
+        for t, name in ((p, "params"), (g, "grads"), (m, "bufs")):
+            if t is None and name == "bufs":
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise M3DError("sgd_step: %s[%d] must be a CUDA (ROCm) tensor; there is no CPU path" % (name, i))
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                raise M3DError("sgd_step: %s[%d] must be a contiguous fp32 tensor of %d elements" % (name, i, p.numel()))
+        e = arr[i]
+        e.p, e.g, e.m, e.n, e.lr, e.wd = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), p.numel(), lrs[i], wds[i]
+    L, st = lib(), _stream()
+    mom, msc = C.c_float(float(momentum)), C.c_float(float(mscale))
+    if stats is None:
+        check(L.m3d_sgd_step(arr, n, mom, msc, None, None, None, st), "sgd_step")
+        return
+    _need_gpu(stats)
+    if stats.dtype != torch.float64 or stats.numel() != 2 or not stats.is_contiguous():
+        raise M3DError("sgd_step: stats must be a contiguous fp64 [2] tensor")
+    _bn_ws(lambda ws, nb: L.m3d_sgd_step(arr, n, mom, msc, _ptr(stats), ws, nb, st), stats.device, "sgd_step")
