@@ -87,6 +87,12 @@ int m3d_roi_align3d_forward_ws2(int aligned_slices, int aligned_height, int alig
                                 int sampling_ratio, const float* d_features, int batch, int channels, int slices,
                                 int height, int width, const float* d_rois, int num_rois, int roi_cols,
                                 float* d_output, void* d_workspace, size_t workspace_bytes, const float* d_feat_absmax, void* stream);
+/* ... and with the bound as feat_absmax_slots floats whose LARGEST is >= max |d_features|: the slot array the conv that produced the
+ * feature maps left (m3d_conv3d_zw_forward's d_out_max) instead of a sweep of them; 1 slot is _ws2. */
+int m3d_roi_align3d_forward_ws3(int aligned_slices, int aligned_height, int aligned_width, float spatial_scale,
+                                int sampling_ratio, const float* d_features, int batch, int channels, int slices, int height,
+                                int width, const float* d_rois, int num_rois, int roi_cols, float* d_output, void* d_ws,
+                                size_t ws_bytes, const float* d_feat_absmax, int feat_absmax_slots, void* stream);
 int m3d_roi_align3d_backward(int aligned_slices, int aligned_height, int aligned_width, float spatial_scale,
                              int sampling_ratio, const float* d_top_grad, const float* d_rois, int num_rois,
                              int roi_cols, float* d_bottom_grad, int batch, int channels, int slices, int height,
@@ -341,6 +347,35 @@ int m3d_compact_rows2(const void* d_src_a, size_t item_stride_bytes_a, size_t ro
  * bbox_transform_3d(rois[:, 1:7], deltas, weights) clipped to (clip_slices, clip_height, clip_width) when clip_slices > 0. */
 int m3d_box_head_outputs(const float* d_outs, const float* d_rois, int num_rois, int num_classes, const double* weights, double xform_clip,
                          double clip_slices, double clip_height, double clip_width, float* d_cls, float* d_bbox, float* d_pred, void* stream);
+/* The whole detection box head as ONE call: RoIAlign3D (roi_res^3 bins) -> fc1 -> fc2 (f16x2 split, ReLU) -> cls_score | bbox_pred as one
+ * GEMM -> m3d_box_head_outputs, launched on one stream exactly as m3d_roi_align3d_forward_ws, m3d_linear_f16x2_forward_bounds (twice),
+ * m3d_linear_forward and m3d_box_head_outputs launch them (same plans, same kernels: bit-identical results).  It exists for the host
+ * time between those launches: it follows the host read that sizes them, while the GPU is idle.  Every buffer is the caller's.
+ *   fixed per network: fc1_packed / fc2_packed (m3d_linear_f16x2_pack of [fc1_out, channels * roi_res^3] and [fc2_out, fc1_out]), the
+ *     biases, outs_weight [7 * num_classes, fc2_out] (cls_score rows, then bbox_pred rows) + outs_bias, the box-decoding weights;
+ *   per call: features [batch, channels, slices, height, width], rois [num_rois, 7], clip (slices, height, width; clip[0] <= 0: none);
+ *     feat_bound: feat_bound_slots floats whose largest is >= max |features| (what the last m3d_conv3d_zw_forward left), or NULL: fc1
+ *     sweeps its input; fc1_bound: m3d_conv3d_zw_slots() floats, ZERO on entry, through which fc1 hands fc2 its operand bound, or
+ *     NULL: fc2 sweeps its input;
+ *   buffers: x [num_rois, channels * roi_res^3], h1 [num_rois, fc1_out], h2 [num_rois, fc2_out], outs [num_rois, 7 * num_classes]
+ *     (intermediates), cls [num_rois, nc], bbox / pred [num_rois, 6 nc] (results), ws (m3d_box_head_workspace_bytes, 16-byte aligned).
+ * num_rois <= 32 is M3D_EUNSUPPORTED (such a batch runs the fp32-input GEMM through the per-layer entries); 0 rows: nothing to do. */
+typedef struct {
+  const void* fc1_packed; const float* fc1_bias; const void* fc2_packed; const float* fc2_bias;
+  const float* outs_weight; const float* outs_bias;
+  int channels, roi_res, sampling_ratio, fc1_out, fc2_out, num_classes;
+  float spatial_scale;
+  double weights[6]; double xform_clip;
+  const float* features; int batch, slices, height, width;
+  const float* rois; int num_rois;
+  double clip[3];
+  const float* feat_bound; int feat_bound_slots; float* fc1_bound;
+  float *x, *h1, *h2, *outs, *cls, *bbox, *pred;
+  void* ws; size_t ws_bytes;
+} m3d_box_head;
+/* bytes of ws that serve every num_rois in 1 .. max_rois (0: a description the call does not take) */
+size_t m3d_box_head_workspace_bytes(const m3d_box_head* head, int max_rois);
+int m3d_box_head_forward(const m3d_box_head* head, void* stream);
 size_t m3d_generate_proposals3d_batched_workspace_bytes(int batch, int A, int S, int H, int W, int pre_nms_topN);
 /* m3d_generate_proposals3d_batched: out_rows = rows of the per-item output blocks, >= min(K, post_nms_topN) with NMS; with nms_thresh <= 0
  * every valid box of the K pre-NMS candidates is a proposal (generate_proposals_3d.py:167-171), so out_rows must be >= K - M3D_EINVAL
@@ -407,6 +442,13 @@ int m3d_linear_f16x2_pack(const float* d_weight, int N, int K, void* d_packed, v
 size_t m3d_linear_f16x2_workspace_bytes(int M, int N, int K);
 int m3d_linear_f16x2_forward(const float* d_x, const void* d_packed, const float* d_bias, float* d_out, int M, int N, int K,
                              int relu, const float* d_x_bound, void* d_ws, size_t ws_bytes, void* stream);
+/* The same call with the bounds travelling as slot arrays, so that neither operand is swept: d_x_bound holds x_bound_slots floats whose
+ * LARGEST is the bound (1: an m3d_absmax result; m3d_conv3d_zw_slots(): what m3d_conv3d_zw_forward left in d_out_max, or what this call
+ * left in d_out_bound).  d_out_bound (or NULL): m3d_conv3d_zw_slots() floats, ZERO on entry, that receive max |d_out| from the launch
+ * that stores d_out (the split-K reduce, or the GEMM's epilogue when K is not split), one atomic maximum per workgroup. */
+int m3d_linear_f16x2_forward_bounds(const float* d_x, const void* d_packed, const float* d_bias, float* d_out, int M, int N, int K,
+                                    int relu, const float* d_x_bound, int x_bound_slots, float* d_out_bound, void* d_ws, size_t ws_bytes,
+                                    void* stream);
 
 /* f-1 A/B: the fc1 GEMM with the RoIAlign gather in its A-operand loader - the [M, C * 343] RoIAlign output is never
  * written.  m3d_roi_align3d_tap_tables: the RoIs' per-axis sample tables (7^3 bins, sampling grid 2 - the shipped geometry) -> d_tab

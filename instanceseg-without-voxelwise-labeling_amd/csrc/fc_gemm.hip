@@ -253,11 +253,37 @@ __global__ __launch_bounds__(256, 2) void fc_gemm_kernel(FcArgs a) {
   }
 }
 
+// Operand bounds that travel with the activations (as conv3d_zw.hip's in_max / out_max): an array of kBoundSlots floats whose largest
+// entry is >= max |x|.  A consumer takes the largest of the n slots it is given (n = 1: a plain m3d_absmax result); a producer adds
+// the largest |value| it stores with ONE atomic per workgroup into slot (block % kBoundSlots) of a zeroed array.
+constexpr int kBoundSlots = 32;
+
+__device__ inline float bound_max(const float* __restrict__ b, int n) {
+  float m = b[0];
+  for (int i = 1; i < n; ++i) m = fmaxf(m, b[i]);
+  return m;
+}
+
+// om = |value| bits (non-negative floats order like their bit patterns); every thread of the workgroup calls this; wmax: one LDS word
+// per wave that nobody else uses any more
+__device__ inline void block_bound_max(unsigned om, unsigned* __restrict__ out_max, unsigned* wmax) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)om, o); om = t > om ? t : om; }
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = om;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < (int)(blockDim.x >> 6); ++k) om = max(om, wmax[k]);
+    if (om) atomicMax(out_max + (blockIdx.x & (kBoundSlots - 1)), om);   // (reading the slot first to skip the atomic was slower: 30 vs 18 us)
+  }
+}
+
 // out[e] = act(bias[n] + sum_s part[s][e]), slices summed in index order (deterministic).  Rows below m_full were cut into
 // `slices` K ranges, the ragged last row tile into `slices_tail`; a part with one slice was stored directly (bias + act applied).
 __global__ __launch_bounds__(256) void fc_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias,
                                                         float* __restrict__ out, long long MN, int N, int slices, int slices_tail,
-                                                        long long full_elems /* m_full * N */, int relu) {
+                                                        long long full_elems /* m_full * N */, int relu,
+                                                        unsigned* __restrict__ out_max /* null, or kBoundSlots zeroed slots */) {
+  unsigned om = 0;                                                 // largest |value| this thread stores, as bits
   // four consecutive outputs per thread (N % 4 == 0: a quad never straddles a row or the full / tail boundary), every slice's quad one
   // 16-byte load, all issued before the first add; the sum order per element is slice 0, 1, 2, ... as before (bit-identical results)
   if ((N & 3) == 0 && ((((size_t)part) | ((size_t)out) | ((size_t)bias)) & 15) == 0) {
@@ -280,17 +306,22 @@ __global__ __launch_bounds__(256) void fc_reduce_kernel(const float* __restrict_
       if (bias) v += *reinterpret_cast<const f32x4r*>(bias + (int)(e % N));
       if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
       *reinterpret_cast<f32x4r*>(out + e) = v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) om = max(om, __float_as_uint(v[j]) & 0x7FFFFFFFu);
     }
-    return;
-  }
+  } else
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < MN; e += (long long)gridDim.x * 256) {
     const int ns = e < full_elems ? slices : slices_tail;
     if (ns == 1) continue;
     float v = part[e];
     for (int s = 1; s < ns; ++s) v += part[(size_t)s * MN + e];
     if (bias) v += bias[(int)(e % N)];
-    out[e] = relu ? fmaxf(v, 0.f) : v;
+    v = relu ? fmaxf(v, 0.f) : v;
+    out[e] = v;
+    om = max(om, __float_as_uint(v) & 0x7FFFFFFFu);
   }
+  __shared__ unsigned wmax[4];
+  if (out_max) block_bound_max(om, out_max, wmax);                 // the next layer's operand bound: no sweep of `out`
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -422,7 +453,9 @@ __global__ __launch_bounds__(256) void fc_f16_pack_kernel(const float* __restric
 struct FcX3Args {
   const float* x; const u32x4* wp; const float* bias; float* out; float* part;
   int M, N, K, mt, nt, slices, chunks, relu, per_xcd;
-  const float* xbound; const float* wamax;     // F16 = 1: device scalars, a bound of max|x| and max|W| (the scales' sources)
+  const float* xbound; const float* wamax;     // F16 = 1: device floats, a bound of max|x| (xbound_n slots) and max|W| (the scales' sources)
+  int xbound_n;
+  unsigned* out_max;       // F16 = 1, slices == 1: the direct-store epilogue adds the largest |value| it stores (null: nobody asks)
   int x_alias;             // > 0 (tuning build only, option tune_fc_x_alias): row m of x is read from row m % x_alias - a cache-resident A
                            // operand: what the GEMM costs when its operand is free (WRONG results; the f-1 lower bound, tools/f1_ab.py)
   // XM = 1 (f-1 A/B): x[m][k] is not read but computed - the RoIAlign gather in the operand loader (taps: roi_tap_table_kernel)
@@ -479,7 +512,7 @@ __global__ __launch_bounds__(128 * WR, WR == 2 ? 2 : 1) void fc_x3_gemm_kernel(F
   float xs = 1.f, out_s0 = 1.f, out_s1 = 1.f;                      // F16: x scale; the two factors that undo the x and W scales
   if constexpr (F16) {
     float ws_, iw;
-    f16_scale_of(*a.xbound, xs, out_s0);
+    f16_scale_of(bound_max(a.xbound, a.xbound_n), xs, out_s0);
     f16_scale_of(*a.wamax, ws_, iw);
     out_s1 = iw;
   }
@@ -636,6 +669,7 @@ __global__ __launch_bounds__(128 * WR, WR == 2 ? 2 : 1) void fc_x3_gemm_kernel(F
 
   const bool direct = a.slices == 1;
   float* dst = direct ? a.out : a.part + (size_t)slice * a.M * a.N;
+  unsigned om = 0;                                                 // direct: the largest |value| stored, as bits (the next layer's bound)
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int n = n0 + wn * 64 + j * 32 + fr;
@@ -649,11 +683,15 @@ __global__ __launch_bounds__(128 * WR, WR == 2 ? 2 : 1) void fc_x3_gemm_kernel(F
         if (m < a.M && n < a.N) {
           float v = acc[i][j][g];
           if constexpr (F16) v = (v * out_s0) * out_s1;            // undo the operand scales (powers of two: exact)
-          if (direct) { v += b; if (a.relu) v = fmaxf(v, 0.f); }
+          if (direct) { v += b; if (a.relu) v = fmaxf(v, 0.f); if constexpr (F16) om = max(om, __float_as_uint(v) & 0x7FFFFFFFu); }
           dst[(size_t)m * a.N + n] = v;
         }
       }
     }
+  }
+  if constexpr (F16) if (direct && a.out_max) {
+    __syncthreads();                                              // every wave is past its last fragment read: the staging image is free
+    block_bound_max(om, a.out_max, lds);
   }
 }
 
@@ -674,7 +712,7 @@ __global__ __launch_bounds__(512, 1) void fc_x3b_gemm_kernel(FcX3Args a) {
   float xs = 1.f, out_s0 = 1.f, out_s1 = 1.f;
   if constexpr (F16) {
     float ws_, iw;
-    f16_scale_of(*a.xbound, xs, out_s0);
+    f16_scale_of(bound_max(a.xbound, a.xbound_n), xs, out_s0);
     f16_scale_of(*a.wamax, ws_, iw);
     out_s1 = iw;
   }
@@ -892,6 +930,7 @@ __global__ __launch_bounds__(512, 1) void fc_x3b_gemm_kernel(FcX3Args a) {
 
   const bool direct = a.slices == 1;
   float* dst = direct ? a.out : a.part + (size_t)slice * a.M * a.N;
+  unsigned om = 0;                                                 // direct: the largest |value| stored, as bits (the next layer's bound)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int n = n0 + wn * 128 + j * 32 + fr;
@@ -905,11 +944,15 @@ __global__ __launch_bounds__(512, 1) void fc_x3b_gemm_kernel(FcX3Args a) {
         if (m < a.M && n < a.N) {
           float v = acc[i][j][g];
           if constexpr (F16) v = (v * out_s0) * out_s1;
-          if (direct) { v += b; if (a.relu) v = fmaxf(v, 0.f); }
+          if (direct) { v += b; if (a.relu) v = fmaxf(v, 0.f); if constexpr (F16) om = max(om, __float_as_uint(v) & 0x7FFFFFFFu); }
           dst[(size_t)m * a.N + n] = v;
         }
       }
     }
+  }
+  if constexpr (F16) if (direct && a.out_max) {
+    __syncthreads();                                              // every wave is past its last fragment read: the staging image is free
+    block_bound_max(om, a.out_max, lds);
   }
 }
 
@@ -1023,7 +1066,7 @@ M3D_API int m3d_linear_forward(const float* d_x, const float* d_weight, const fl
     long long blocks = (MN + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, p.slices,
-                       p.slices_tail, (long long)(p.mt_full < p.mt ? p.mt_full * BM : M) * N, relu);
+                       p.slices_tail, (long long)(p.mt_full < p.mt ? p.mt_full * BM : M) * N, relu, (unsigned*)nullptr);
   }
   return m3d::check_launch("linear_forward");
 }
@@ -1073,7 +1116,7 @@ M3D_API int m3d_linear_bf16x3_forward(const float* d_x, const void* d_packed, co
     const long long MN = (long long)M * N;
     long long blocks = (MN + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu);
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu, (unsigned*)nullptr);
   }
   return m3d::check_launch("linear_bf16x3_forward");
 }
@@ -1132,9 +1175,19 @@ M3D_API size_t m3d_linear_f16x2_workspace_bytes(int M, int N, int K) {
 
 M3D_API int m3d_linear_f16x2_forward(const float* d_x, const void* d_packed, const float* d_bias, float* d_out, int M, int N, int K,
                                      int relu, const float* d_x_bound, void* d_ws, size_t ws_bytes, void* stream) {
+  return m3d_linear_f16x2_forward_bounds(d_x, d_packed, d_bias, d_out, M, N, K, relu, d_x_bound, 1, nullptr, d_ws, ws_bytes, stream);
+}
+
+/* ... with the bounds travelling as slot arrays: d_x_bound holds x_bound_slots floats (the largest is the bound: 1 = an m3d_absmax result,
+ * m3d_conv3d_zw_slots() = what a conv3d_zw launch or this call left), d_out_bound (or NULL) m3d_conv3d_zw_slots() ZEROED floats
+ * that receive max |d_out| from the launch that stores d_out (the split-K reduce, or the GEMM's own epilogue): no sweep of either. */
+M3D_API int m3d_linear_f16x2_forward_bounds(const float* d_x, const void* d_packed, const float* d_bias, float* d_out, int M, int N, int K,
+                                            int relu, const float* d_x_bound, int x_bound_slots, float* d_out_bound, void* d_ws,
+                                            size_t ws_bytes, void* stream) {
   if (M < 0 || N <= 0 || K <= 0) return M3D_EINVAL;
   if (M == 0) return M3D_OK;
   if (!d_x || !d_packed || !d_out || !d_ws) return M3D_EINVAL;
+  if (d_x_bound && (x_bound_slots < 1 || x_bound_slots > 1024)) return M3D_EINVAL;
   if (K % 32 != 0 || ((uintptr_t)d_x & 15) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_ws & 15)) return M3D_EUNSUPPORTED;
   const bool big = f16x2_big_tiles(M, N);
   X3Plan p = x3_plan(M, N, K);
@@ -1146,10 +1199,11 @@ M3D_API int m3d_linear_f16x2_forward(const float* d_x, const void* d_packed, con
   if (!d_x_bound) {                                               // no bound from the producer: sweep x itself
     float* b = reinterpret_cast<float*>(static_cast<char*>(d_ws) + part_bytes);
     if (const int rc = m3d_absmax(d_x, (long long)M * K, b, stream)) return rc;
-    d_x_bound = b;
+    d_x_bound = b; x_bound_slots = 1;
   }
   FcX3Args a{d_x, (const u32x4*)d_packed, d_bias, d_out, (float*)d_ws, M, N, K, p.mt, p.nt, s, K / 32, relu, p.per_xcd};
-  a.xbound = d_x_bound;
+  a.xbound = d_x_bound; a.xbound_n = x_bound_slots;
+  a.out_max = reinterpret_cast<unsigned*>(d_out_bound);
   a.wamax = reinterpret_cast<const float*>(static_cast<const char*>(d_packed) + f16x2_plane_bytes(N, K));
   a.x_alias = 0;
   a.feat = nullptr; a.taps = nullptr; a.roi_batch = nullptr; a.fC = a.fS = a.fH = a.fW = 0;
@@ -1171,7 +1225,8 @@ M3D_API int m3d_linear_f16x2_forward(const float* d_x, const void* d_packed, con
     const long long MN = (long long)M * N;
     long long blocks = (MN + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu);
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu,
+                       reinterpret_cast<unsigned*>(d_out_bound));
   }
   return m3d::check_launch("linear_f16x2_forward");
 }
@@ -1223,7 +1278,7 @@ M3D_API int m3d_linear_bf16x3_roi_forward(const float* d_features, int batch, in
     const long long MN = (long long)M * N;
     long long blocks = (MN + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu);
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu, (unsigned*)nullptr);
   }
   return m3d::check_launch("linear_bf16x3_roi_forward");
 }
@@ -1254,7 +1309,7 @@ M3D_API int m3d_linear_bf16x3_w32_forward(const float* d_x, const float* d_weigh
     const long long MN = (long long)M * N;
     long long blocks = (MN + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu);
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)d_ws, d_bias, d_out, MN, N, s, s, MN, relu, (unsigned*)nullptr);
   }
   return m3d::check_launch("linear_bf16x3_w32_forward");
 }

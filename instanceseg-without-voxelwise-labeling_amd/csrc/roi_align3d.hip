@@ -614,7 +614,7 @@ __global__ __launch_bounds__(256) void roi_align3d_fwd_v3_kernel(const float* __
 template <int KS>
 __global__ __launch_bounds__(256) void roi_align3d_fwd_gemm_kernel(const float* __restrict__ feat, float* __restrict__ out, int B, int C, int S,
                                                                    int H, int W, const int* __restrict__ order, const int* __restrict__ tabs,
-                                                                   const float* __restrict__ feat_absmax) {
+                                                                   const float* __restrict__ feat_absmax, int absmax_slots) {
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -651,7 +651,9 @@ __global__ __launch_bounds__(256) void roi_align3d_fwd_gemm_kernel(const float* 
   }
   __syncthreads();
   float fs, inv_f;
-  m3d::f16_scale_of(*feat_absmax, fs, inv_f);
+  float fmax = feat_absmax[0];                                     // the bound: the largest of its slots (one: an m3d_absmax result)
+  for (int i = 1; i < absmax_slots; ++i) fmax = fmaxf(fmax, feat_absmax[i]);
+  m3d::f16_scale_of(fmax, fs, inv_f);
   constexpr float kMs = 16384.f, kInvMs = 1.f / 16384.f;     // operator scale 2^14: an axis weight is <= 2 (two samples on one voxel), the
                                                              // y row carries 1 / 8: M <= 2 * 2 * 0.25 = 1 -> <= 2^14 in fp16
   const float* fbase = feat + (size_t)g.batch * C * S * HW + (size_t)sh.rng[0] * HW + sh.rng[2] * W + sh.rng[4];
@@ -1012,7 +1014,7 @@ __global__ __launch_bounds__(64) void roi_tap_table_kernel(const float* __restri
 
 int launch(int mode /*0 fast fwd, 1 exact fwd, 2 backward*/, int AS, int AH, int AW, float scale, int ratio, const float* a, const float* rois, float* o, int B,
            int C, int S, int H, int W, int R, int roi_cols, void* stream, void* ws = nullptr, size_t ws_bytes = 0,
-           const float* feat_absmax = nullptr) {
+           const float* feat_absmax = nullptr, int absmax_slots = 1) {
   if (roi_cols != 7) return M3D_EINVAL;   // roi_align_cuda_3d.c:19-22
   if (R < 0 || B <= 0 || C <= 0 || S <= 0 || H <= 0 || W <= 0 || AS <= 0 || AH <= 0 || AW <= 0) return M3D_EINVAL;
   if (R == 0) return M3D_OK;
@@ -1047,9 +1049,9 @@ int launch(int mode /*0 fast fwd, 1 exact fwd, 2 backward*/, int AS, int AH, int
       hipLaunchKernelGGL(roi_class_kernel, dim3(R), block, 0, m3d::as_stream(stream), rois, o, B, C, S, H, W, scale, R, order, tabs, gemm);
       if (gemm) {
         hipLaunchKernelGGL(roi_align3d_fwd_gemm_kernel<4>, dim3(R), block, 0, m3d::as_stream(stream), a, o, B, C, S, H, W, (const int*)order,
-                           (const int*)tabs, feat_absmax);
+                           (const int*)tabs, feat_absmax, absmax_slots);
         hipLaunchKernelGGL(roi_align3d_fwd_gemm_kernel<8>, dim3(R), block, 0, m3d::as_stream(stream), a, o, B, C, S, H, W, (const int*)order,
-                           (const int*)tabs, feat_absmax);
+                           (const int*)tabs, feat_absmax, absmax_slots);
       }
       // option tune_roi_xcd = 1 (tuning build; A/B and the PMC passes of profiles/r06_roi_xcd_ab.txt): the XCD-aware channel split
       // described in the kernel.  It removes the sub-volume reads' L2 misses and leaves the time where it was (0.237 vs 0.225 ms at
@@ -1107,6 +1109,17 @@ M3D_API int m3d_roi_align3d_forward_ws2(int AS, int AH, int AW, float spatial_sc
                                         const float* d_feat_absmax, void* stream) {
   return launch(0, AS, AH, AW, spatial_scale, sampling_ratio, d_features, d_rois, d_output, batch, channels, slices, height,
                 width, num_rois, roi_cols, stream, d_ws, ws_bytes, d_feat_absmax);
+}
+
+/* ... with the bound as feat_absmax_slots floats whose largest is >= max |d_features|: the slot array the conv that produced the feature
+ * maps left (m3d_conv3d_zw_forward's d_out_max) instead of a sweep of them.  1 slot: _ws2. */
+M3D_API int m3d_roi_align3d_forward_ws3(int AS, int AH, int AW, float spatial_scale, int sampling_ratio, const float* d_features,
+                                        int batch, int channels, int slices, int height, int width, const float* d_rois,
+                                        int num_rois, int roi_cols, float* d_output, void* d_ws, size_t ws_bytes,
+                                        const float* d_feat_absmax, int feat_absmax_slots, void* stream) {
+  if (d_feat_absmax && (feat_absmax_slots < 1 || feat_absmax_slots > 1024)) return M3D_EINVAL;
+  return launch(0, AS, AH, AW, spatial_scale, sampling_ratio, d_features, d_rois, d_output, batch, channels, slices, height,
+                width, num_rois, roi_cols, stream, d_ws, ws_bytes, d_feat_absmax, feat_absmax_slots);
 }
 
 M3D_API int m3d_roi_align3d_backward(int AS, int AH, int AW, float spatial_scale, int sampling_ratio, const float* d_top_grad,

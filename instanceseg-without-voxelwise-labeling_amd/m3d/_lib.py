@@ -11,11 +11,12 @@ _lib = None
 SYMBOLS = [
     "m3d_version", "m3d_error_string", "m3d_last_hip_error", "m3d_set_option", "m3d_get_option", "m3d_tuning_build",
     "m3d_conv3d_stem5_prepare_dgrad_weights", "m3d_conv3d_stem5_dgrad", "m3d_norm1_workspace_bytes", "m3d_norm1", "m3d_norm1_batched",
-    "m3d_linear_workspace_bytes", "m3d_linear_forward", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_pack", "m3d_absmax", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_pack", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_f16x2_forward",
+    "m3d_linear_workspace_bytes", "m3d_linear_forward", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_pack", "m3d_absmax", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_pack", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_f16x2_forward", "m3d_linear_f16x2_forward_bounds",
+    "m3d_box_head_workspace_bytes", "m3d_box_head_forward",
     "m3d_linear_bf16x3_workspace_bytes", "m3d_linear_bf16x3_forward", "m3d_mask_paste3d_workspace_bytes", "m3d_mask_paste3d", "m3d_linear_bf16x3_w32_workspace_bytes", "m3d_linear_bf16x3_w32_forward", "m3d_roi_align3d_tap_tables", "m3d_linear_bf16x3_roi_workspace_bytes", "m3d_linear_bf16x3_roi_forward",
     "m3d_fused_max_boxes", "m3d_compact_rows", "m3d_compact_rows2", "m3d_box_head_outputs", "m3d_conv3d_forward_split_sigmoid", "m3d_generate_proposals3d_batched_workspace_bytes", "m3d_generate_proposals3d_batched",
     "m3d_box_results3d_batched_workspace_bytes", "m3d_box_results3d_batched", "m3d_nms3d_batched_workspace_bytes", "m3d_nms3d_batched",
-    "m3d_roi_align3d_forward", "m3d_roi_align3d_forward_exact", "m3d_roi_align3d_backward", "m3d_roi_align3d_workspace_bytes", "m3d_roi_align3d_forward_ws", "m3d_roi_align3d_forward_ws2",
+    "m3d_roi_align3d_forward", "m3d_roi_align3d_forward_exact", "m3d_roi_align3d_backward", "m3d_roi_align3d_workspace_bytes", "m3d_roi_align3d_forward_ws", "m3d_roi_align3d_forward_ws2", "m3d_roi_align3d_forward_ws3",
     "m3d_nms3d_workspace_bytes", "m3d_nms3d", "m3d_bbox_overlaps3d", "m3d_bbox_transform3d",
     "m3d_generate_proposals3d_workspace_bytes", "m3d_generate_proposals3d",
     "m3d_conv3d_packed_weight_bytes", "m3d_conv3d_pack_weights", "m3d_conv3d_forward", "m3d_conv3d_forward_dilated", "m3d_conv3d_forward_windowed", "m3d_conv3d_forward_pool2", "m3d_conv3d_direct_plan", "m3d_conv3d_direct_plan_count",
@@ -41,6 +42,19 @@ SYMBOLS = [
 class SgdTensor(C.Structure):
     """m3d_sgd_tensor of include/m3d.h: one parameter of an m3d_sgd_step call"""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("n", C.c_longlong), ("lr", C.c_float), ("wd", C.c_float)]
+
+
+class BoxHead(C.Structure):
+    """m3d_box_head of include/m3d.h: the description m3d_box_head_forward takes"""
+    _fields_ = [("fc1_packed", C.c_void_p), ("fc1_bias", C.c_void_p), ("fc2_packed", C.c_void_p), ("fc2_bias", C.c_void_p),
+                ("outs_weight", C.c_void_p), ("outs_bias", C.c_void_p),
+                ("channels", C.c_int), ("roi_res", C.c_int), ("sampling_ratio", C.c_int), ("fc1_out", C.c_int), ("fc2_out", C.c_int),
+                ("num_classes", C.c_int), ("spatial_scale", C.c_float), ("weights", C.c_double * 6), ("xform_clip", C.c_double),
+                ("features", C.c_void_p), ("batch", C.c_int), ("slices", C.c_int), ("height", C.c_int), ("width", C.c_int),
+                ("rois", C.c_void_p), ("num_rois", C.c_int), ("clip", C.c_double * 3),
+                ("feat_bound", C.c_void_p), ("feat_bound_slots", C.c_int), ("fc1_bound", C.c_void_p),
+                ("x", C.c_void_p), ("h1", C.c_void_p), ("h2", C.c_void_p), ("outs", C.c_void_p), ("cls", C.c_void_p),
+                ("bbox", C.c_void_p), ("pred", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
 class M3DError(RuntimeError):
@@ -71,7 +85,8 @@ def _load(path):
               "m3d_box_results3d_batched_workspace_bytes", "m3d_nms3d_batched_workspace_bytes", "m3d_otsu2d_workspace_bytes",
               "m3d_cc_workspace_bytes", "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_stem_wino_packed_weight_bytes",
               "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
-              "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes"):
+              "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes",
+              "m3d_box_head_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -10,6 +10,7 @@ The state-dict key layout is the reference's: Conv_Body.conv1a.weight
 Every op, the linear layers included (split-K fp32 MFMA GEMM, csrc/fc_gemm.hip), is a libm3d.so kernel; torch supplies
 device memory, streams and a few elementwise helpers (sigmoid, softmax, cat).
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -133,13 +134,17 @@ class DetectorM3D:
         return self.convs[li](x, self._bound, bound_slot)
 
     @staticmethod
+    def _carried_bound(x):
+        """The slot array the launch that produced x left on it (its largest entry = max |x|), or None (also after an in-place write)."""
+        b = getattr(x, "_m3d_bound", None)
+        return b[0] if b is not None and b[1] == x._version else None
+
+    @staticmethod
     def _bound(x):
         """The operand bound of an activation tensor for the f16x2 conv kernels: left on the tensor by the launch that produced it, else
         one sweep of it (the chain's first layer, or a tensor that came from somewhere else)."""
-        b = getattr(x, "_m3d_bound", None)
-        if b is not None and b[1] == x._version:           # (an in-place write since the producing launch makes the bound stale: sweep again)
-            return b[0]
-        return ops.ZwConv3d.bound_of(x)
+        b = DetectorM3D._carried_bound(x)
+        return b if b is not None else ops.ZwConv3d.bound_of(x)
 
     def span(self, name):
         return self.probe(name) if self.probe is not None else _NOSPAN
@@ -180,11 +185,14 @@ class DetectorM3D:
 
     def conv_body(self, x, first=0, last=None):
         names = dsn_layers(self.cfg.stride)
-        # the f16x2 layers' operand bounds (one zeroed slot array per layer, filled by the producing launch): ONE fill for the whole body
-        slots = torch.zeros((len(self.body), ops.ZwConv3d.SLOTS), dtype=torch.float32, device=x.device) if self.conv_f16 else None
+        # the f16x2 layers' operand bounds (one zeroed slot array per layer, filled by the producing launch): ONE fill for the whole body,
+        # and in it one more row for the box head (fc1's storing launch -> fc2's operand bound), which travels with the feature maps
+        slots = torch.zeros((len(self.body) + 1, ops.ZwConv3d.SLOTS), dtype=torch.float32, device=x.device) if self.conv_f16 else None
         for li in range(first, len(self.body) if last is None else last):
             with self.span(names[li][0]):
                 x = self.body_layer(li, x, slots[li] if slots is not None else None)
+        if slots is not None:
+            x._m3d_head_bound = slots[len(self.body)]
         return x
 
     def capture_body(self, x, first=0, last=None):
@@ -234,27 +242,117 @@ class DetectorM3D:
         """RoIAlign3D -> fc1 -> fc2 -> (cls_score | bbox_pred as one GEMM) -> softmax / deltas / decoded + clipped boxes in one launch:
         (cls [R,nc], bbox [R,6nc], pred_boxes [R,6nc]).  rois [R,7]."""
         c, P = self.cfg, self.P
+        if self.probe is None and self._one_call_ok(feat, rois, int(rois.shape[0])):
+            return self._box_head_call(feat, rois, int(rois.shape[0]), clip_to)
+        f16 = [isinstance(self.fc_split.get(n), ops.SplitLinearF16) for n in ("fc1", "fc2")]
+        # fc1 -> fc2: a zeroed slot array (conv_body's one fill) that fc1's storing launch fills with max |fc1 output|; used once
+        hb = feat.__dict__.pop("_m3d_head_bound", None) if all(f16) and rois.shape[0] > 32 else None
         with self.span("roi_align3d"):
-            # the feature maps' largest magnitude (16 MB sweep, once): the operand scale of the f16x2 kernels - RoIAlign3D's matrix-core form
-            # for small sub-volumes and, since every RoIAlign value is a convex combination of feature-map values, fc1's x scale
-            fmax = ops.absmax(feat) if self.roi_gemm or any(isinstance(v, ops.SplitLinearF16) for v in self.fc_split.values()) else None
+            # the feature maps' largest magnitude: the operand scale of the f16x2 kernels - RoIAlign3D's matrix-core form for small
+            # sub-volumes and, since every RoIAlign value is a convex combination of feature-map values, fc1's x scale.  The conv that
+            # produced the maps left it in its bound slots; maps from elsewhere (PRM, a caller's tensor) are swept (16 MB, once)
+            fmax = None
+            if f16[0] or self.roi_gemm:
+                fmax = self._carried_bound(feat)
+                if fmax is None:
+                    fmax = ops.absmax(feat)
             x = ops.roi_align3d_forward(feat, rois, c.roi_res, c.roi_res, c.roi_res, 1.0 / c.stride, c.sampling_ratio,
                                         feat_absmax=fmax if self.roi_gemm else None)
-        x = x.view(x.shape[0], -1)
+        x = x.flatten(1)                                                                            # (also of no rows)
         for name in ("fc1", "fc2"):                                                                 # :114-115
             with self.span(name):
                 if name in self.fc_split:
                     lin = self.fc_split[name]
                     if isinstance(lin, ops.SplitLinearF16):
-                        # fc1's operand scale from the feature map (16 MB) instead of the RoIAlign output (440 MB): every RoIAlign value is a
-                        # convex combination of feature-map values; fc2's input is small and swept by the call itself
-                        x = lin(x, relu=True, x_bound=fmax if name == "fc1" else None)
+                        # fc1's operand scale from the feature map instead of the RoIAlign output (440 MB): every RoIAlign value is a
+                        # convex combination of feature-map values; fc2's from fc1's storing launch (without it: swept by the call itself)
+                        x = lin(x, relu=True, x_bound=fmax, out_bound=hb) if name == "fc1" else lin(x, relu=True, x_bound=hb)
                     else:
                         x = lin(x, relu=True)
                 else:
                     x = ops.linear(x, P["Box_Head.%s.weight" % name], P["Box_Head.%s.bias" % name], relu=True)
         o = ops.linear(x, self.outs_w, self.outs_b)              # cls_score and bbox_pred share their input: one GEMM (:42,45)
         return ops.box_head_outputs(o, rois, c.num_classes, c.bbox_reg_weights, clip_to=clip_to)   # :43-44 (eval) + core/test.py:250-251
+
+    # ---- the same chain as ONE library call (m3d_box_head_forward): the bare path of a detection step.  Between the host read of the
+    # proposal counts and the first launch behind it the GPU is idle, so everything that does not need the counts is done before the
+    # read (head_prepare, from detect_batch_begin) and every intermediate buffer is kept, grow-only, per detector and stream.
+    def _one_call_ok(self, feat, rois, R):
+        return (R > 32 and not self.roi_gemm and all(isinstance(self.fc_split.get(n), ops.SplitLinearF16) for n in ("fc1", "fc2"))
+                and feat.is_cuda and feat.dtype == torch.float32 and feat.is_contiguous()
+                and rois.dtype == torch.float32 and rois.is_contiguous() and rois.dim() == 2 and rois.shape[1] == 7)
+
+    def head_prepare(self, feat, rois_buf, clip_to=None):
+        """The m3d_box_head description of one call, all but the row count and the buffers: (description, tensors it points to)."""
+        c = self.cfg
+        tmpl = self.__dict__.get("_head_tmpl")
+        if tmpl is None:
+            fc1, fc2 = self.fc_split["fc1"], self.fc_split["fc2"]
+            tmpl = ops.BoxHead(fc1_packed=fc1.packed.data_ptr(), fc1_bias=fc1.bias.data_ptr(), fc2_packed=fc2.packed.data_ptr(),
+                               fc2_bias=fc2.bias.data_ptr(), outs_weight=self.outs_w.data_ptr(), outs_bias=self.outs_b.data_ptr(),
+                               channels=fc1.K // c.roi_res ** 3, roi_res=c.roi_res, sampling_ratio=c.sampling_ratio, fc1_out=fc1.N,
+                               fc2_out=fc2.N, num_classes=c.num_classes, spatial_scale=1.0 / c.stride,
+                               weights=(C.c_double * 6)(*[float(v) for v in c.bbox_reg_weights]), xform_clip=ops.BBOX_XFORM_CLIP)
+            self._head_tmpl = tmpl
+        d = ops.BoxHead.from_buffer_copy(tmpl)
+        B, Cc, S, H, W = feat.shape
+        assert Cc == d.channels and self.fc_split["fc2"].K == d.fc1_out and self.outs_w.shape[1] == d.fc2_out
+        fb = self._carried_bound(feat)
+        hb = feat.__dict__.pop("_m3d_head_bound", None)
+        d.features, d.batch, d.slices, d.height, d.width, d.rois = feat.data_ptr(), B, S, H, W, rois_buf.data_ptr()
+        if fb is not None:
+            d.feat_bound, d.feat_bound_slots = fb.data_ptr(), fb.numel()
+        if hb is not None:
+            d.fc1_bound = hb.data_ptr()
+        if clip_to is not None:
+            d.clip = (C.c_double * 3)(*[float(v) for v in clip_to])
+        return d, (feat, rois_buf, fb, hb)
+
+    def _head_buffers(self, d, R, device):
+        """x, fc1 / fc2 outputs, the merged cls | bbox scores and the workspace of the stream's box head, for at least R rows"""
+        pool = self.__dict__.setdefault("_head_bufs", {})
+        key = torch.cuda.current_stream().cuda_stream
+        b = pool.get(key)
+        if b is None or b["rows"] < R:
+            rows = (R + 255) // 256 * 256
+            wsb = int(ops.lib().m3d_box_head_workspace_bytes(C.byref(d), rows))
+            if wsb == 0:
+                raise ops.M3DError("m3d_box_head_workspace_bytes: the library does not take this box head")
+            k1 = d.channels * d.roi_res ** 3
+            pool[key] = b = None                                                     # (the old buffers go first)
+            b = pool[key] = dict(rows=rows, wsb=wsb, ws=torch.empty((wsb,), dtype=torch.uint8, device=device),
+                                 **{n: torch.empty((rows, w), dtype=torch.float32, device=device)
+                                    for n, w in (("x", k1), ("h1", d.fc1_out), ("h2", d.fc2_out), ("outs", 7 * d.num_classes))})
+            b["ptrs"] = tuple(b[n].data_ptr() for n in ("x", "h1", "h2", "outs", "ws"))
+        return b
+
+    def _head_stage(self, prepared, device, rows=1):
+        """Everything of a call but the row count, so that it can be done BEFORE the host read: the stream's buffers (for at least `rows`
+        rows) and the result tensor (cls | bbox | pred of as many rows as the buffers hold, each on a 256-byte boundary; the caller's to keep)."""
+        d, keep = prepared
+        b = self._head_buffers(d, rows, device)
+        cap, nc = b["rows"], d.num_classes
+        ob = (cap * nc + 63) // 64 * 64
+        op = ob + (cap * 6 * nc + 63) // 64 * 64
+        res = torch.empty((op + cap * 6 * nc,), dtype=torch.float32, device=device)
+        p = res.data_ptr()
+        d.cls, d.bbox, d.pred = p, p + 4 * ob, p + 4 * op
+        d.x, d.h1, d.h2, d.outs, d.ws = b["ptrs"]
+        d.ws_bytes = b["wsb"]
+        return d, keep, res, cap, ob, op, ops._stream()
+
+    @staticmethod
+    def _head_launch(staged, R):
+        """m3d_box_head_forward on the first R rows: (cls, bbox, pred_boxes), bit-equal to the per-layer path's"""
+        d, _, res, cap, ob, op, stream = staged
+        assert R <= cap
+        d.num_rois = R
+        ops.check(ops.lib().m3d_box_head_forward(C.byref(d), stream), "box_head_forward")
+        nc = d.num_classes
+        return res[:R * nc].view(R, nc), res[ob:ob + R * 6 * nc].view(R, 6 * nc), res[op:op + R * 6 * nc].view(R, 6 * nc)
+
+    def _box_head_call(self, feat, rois_buf, R, clip_to=None):
+        return self._head_launch(self._head_stage(self.head_prepare(feat, rois_buf, clip_to), feat.device, R), R)
 
     def box_head(self, feat, rois):
         cls, bbox, _ = self.box_head_outputs(feat, rois)
@@ -332,6 +430,8 @@ class DetectorM3D:
                 st["rois_packed"], st["kidx_packed"], st["offs_dev"] = ops.compact_rows2(st["props"][0], st["props"][2], num, st["num_host"])
                 st["ready"] = torch.cuda.Event()
                 st["ready"].record()
+                if self.has_head and self.probe is None and self._one_call_ok(feat, st["rois_packed"], 33):
+                    st["head"] = self.head_prepare(feat, st["rois_packed"], im_info[:3])    # all but the row count: before the read
                 # finish() may run on another stream: it orders its readers of the packed buffers behind this event with a device-side
                 # wait as well (the host wait on it covers the same-thread case)
                 st["packed_ready"] = st["ready"]
@@ -360,14 +460,21 @@ class DetectorM3D:
         if not st["fused"]:
             return self._detect_batch_unfused(feat, prob, deltas, im_info, as_dicts)
         rois_b, probs_b, kidx_b, num = st["props"]
+        torch.cuda.current_stream().wait_event(st["packed_ready"])                 # device-side: compact_rows -> RoIAlign / box results
+        # the bare path: buffers, result tensor and every argument but the row count are ready before the host waits
+        staged = self._head_stage(st.pop("head"), feat.device) if self.probe is None and "head" in st else None
         st["ready"].synchronize()                                                  # host read 1: sizes the GEMM rows
         counts = st["num_host"].tolist()
         total = sum(counts)
         # the GPU is idle from here until the first launch below: nothing but that launch's arguments is prepared first, the rest of
         # the bookkeeping (stream marks, dictionaries, host-side offsets) follows behind the box head's launches
         head = self.has_head and total > 0
-        torch.cuda.current_stream().wait_event(st["packed_ready"])                 # device-side: compact_rows -> RoIAlign / box results
-        if head:
+        if head and total > 32 and staged is not None:
+            if total > staged[3]:                                                   # more rows than ever before on this stream: grow (rare)
+                staged = self._head_stage(staged[:2], feat.device, total)
+            cls, bbox, pred = self._head_launch(staged, total)                      # ONE library call queues the whole box head
+            kidx = st["kidx_packed"][:total]
+        elif head:
             rois, kidx = st["rois_packed"][:total], st["kidx_packed"][:total]       # (were two torch.cat launches behind the host read)
             cls, bbox, pred = self.box_head_outputs(feat, rois, clip_to=im_info[:3])   # one RoIAlign + one GEMM chain for all tiles
         self._release_counts(st.pop("num_host"))                                   # read: back to the pool

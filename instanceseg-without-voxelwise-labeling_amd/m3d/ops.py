@@ -7,7 +7,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import lib, check, M3DError, SgdTensor
+from ._lib import lib, check, M3DError, SgdTensor, BoxHead
 
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
@@ -51,8 +51,9 @@ def _claim(out):
 def roi_align3d_forward(features, rois, AS, AH, AW, spatial_scale, sampling_ratio, exact=False, ordered=True, feat_absmax=None):
     """exact=True: the reference kernel's fp32 operation order (bit-identical to the oracle); default: the
     separable fast form (same samples and weights, different summation order).  ordered=False: RoIs launched in index order (A/B).
-    feat_absmax (round 6; a 1-element device tensor >= max |features|, ops.absmax): RoIs with sub-volumes of <= 128 voxels run as one GEMM
-    per RoI on the f16 matrix cores (m3d_roi_align3d_forward_ws2); None keeps every RoI on the separable kernels."""
+    feat_absmax (round 6; device floats whose largest is >= max |features|: ops.absmax, or the slot array the producing conv left): RoIs
+    with sub-volumes of <= 128 voxels run as one GEMM per RoI on the f16 matrix cores (m3d_roi_align3d_forward_ws3); None keeps every RoI
+    on the separable kernels."""
     _need_gpu(features, rois)
     features, rois = _f32c(features), _f32c(rois)
     B, Cc, S, H, W = features.shape
@@ -69,9 +70,9 @@ def roi_align3d_forward(features, rois, AS, AH, AW, spatial_scale, sampling_rati
     ws = torch.empty((max(wsb, 4),), dtype=torch.uint8, device=features.device) if ordered else None
     if feat_absmax is not None and ordered:
         _need_gpu(feat_absmax)
-        check(lib().m3d_roi_align3d_forward_ws2(int(AS), int(AH), int(AW), C.c_float(spatial_scale), int(sampling_ratio), _ptr(features), B, Cc, S, H, W,
-                                                _ptr(rois), R, cols, _ptr(out), _ptr(ws), C.c_size_t(wsb), _ptr(feat_absmax), _stream()),
-              "roi_align3d_forward")
+        check(lib().m3d_roi_align3d_forward_ws3(int(AS), int(AH), int(AW), C.c_float(spatial_scale), int(sampling_ratio), _ptr(features), B, Cc, S, H, W,
+                                                _ptr(rois), R, cols, _ptr(out), _ptr(ws), C.c_size_t(wsb), _ptr(feat_absmax),
+                                                int(feat_absmax.numel()), _stream()), "roi_align3d_forward")
         return out
     check(lib().m3d_roi_align3d_forward_ws(int(AS), int(AH), int(AW), C.c_float(spatial_scale), int(sampling_ratio), _ptr(features), B, Cc, S, H, W,
                                            _ptr(rois), R, cols, _ptr(out), _ptr(ws), C.c_size_t(wsb), _stream()), "roi_align3d_forward")
@@ -646,8 +647,10 @@ def absmax(x):
 class SplitLinearF16:
     """nn.Linear on the f16 matrix cores at fp32 accuracy with THREE products per fp32 product (csrc/fc_gemm.hip, "f16x2 split": both
     operands scaled by a power of two and cut into two fp16 numbers, 22 bits; the dropped terms are below the rounding of the fp32
-    accumulation).  Weights cut once (4 bytes per element).  __call__(x, relu, out, x_bound): x_bound = a 1-element device tensor
-    >= max|x| (e.g. ops.absmax of the feature map the RoIAlign read); None: the library sweeps x itself."""
+    accumulation).  Weights cut once (4 bytes per element).  __call__(x, relu, out, x_bound, out_bound): x_bound = device floats whose
+    largest is >= max|x| - one (ops.absmax of x, or of the feature map the RoIAlign read) or a slot array (ZwConv3d.SLOTS: what the conv
+    that produced the feature map, or an earlier call's out_bound, left); None: the library sweeps x itself.  out_bound: a ZEROED
+    [ZwConv3d.SLOTS] tensor that receives max|out| from the launch that stores `out` (the next layer's x_bound: no sweep of `out`)."""
 
     @staticmethod
     def supported(weight):
@@ -665,7 +668,7 @@ class SplitLinearF16:
         self.bias = None if bias is None else _f32c(bias)
         self.weight = weight
 
-    def __call__(self, x, relu=False, out=None, x_bound=None):
+    def __call__(self, x, relu=False, out=None, x_bound=None, out_bound=None):
         _need_gpu(x)
         x = _f32c(x)
         M, K = x.shape
@@ -676,15 +679,19 @@ class SplitLinearF16:
             out = torch.empty((M, self.N), dtype=torch.float32, device=x.device)
         if M == 0:
             return out
-        if M <= 32:                                       # a handful of rows: the fp32-input kernel's ragged-tile path
+        if M <= 32:                                       # a handful of rows: the fp32-input kernel's ragged-tile path (out_bound stays zero)
             return linear(x, self.weight, self.bias, relu=relu, out=out)
         if x_bound is not None:
             _need_gpu(x_bound)
-            assert x_bound.dtype == torch.float32 and x_bound.numel() == 1
+            assert x_bound.dtype == torch.float32 and x_bound.numel() in (1, ZwConv3d.SLOTS) and x_bound.is_contiguous()
+        if out_bound is not None:
+            _need_gpu(out_bound)
+            assert out_bound.dtype == torch.float32 and out_bound.numel() == ZwConv3d.SLOTS and out_bound.is_contiguous()
         wsb = lib().m3d_linear_f16x2_workspace_bytes(M, self.N, K)
         ws = torch.empty((wsb // 4,), dtype=torch.float32, device=x.device)
-        check(lib().m3d_linear_f16x2_forward(_ptr(x), _ptr(self.packed), _ptr(self.bias), _ptr(out), M, self.N, K, int(bool(relu)),
-                                             _ptr(x_bound), _ptr(ws), C.c_size_t(wsb), _stream()), "linear_f16x2_forward")
+        check(lib().m3d_linear_f16x2_forward_bounds(_ptr(x), _ptr(self.packed), _ptr(self.bias), _ptr(out), M, self.N, K, int(bool(relu)),
+                                                    _ptr(x_bound), 0 if x_bound is None else int(x_bound.numel()), _ptr(out_bound),
+                                                    _ptr(ws), C.c_size_t(wsb), _stream()), "linear_f16x2_forward")
         return out
 
 
