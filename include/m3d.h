@@ -488,6 +488,10 @@ int m3d_norm1(const void* d_in, int in_dtype, int64_t n, int f32_arith, float* d
  * d_stats [batch,3] or null; d_ws: batch * m3d_norm1_workspace_bytes() */
 int m3d_norm1_batched(const void* d_in, int in_dtype, int batch, int64_t n, int f32_arith, float* d_out, double* d_stats, void* d_ws,
                       size_t ws_bytes, void* stream);
+/* The statistics alone: the same two passes and a finish that writes mean, std, count to d_stats [batch,3] (required); no normalised
+ * volume is written.  The same partials summed in the same order: the same bits as d_stats of m3d_norm1 / m3d_norm1_batched.
+ * d_ws: batch * m3d_norm1_workspace_bytes(). */
+int m3d_norm1_stats(const void* d_in, int in_dtype, int batch, int64_t n, double* d_stats, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Peak-response back-propagation on cropped windows (all kept peaks of a tile as one batch).  Replaces the
@@ -1037,6 +1041,41 @@ typedef struct { float* p; const float* g; float* m; long long n; float lr; floa
 int m3d_sgd_chunk(void);
 int m3d_sgd_step(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, double* d_stats, void* d_ws, size_t* ws_bytes,
                  void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Training samples (train_sample.hip; DESIGN, "Training samples"): the minibatch of lib/roi_data/minibatch.py built on the device from
+ * volumes that stay resident there - prep_im_for_blob(..., 'train') and crop_data_3d of lib/utils/blob.py:97-202.
+ * `images` is a HOST array of `count` descriptors (they travel as kernel arguments): the device volume [depth,height,width] (dtype 0 =
+ * uint16, 1 = float32), the device pointer to its mean, std, count (m3d_norm1_stats), its device boxes fp32 [num_boxes,6]
+ * (x1,y1,z1,x2,y2,z2) and start_max (x, y, z) = min(floor(min over boxes of the lower coordinate), dim - in_size) of blob.py:106-114.
+ * in_size: host (slices, height, width) of the crop.  seeds: host, one per image.  fixed_origin: NULL, or host [count,3] (x, y, z).
+ * Search (one workgroup per image; need_crop != 0, no fixed_origin): per axis a (0 = x, 1 = y, 2 = z) the start is 0 where start_max[a]
+ * == 0, else (key(a) * (start_max[a] + 1)) >> 32 with key(a) = mix_key(seed_stream(seed), a) of the sampling contract; the candidates of
+ * an axis are range(start, dim - size, size / 2) followed by dim - size; candidates are numbered z outer, y, x inner.  A candidate's score
+ * is the sum, in box order and in fp64, of ((x2 - x1) + 1)((y2 - y1) + 1)((z2 - z1) + 1) over the boxes that stay non-degenerate (no
+ * lower coordinate equal to its upper one) after the fp32 shift and clip min(max(b - o, 0), size - 1); the differences are taken in fp64
+ * from the fp32 coordinates.  The first strict maximum wins; no candidate above 0: status 1 and candidate 0.  The reference sums the
+ * volumes in fp32: the same choice while all coordinates are integers and the sum stays below 2^24.  With fixed_origin the one candidate
+ * is that origin.  need_crop == 0: origin 0, boxes pass through unshifted and unfiltered, 0 candidates, score 0.
+ * Outputs (device): d_data fp32 [count, in_size] = ((float)x - (float)mean) / (float)std at every voxel of the crop, the arithmetic of
+ * m3d_norm1 with f32_arith = 1, in 16-byte stores wherever a row of the output allows them; d_boxes fp32 [count,max_boxes,6] the kept
+ * boxes shifted and clipped, in order, rows beyond the count 0; d_keep int32 [count,max_boxes] their source indices ascending, -1
+ * beyond; d_info int32 [count,8] = ox, oy, oz, kept, status, candidates, 0, 0; d_score fp64 [count] the winner's volume.
+ * Two launches, no host synchronisation, allocation or copy; integer and value-ordered selection only: bit-identical run to run.
+ * Workspace: the convention of m3d_sgd_step (the call needs 0 bytes; d_ws and ws_bytes may be NULL).
+ * Limits, checked before any device pointer is followed or anything is launched.  M3D_EINVAL: a NULL or misaligned pointer, count < 0,
+ * an in_size entry < 2, a dim < in_size, start_max < 0 or > dim - size, fixed_origin outside [0, dim - size], need_crop == 0 with dims
+ * != in_size, num_boxes < 1, another dtype.  M3D_EUNSUPPORTED: count > 64, num_boxes > 2048, max_boxes < num_boxes, 2^31 candidates or
+ * more.  count == 0 does nothing.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* vol; const double* stats; const float* boxes;
+  int dtype, depth, height, width, num_boxes;
+  int start_max[3];
+} m3d_train_image;
+int m3d_train_sample(const m3d_train_image* images, int count, const int* in_size, int need_crop, const uint64_t* seeds,
+                     const int* fixed_origin, int max_boxes, float* d_data, float* d_boxes, int32_t* d_keep, int32_t* d_info,
+                     double* d_score, void* d_ws, size_t* ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

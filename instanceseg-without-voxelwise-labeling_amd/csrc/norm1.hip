@@ -138,6 +138,25 @@ __global__ __launch_bounds__(256) void norm1_apply_kernel(const T* __restrict__ 
   if (const long long e = end_element<V>(sp, n); e < n) out[e] = one(in[e]);
 }
 
+// the statistics alone: the reductions of norm1_apply_kernel, in its order
+__global__ __launch_bounds__(256) void norm1_stats_kernel(const double* __restrict__ ws, double* __restrict__ stats) {
+  __shared__ double sm[4];
+  ws += (size_t)blockIdx.y * 3 * kBlocks; stats += 3 * blockIdx.y;
+  const double cnt = reduce_partials(ws + kBlocks, sm);
+  const double mean = reduce_partials(ws, sm) / cnt;
+  const double sd = sqrt(reduce_partials(ws + 2 * kBlocks, sm) / cnt);
+  if (threadIdx.x == 0) { stats[0] = mean; stats[1] = sd; stats[2] = cnt; }
+}
+
+template <typename T>
+int run_stats(const T* in, int batch, long long n, double* ws, double* stats, hipStream_t st) {
+  if ((uintptr_t)in % sizeof(T)) return M3D_EINVAL;
+  hipLaunchKernelGGL(norm1_sum_kernel<T>, dim3(kBlocks, batch), dim3(256), 0, st, in, n, ws);
+  hipLaunchKernelGGL(norm1_var_kernel<T>, dim3(kBlocks, batch), dim3(256), 0, st, in, n, ws);
+  hipLaunchKernelGGL(norm1_stats_kernel, dim3(1, batch), dim3(256), 0, st, (const double*)ws, stats);
+  return m3d::check_launch("norm1_stats");
+}
+
 template <typename T>
 int run(const T* in, int batch, long long n, int f32_arith, float* out, double* ws, double* stats, hipStream_t st) {
   if (((uintptr_t)in % sizeof(T)) || ((uintptr_t)out % sizeof(float))) return M3D_EINVAL;     // element-aligned bases (any torch tensor is)
@@ -173,5 +192,16 @@ M3D_API int m3d_norm1_batched(const void* d_in, int in_dtype, int batch, int64_t
   hipStream_t st = m3d::as_stream(stream);
   if (in_dtype == 0) return run((const uint16_t*)d_in, batch, (long long)n, f32_arith, d_out, (double*)d_ws, d_stats, st);
   if (in_dtype == 1) return run((const float*)d_in, batch, (long long)n, f32_arith, d_out, (double*)d_ws, d_stats, st);
+  return M3D_EINVAL;
+}
+
+/* the statistics of `batch` volumes without the normalised output: d_stats [batch, 3] = mean, std, count, the bits m3d_norm1_batched writes */
+M3D_API int m3d_norm1_stats(const void* d_in, int in_dtype, int batch, int64_t n, double* d_stats, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_in || !d_stats || !d_ws || n <= 0 || batch <= 0 || batch > 65535) return M3D_EINVAL;
+  if (((uintptr_t)d_stats | (uintptr_t)d_ws) & 7) return M3D_EINVAL;
+  if (ws_bytes < (size_t)batch * m3d_norm1_workspace_bytes()) return M3D_EWORKSPACE;
+  hipStream_t st = m3d::as_stream(stream);
+  if (in_dtype == 0) return run_stats((const uint16_t*)d_in, batch, (long long)n, (double*)d_ws, d_stats, st);
+  if (in_dtype == 1) return run_stats((const float*)d_in, batch, (long long)n, (double*)d_ws, d_stats, st);
   return M3D_EINVAL;
 }

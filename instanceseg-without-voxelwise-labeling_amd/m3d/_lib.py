@@ -10,7 +10,7 @@ _lib = None
 
 SYMBOLS = [
     "m3d_version", "m3d_error_string", "m3d_last_hip_error", "m3d_set_option", "m3d_get_option", "m3d_tuning_build",
-    "m3d_conv3d_stem5_prepare_dgrad_weights", "m3d_conv3d_stem5_dgrad", "m3d_norm1_workspace_bytes", "m3d_norm1", "m3d_norm1_batched",
+    "m3d_conv3d_stem5_prepare_dgrad_weights", "m3d_conv3d_stem5_dgrad", "m3d_norm1_workspace_bytes", "m3d_norm1", "m3d_norm1_batched", "m3d_norm1_stats",
     "m3d_linear_workspace_bytes", "m3d_linear_forward", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_pack", "m3d_absmax", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_pack", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_f16x2_forward", "m3d_linear_f16x2_forward_bounds",
     "m3d_box_head_workspace_bytes", "m3d_box_head_forward",
     "m3d_linear_bf16x3_workspace_bytes", "m3d_linear_bf16x3_forward", "m3d_mask_paste3d_workspace_bytes", "m3d_mask_paste3d", "m3d_linear_bf16x3_w32_workspace_bytes", "m3d_linear_bf16x3_w32_forward", "m3d_roi_align3d_tap_tables", "m3d_linear_bf16x3_roi_workspace_bytes", "m3d_linear_bf16x3_roi_forward",
@@ -36,12 +36,19 @@ SYMBOLS = [
     "m3d_box_head_targets_workspace_bytes", "m3d_box_head_targets", "m3d_box_head_target_blobs", "m3d_box_head_loss",
     "m3d_bn_stats", "m3d_bn_invstd", "m3d_bn_apply", "m3d_bn_backward",
     "m3d_sgd_chunk", "m3d_sgd_step",
+    "m3d_train_sample",
 ]
 
 
 class SgdTensor(C.Structure):
     """m3d_sgd_tensor of include/m3d.h: one parameter of an m3d_sgd_step call"""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("n", C.c_longlong), ("lr", C.c_float), ("wd", C.c_float)]
+
+
+class TrainImage(C.Structure):
+    """m3d_train_image of include/m3d.h: one image of an m3d_train_sample call"""
+    _fields_ = [("vol", C.c_void_p), ("stats", C.c_void_p), ("boxes", C.c_void_p), ("dtype", C.c_int), ("depth", C.c_int),
+                ("height", C.c_int), ("width", C.c_int), ("num_boxes", C.c_int), ("start_max", C.c_int * 3)]
 
 
 class BoxHead(C.Structure):

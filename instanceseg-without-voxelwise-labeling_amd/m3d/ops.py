@@ -7,12 +7,12 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import lib, check, M3DError, SgdTensor, BoxHead
+from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage
 
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -790,6 +790,88 @@ def norm1_batched(vols, f32_arith=True, out=None):
     check(lib().m3d_norm1_batched(_ptr(vols), 0 if vols.dtype == torch.uint16 else 1, B, C.c_int64(n), int(bool(f32_arith)),
                                   _ptr(out), None, _ptr(ws), C.c_size_t(wsb), _stream()), "norm1_batched")
     return out
+
+
+def norm1_stats(vols, batch=None):
+    """mean, std, count of vol[vol > 0] without the normalised volume: fp64 [3] (batch=None: `vols` is one volume), or fp64 [batch, 3] for
+    `batch` volumes of equal size stacked in `vols`.  The bits ops.norm1(..., return_stats=True) reports."""
+    _need_gpu(vols)
+    vols = vols.contiguous()
+    if vols.dtype not in (torch.uint16, torch.float32):
+        raise TypeError("norm1 takes uint16 or float32 volumes")
+    B = 1 if batch is None else int(batch)
+    if B < 1 or vols.numel() % B:
+        raise M3DError("norm1_stats: %d elements do not make %d volumes" % (vols.numel(), B))
+    wsb = lib().m3d_norm1_workspace_bytes() * B
+    ws = torch.empty((wsb // 8,), dtype=torch.float64, device=vols.device)
+    stats = torch.empty((B, 3), dtype=torch.float64, device=vols.device)
+    check(lib().m3d_norm1_stats(_ptr(vols), 0 if vols.dtype == torch.uint16 else 1, B, C.c_int64(vols.numel() // B), _ptr(stats),
+                                _ptr(ws), C.c_size_t(wsb), _stream()), "norm1_stats")
+    return stats[0] if batch is None else stats
+
+
+# ------------------------------------------------------------------ training samples (csrc/train_sample.hip)
+def train_sample(images, in_size, need_crop, seeds, max_boxes, fixed_origin=None, data=None, meta=None, boxes_out=None, score=None):
+    """m3d_train_sample: the normalised crops and ground-truth boxes of a minibatch, from volumes resident on the device, on the current
+    stream and without a host round trip.
+
+    images: per image (vol, stats, boxes, start_max): vol a contiguous CUDA uint16 / float32 [D,H,W] tensor, stats its fp64 [3] statistics
+    (norm1_stats), boxes CUDA fp32 [K,6], start_max host (x, y, z).  in_size (s, h, w); seeds: one int per image; fixed_origin: None or
+    per image (x, y, z).  data: None, or the contiguous fp32 tensor of B s h w elements to write; meta: None, or a contiguous int32 tensor
+    of B (8 + max_boxes) elements that receives info and keep side by side (one copy brings both to the host); boxes_out, score: None, or
+    the contiguous fp32 / fp64 tensors of B max_boxes 6 / B elements to write.
+    Returns data fp32 [B,1,s,h,w], boxes fp32 [B,max_boxes,6], keep int32 [B,max_boxes], info int32 [B,8], score fp64 [B]."""
+    B = len(images)
+    s, h, w = (int(v) for v in in_size)
+    arr = (TrainImage * max(B, 1))()
+    dev = None
+    for i, (vol, stats, boxes, start_max) in enumerate(images):
+        _need_gpu(vol, stats, boxes)
+        if vol.dtype not in (torch.uint16, torch.float32) or vol.dim() != 3 or not vol.is_contiguous():
+            raise M3DError("train_sample: volume %d must be a contiguous uint16 or float32 [D,H,W] tensor" % i)
+        if stats.dtype != torch.float64 or stats.numel() != 3 or not stats.is_contiguous():
+            raise M3DError("train_sample: statistics %d must be a contiguous fp64 [3] tensor" % i)
+        if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 6 or not boxes.is_contiguous():
+            raise M3DError("train_sample: boxes %d must be a contiguous fp32 [K,6] tensor" % i)
+        dev = vol.device
+        e = arr[i]
+        e.vol, e.stats, e.boxes, e.dtype = vol.data_ptr(), stats.data_ptr(), boxes.data_ptr(), 0 if vol.dtype == torch.uint16 else 1
+        e.depth, e.height, e.width, e.num_boxes = int(vol.shape[0]), int(vol.shape[1]), int(vol.shape[2]), int(boxes.shape[0])
+        e.start_max[0], e.start_max[1], e.start_max[2] = (int(v) for v in start_max)
+    if dev is None:
+        raise M3DError("train_sample: no images")
+    max_boxes = int(max_boxes)
+    if data is None:
+        data = torch.empty((B, 1, s, h, w), dtype=torch.float32, device=dev)
+    elif not data.is_cuda or data.dtype != torch.float32 or data.numel() != B * s * h * w or not data.is_contiguous():
+        raise M3DError("train_sample: data must be a contiguous CUDA fp32 tensor of %d elements" % (B * s * h * w))
+    _claim(data)
+    if meta is None:
+        meta = torch.empty((B * (8 + max_boxes),), dtype=torch.int32, device=dev)
+    elif not meta.is_cuda or meta.dtype != torch.int32 or meta.numel() != B * (8 + max_boxes) or not meta.is_contiguous():
+        raise M3DError("train_sample: meta must be a contiguous CUDA int32 tensor of %d elements" % (B * (8 + max_boxes)))
+    info, keep = meta.view(-1)[:B * 8].view(B, 8), meta.view(-1)[B * 8:].view(B, max_boxes)
+    if boxes_out is None:
+        boxes_out = torch.empty((B, max_boxes, 6), dtype=torch.float32, device=dev)
+    elif not boxes_out.is_cuda or boxes_out.dtype != torch.float32 or boxes_out.numel() != B * max_boxes * 6 or not boxes_out.is_contiguous():
+        raise M3DError("train_sample: boxes_out must be a contiguous CUDA fp32 tensor of %d elements" % (B * max_boxes * 6))
+    if score is None:
+        score = torch.empty((B,), dtype=torch.float64, device=dev)
+    elif not score.is_cuda or score.dtype != torch.float64 or score.numel() != B or not score.is_contiguous():
+        raise M3DError("train_sample: score must be a contiguous CUDA fp64 tensor of %d elements" % B)
+    size = (C.c_int * 3)(s, h, w)
+    sd = (C.c_uint64 * max(B, 1))(*[int(v) & (2 ** 64 - 1) for v in seeds]) if seeds is not None else None
+    fx = None
+    if fixed_origin is not None:
+        flat = [int(v) for o in fixed_origin for v in o]
+        if len(flat) != 3 * B:
+            raise M3DError("train_sample: fixed_origin needs (x, y, z) per image")
+        fx = (C.c_int * (3 * B))(*flat)
+    if sd is not None and len(seeds) != B:
+        raise M3DError("train_sample: one seed per image")
+    check(lib().m3d_train_sample(arr, B, size, int(bool(need_crop)), sd, fx, max_boxes, _ptr(data), _ptr(boxes_out), _ptr(keep), _ptr(info),
+                                 _ptr(score), None, None, _stream()), "train_sample")
+    return data.view(B, 1, s, h, w), boxes_out.view(B, max_boxes, 6), keep, info, score.view(B)
 
 
 # ------------------------------------------------------------------ Otsu 2D
