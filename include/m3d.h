@@ -1077,6 +1077,32 @@ int m3d_train_sample(const m3d_train_image* images, int count, const int* in_siz
                      const int* fixed_origin, int max_boxes, float* d_data, float* d_boxes, int32_t* d_keep, int32_t* d_info,
                      double* d_score, void* d_ws, size_t* ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Backward of the fully-connected layers (fc_backward.hip; DESIGN, "Box-head backward"): the autograd of nn.Linear at
+ * lib/modeling/fast_rcnn_heads.py:84-85,114-117 (fc1, fc2) and :15-19,42-45 (cls_score, bbox_pred), on the operands as PyTorch stores
+ * them - no transposed copy of any operand is made.
+ *   m3d_linear_dgrad   d_gx [M,K] = d_gy [M,N] . d_weight [N,K]
+ *   m3d_linear_wgrad   d_gw [N,K] = d_gy [M,N]^T . d_x [M,K];  d_gb [N] (or NULL) = sum over m of d_gy[m,n], out of the same launch
+ * fp32-input MFMA GEMMs (v_mfma_f32_32x32x2_f32), fp32 accumulation.  Where the output has few tiles the reduction is cut into at most
+ * 64 slices, a function of (M, N, K) only; the partial sums live in d_ws and are added in slice order, and d_gb is summed in row order
+ * without atomics: results are bit-identical run to run.  Error bound per element, with R the reduction length (N for dgrad, M for wgrad
+ * and d_gb) and S the slices: |out - out64| <= gamma_n sum |a_k b_k| + 2^-24 |out64|, n = R + S, gamma_n = n 2^-24 / (1 - n 2^-24), the
+ * sums taken in fp64 from the fp32 inputs; an output whose products are all zero is exactly 0.
+ * d_weight, d_x, d_gx, d_gw: K % 4 == 0 and 16-byte aligned, as m3d_linear_forward.  d_gy: any M, N >= 1 at 4-byte alignment (rows that
+ * are not 16-byte multiples are loaded element by element).
+ * Limits, checked before any device pointer is followed or anything is launched.  M3D_EINVAL: a NULL required pointer, a pointer that is
+ * not 4-byte aligned, N < 1, K < 1, M < 0, d_ws NULL or ws_bytes smaller than the matching *_workspace_bytes (which may be 0: then
+ * d_ws may be NULL).  M3D_EUNSUPPORTED: K % 4 != 0, a big operand (or a needed d_ws) that is not 16-byte aligned, an operand of 2^31
+ * elements or more.  M == 0: dgrad does nothing; wgrad zero-fills d_gw, and d_gb if given (d_gy and d_x are not looked at).
+ * The workspace sizes are multiples of 16 and non-decreasing in M.
+ * ------------------------------------------------------------------------------------------------------- */
+size_t m3d_linear_dgrad_workspace_bytes(int M, int N, int K);
+int m3d_linear_dgrad(const float* d_gy, const float* d_weight, float* d_gx, int M, int N, int K, void* d_ws, size_t ws_bytes,
+                     void* stream);
+size_t m3d_linear_wgrad_workspace_bytes(int M, int N, int K);
+int m3d_linear_wgrad(const float* d_gy, const float* d_x, float* d_gw, float* d_gb, int M, int N, int K, void* d_ws, size_t ws_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

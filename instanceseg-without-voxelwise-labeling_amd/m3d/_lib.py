@@ -37,6 +37,7 @@ SYMBOLS = [
     "m3d_bn_stats", "m3d_bn_invstd", "m3d_bn_apply", "m3d_bn_backward",
     "m3d_sgd_chunk", "m3d_sgd_step",
     "m3d_train_sample",
+    "m3d_linear_dgrad_workspace_bytes", "m3d_linear_dgrad", "m3d_linear_wgrad_workspace_bytes", "m3d_linear_wgrad",
 ]
 
 
@@ -93,7 +94,7 @@ def _load(path):
               "m3d_cc_workspace_bytes", "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_stem_wino_packed_weight_bytes",
               "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
               "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes",
-              "m3d_box_head_workspace_bytes"):
+              "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -237,8 +237,8 @@ def _split_linear(weight, bias):
 
 class _LinearFn(torch.autograd.Function):
     """x [M,K] . W[N,K]^T + b on libm3d's GEMMs: the bf16x3 split kernels (fp32 accuracy) where K % 32 == 0 and N >= 64 (fc1, fc2),
-    else the fp32-input MFMA kernel (cls_score, bbox_pred).  Backward (training; off the inference path): the same kernels on
-    transposed operands."""
+    else the fp32-input MFMA kernel (cls_score, bbox_pred).  Backward (training; off the inference path): libm3d's dgrad and wgrad
+    GEMMs on the saved operands as they are (csrc/fc_backward.hip) - no transposed copy, the bias gradient out of the wgrad launch."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -254,11 +254,12 @@ class _LinearFn(torch.autograd.Function):
         gy = gy.contiguous()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = ops.linear(gy, weight.detach().t().contiguous()) if gy.shape[1] % 4 == 0 else gy @ weight.detach()
-        if ctx.needs_input_grad[1]:
-            gw = ops.linear(gy.t().contiguous(), x.detach().t().contiguous()) if gy.shape[0] % 4 == 0 else gy.t() @ x.detach()
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = gy.sum(0)
+            gx = ops.linear_dgrad(gy, weight.detach())
+        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_gb:
+            gw, gb = ops.linear_wgrad(gy, x.detach(), bias=want_gb)
+            if not ctx.needs_input_grad[1]:
+                gw = None
         return gx, gw, gb
 
 

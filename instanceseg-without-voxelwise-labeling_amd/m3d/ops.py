@@ -12,7 +12,7 @@ from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -574,6 +574,44 @@ def linear(x, weight, bias=None, relu=False, out=None):
     check(lib().m3d_linear_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), M, N, K, int(bool(relu)), _ptr(ws),
                                    C.c_size_t(wsb), _stream()), "linear_forward")
     return out
+
+
+def linear_dgrad(gy, weight, out=None):
+    """The input gradient of `linear`: gy [M,N] @ weight [N,K] -> [M,K] (m3d_linear_dgrad), on the weight as nn.Linear stores it - no
+    transposed copy.  weight: K % 4 == 0, 16-byte aligned; gy: any M, N.  Autograd of fast_rcnn_heads.py:84-85,114-117,15-19,42-45."""
+    _need_gpu(gy, weight)
+    gy, weight = _f32c(gy), _f32c(weight)
+    M, N = gy.shape
+    K = weight.shape[1]
+    if weight.shape[0] != N:
+        raise ValueError("linear_dgrad: gy is [%d,%d] but weight is %s" % (M, N, tuple(weight.shape)))
+    _claim(out)
+    if out is None:
+        out = torch.empty((M, K), dtype=torch.float32, device=gy.device)
+    wsb = lib().m3d_linear_dgrad_workspace_bytes(M, N, K)
+    ws = torch.empty((wsb // 4,), dtype=torch.float32, device=gy.device) if wsb else None
+    check(lib().m3d_linear_dgrad(_ptr(gy), _ptr(weight), _ptr(out), M, N, K, _ptr(ws), C.c_size_t(wsb), _stream()), "linear_dgrad")
+    return out
+
+
+def linear_wgrad(gy, x, bias=True, out=None):
+    """The weight and bias gradients of `linear` in one launch: (gy.T [N,M] @ x [M,K] -> [N,K], gy.sum(0) -> [N] or None without
+    `bias`) (m3d_linear_wgrad), on both operands as they are - no transposed copy; an empty batch gives zeros.  x: K % 4 == 0, 16-byte
+    aligned; gy: any M, N.  `out`: the [N,K] tensor to write.  Autograd of fast_rcnn_heads.py:84-85,114-117,15-19,42-45."""
+    _need_gpu(gy, x)
+    gy, x = _f32c(gy), _f32c(x)
+    M, N = gy.shape
+    K = x.shape[1]
+    if x.shape[0] != M:
+        raise ValueError("linear_wgrad: gy is [%d,%d] but x is %s" % (M, N, tuple(x.shape)))
+    _claim(out)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=gy.device)
+    gb = torch.empty((N,), dtype=torch.float32, device=gy.device) if bias else None
+    wsb = lib().m3d_linear_wgrad_workspace_bytes(M, N, K)
+    ws = torch.empty((wsb // 4,), dtype=torch.float32, device=gy.device) if wsb else None
+    check(lib().m3d_linear_wgrad(_ptr(gy), _ptr(x), _ptr(out), _ptr(gb), M, N, K, _ptr(ws), C.c_size_t(wsb), _stream()), "linear_wgrad")
+    return out, gb
 
 
 class SplitLinear:
