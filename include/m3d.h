@@ -979,6 +979,64 @@ int m3d_box_head_loss(const float* d_cls_score, const float* d_bbox_pred, const 
                       float* d_grad_score, float* d_grad_pred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Mask-branch training step (csrc/mask_train.hip; DESIGN, "Mask-branch training targets"): what add_mask_rcnn_blobs
+ * (lib/roi_data/mask_rcnn.py:34-135) does on the host for every sampled fg RoI - a volume filled in Python, skimage's resize, a
+ * threshold - and mask_rcnn_losses (lib/modeling/mask_rcnn_heads.py:90-99).  With the resize carried out in fp64, "resize > 0" is a set
+ * predicate: output (i,j,k) is set iff a source voxel is set inside F_s(i) x F_h(j) x F_w(k), F_n(i) = [lo, hi] the source indices
+ * whose weight at output i is not 0 (Gaussian radius int(4 sigma + 0.5), sigma = max(0, (n / M - 1) / 2), none for sigma <= 1e-15;
+ * order-1 corners of the fp64 coordinate n / M (i + 0.5) - 0.5, the upper one only with a weight that is not exactly 0; mirror
+ * boundary).  That is what is computed.  The reference's resize writes fp32 and loses products below 2^-150: on extents where a corner
+ * weight is about 2e-15 (M = 14: 18, 34, 58, 82, ... - 42 lengths up to 1024) the result can hold voxels, on that corner's output index,
+ * which the reference leaves 0; never fewer (DESIGN).
+ *   m3d_mask_targets  d_labels int32 [B, batch], d_rois fp32 [B, batch, 6], d_counts int64 [B, 8]: the stacked outputs of
+ *                     m3d_box_head_targets; the fg rows of image b are its first min(counts[b][1], fg_per_im) rows.  gt_offsets HOST
+ *                     int32 [B + 1], d_gt_classes int32 / d_gt_crowd uint8 [sum K] (NULL: all 1 / none) as for m3d_box_head_targets.
+ *                     Per fg row: the IoU (m3d_bbox_overlaps3d) against the boxes of the image's objects with class > 0 that are not
+ *                     crowd, in their order; the FIRST arg-max is the row's object (all-zero IoUs: the first such object; no such
+ *                     object: index -1 and an all-zero target).
+ *                     mode M3D_MASK_SPOT: d_spots fp32 [sum K, 4] = (x, y, z, r) in tile coordinates, in_size HOST int32 [3] =
+ *                     TRAIN.IN_SIZE (slices, height, width).  Boxes: spots_to_boxes (segms.py:209-225), c -+ (r - 1) in fp32 clipped
+ *                     to [0, IN_SIZE - 1].  Target: spot_to_mask_wrt_box (segms.py:120-150): extents int(max(hi - lo, 2)) of the fp32
+ *                     RoI (no + 1), centre sp - lo in fp32, voxel set iff ((i - z)^2 + (j - y)^2) + (k - x)^2 < r^2 in fp32 (strict)
+ *                     for some integer point of the footprint box - decided at the per-axis nearest integers.
+ *                     mode M3D_MASK_LABELS: d_gt fp32 [sum K, 6] the roidb boxes, d_markers int32 [sum K], images HOST [B]: per image
+ *                     the device label volume [depth, height, width] in tile coordinates, dtype 0 = uint16, 1 = int32.  Target:
+ *                     rle_to_mask_wrt_box (segms.py:152-193) with mask_gt = (label == marker): both boxes truncated towards zero,
+ *                     extent max(hi - lo, 2) of the integer RoI, copied region [max(lo), min(hi)) per axis (cut to the extent and to
+ *                     the volume, so every read lies inside it; an empty intersection copies nothing, where the reference raises),
+ *                     then the interval-"any" along x, y and z, one read per label.
+ *                     RoI extents are clamped to [2, 1024] on the device before any size is derived from them.
+ *                     Outputs (device, fixed shapes, written whole): d_masks int32 [B, fg_per_im, Cm M^3], z-major as
+ *                     np.reshape(mask, M**3), Cm = cls_specific ? num_classes : 1; with cls_specific every slot outside the row's
+ *                     class block is -1 (_expand_to_class_specific_mask_targets); rows beyond the fg count are all -1.
+ *                     d_mask_rois fp32 [B, fg_per_im, 6] (0 beyond), d_assign int32 [B, fg_per_im] the object's index within the
+ *                     image (-1 beyond), d_mask_counts int64 [B, 4] = fg rows, positive voxels, labelled voxels, 0.
+ *                     One launch; integer logic and integer atomics only: bit-identical run to run.  No workspace.
+ *   m3d_mask_loss     d_mask_pred fp32 [num_rois, mask_classes, M, M, M], d_masks int32 of the same element count.  W = the number
+ *                     of targets > -1, counted on the device (d_num int64 [1], may be NULL).  d_loss fp32 [1] = weight_loss_mask *
+ *                     sum over t > -1 of (max(x, 0) - x t + log1p(exp(-|x|))) / W; d_grad (input shape, written whole) =
+ *                     weight_loss_mask (sigmoid(x) - t) / W at labelled elements, exactly 0 elsewhere.  W = 0 (the reference divides
+ *                     0 by 0): loss 0 and an all-zero gradient.  Terms in fp64 from the fp32 inputs; one partial sum per chunk of
+ *                     4096 elements (fixed tree), a finish kernel adds them in ascending order; each result rounded once; no
+ *                     floating-point atomics.  Workspace m3d_mask_loss_workspace_bytes(num_rois, mask_classes, M), 8-byte aligned.
+ * Limits, checked before any device pointer is followed or anything is launched.  M3D_EINVAL: a NULL or misaligned pointer, M < 2,
+ * fg_per_im < 1, batch_per_im < 1, num_images < 1, num_classes < 2, another mode, another label dtype, descending offsets, in mask mode
+ * an image without objects (the sampler's counts are not read on the host, so every image may hold fg rows) or without a volume.
+ * M3D_EUNSUPPORTED: num_images > 64, M > 32, num_classes > 64, fg_per_im > 4096, K > 2048 in an image, 2^31 loss elements or more.
+ * ------------------------------------------------------------------------------------------------------- */
+#define M3D_MASK_SPOT 0
+#define M3D_MASK_LABELS 1
+typedef struct { const void* labels; int dtype, depth, height, width; } m3d_mask_image;
+int m3d_mask_targets(const int32_t* d_labels, const float* d_rois, const int64_t* d_counts, int num_images, int batch_per_im,
+                     int fg_per_im, int resolution, int num_classes, int cls_specific, int mode, const int32_t* gt_offsets,
+                     const int32_t* d_gt_classes, const uint8_t* d_gt_crowd, const float* d_spots, const int32_t* in_size,
+                     const float* d_gt, const int32_t* d_markers, const m3d_mask_image* images, int32_t* d_masks, float* d_mask_rois,
+                     int32_t* d_assign, int64_t* d_mask_counts, void* stream);
+size_t m3d_mask_loss_workspace_bytes(int64_t num_rois, int mask_classes, int resolution);
+int m3d_mask_loss(const float* d_mask_pred, const int32_t* d_masks, int64_t num_rois, int mask_classes, int resolution,
+                  double weight_loss_mask, float* d_loss, int64_t* d_num, float* d_grad, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * BatchNorm3d on batch statistics (csrc/bn_train.hip): what nn.BatchNorm3d -> nnf.relu -> nn.MaxPool3d(2, 2) of lib/modeling/DSN.py:19-68
  * do under maskRCNN.train(), forward and backward.  d_x fp32 contiguous [batch, channels, depth, height, width]; V = depth height width
  * values per (image, channel) slab, n = batch V values per channel.  Every sum runs in fp64 over spans of one slab whose boundaries

@@ -38,6 +38,7 @@ SYMBOLS = [
     "m3d_sgd_chunk", "m3d_sgd_step",
     "m3d_train_sample",
     "m3d_linear_dgrad_workspace_bytes", "m3d_linear_dgrad", "m3d_linear_wgrad_workspace_bytes", "m3d_linear_wgrad",
+    "m3d_mask_targets", "m3d_mask_loss_workspace_bytes", "m3d_mask_loss",
 ]
 
 
@@ -50,6 +51,11 @@ class TrainImage(C.Structure):
     """m3d_train_image of include/m3d.h: one image of an m3d_train_sample call"""
     _fields_ = [("vol", C.c_void_p), ("stats", C.c_void_p), ("boxes", C.c_void_p), ("dtype", C.c_int), ("depth", C.c_int),
                 ("height", C.c_int), ("width", C.c_int), ("num_boxes", C.c_int), ("start_max", C.c_int * 3)]
+
+
+class MaskImage(C.Structure):
+    """m3d_mask_image of include/m3d.h: the label volume of one image of an m3d_mask_targets call in mask mode"""
+    _fields_ = [("labels", C.c_void_p), ("dtype", C.c_int), ("depth", C.c_int), ("height", C.c_int), ("width", C.c_int)]
 
 
 class BoxHead(C.Structure):
@@ -94,7 +100,8 @@ def _load(path):
               "m3d_cc_workspace_bytes", "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_stem_wino_packed_weight_bytes",
               "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
               "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes",
-              "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes"):
+              "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes",
+              "m3d_mask_loss_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -143,6 +143,20 @@ def epoch_order(n, seed, epoch):
     return sorted(range(n), key=lambda i: (keys[i], i))
 
 
+def _shift_spots(segms, keep, origin, cfg):
+    """blob.py:153-161: the centres of the kept spheres move by the crop origin (x, y, z) and are clipped to [0, IN_SIZE - 1], in fp32;
+    the radius stays.  Without a crop (NEED_CROP False) crop_data_3d never runs and the spheres pass through."""
+    if segms is None:
+        return None
+    sp = np.array(segms[keep], np.float32).reshape(-1, 4)
+    if cfg.NEED_CROP:
+        S, H, W = cfg.IN_SIZE
+        for a, top in enumerate((W - 1, H - 1, S - 1)):
+            sp[:, a] -= np.float32(origin[a])
+            np.clip(sp[:, a], 0, top, out=sp[:, a])
+    return sp
+
+
 class Batch:
     """One minibatch.  Device tensors: data fp32 [B,1,s,h,w]; boxes fp32 [B,max_boxes,6] (kept boxes first, in order, then zeros); keep
     int32 [B,max_boxes] (source index of every kept box, then -1); info int32 [B,8] = ox, oy, oz, kept, status, candidates, 0, 0; score
@@ -159,14 +173,15 @@ class Batch:
             B = len(self.indices)
             h = self._host.numpy()
             info, keep = h[:B * 8].reshape(B, 8), h[B * 8:].reshape(B, -1)
-            boxes, classes, crowd = [], [], []
+            boxes, classes, crowd, spots = [], [], [], []
             for b, i in enumerate(self.indices):
                 n = int(info[b, 3])
                 k = keep[b, :n]
                 boxes.append(self.boxes[b, :n])
                 classes.append(self._set.classes[i][k])
                 crowd.append(self._set.crowd[i][k])
-            self._lists = (boxes, classes, crowd, info.copy())
+                spots.append(_shift_spots(self._set.segms[i], k, info[b, :3], self._set.cfg))
+            self._lists = (boxes, classes, crowd, info.copy(), spots)
         return self._lists
 
     @property
@@ -183,12 +198,18 @@ class Batch:
         return self._read()[2]
 
     @property
+    def gt_spots(self):
+        """per image the spheres (x, y, z, r) of the kept boxes in tile coordinates, host fp32 [K_b,4] (None for a dataset without
+        segms): what mask_targets takes with anno_type 'spot'.  Waits for the same host read as gt_boxes."""
+        return self._read()[4]
+
+    @property
     def host_info(self):
         return self._read()[3]
 
     def rpn_boxes(self, b):
         """(gt, dc) of image b as add_rpn_blobs splits them (rpn.py:66-73): the boxes of a class that are no crowd, and the crowd boxes"""
-        boxes, classes, crowd, _ = self._read()
+        boxes, classes, crowd = self._read()[:3]
         gt_i, dc_i = np.flatnonzero((classes[b] > 0) & ~crowd[b]), np.flatnonzero(crowd[b])
         if len(dc_i) == 0 and len(gt_i) == len(classes[b]):
             return boxes[b], boxes[b][:0]
@@ -207,7 +228,7 @@ class TrainSet:
         if len(volumes) != len(annotations) or not len(volumes):
             raise ops.M3DError("TrainSet: one annotation per volume, and at least one volume")
         self.cfg, self.device = cfg, torch.device(device)
-        self.volumes, self.stats, self.boxes, self.classes, self.crowd, self.start_max = [], [], [], [], [], []
+        self.volumes, self.stats, self.boxes, self.classes, self.crowd, self.start_max, self.segms = [], [], [], [], [], [], []
         s, h, w = cfg.IN_SIZE
         for vol, ann in zip(volumes, annotations):
             boxes, classes, crowd = list(ann)[:3]
@@ -227,6 +248,8 @@ class TrainSet:
             self.boxes.append(torch.from_numpy(boxes).to(self.device))
             self.classes.append(np.asarray(classes, np.int32).reshape(-1))
             self.crowd.append(np.asarray(crowd, bool).reshape(-1))
+            sg = getattr(ann, "segms", None)
+            self.segms.append(None if sg is None else np.ascontiguousarray(sg, np.float32).reshape(-1, 4))
             lo = np.floor(boxes[:, :3].min(axis=0))
             self.start_max.append(tuple(int(min(lo[a], d - n)) for a, d, n in ((0, W, w), (1, H, h), (2, D, s))))   # blob.py:106-114
         self.max_boxes = max(int(b.shape[0]) for b in self.boxes)

@@ -7,13 +7,13 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage
+from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage, MaskImage
 
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -2169,6 +2169,85 @@ def box_head_loss_grad(cls_score, bbox_pred, labels, targets, counts):
     check(lib().m3d_box_head_loss(_ptr(x), _ptr(p), _ptr(labels), _ptr(targets), _ptr(counts), B, batch, Cn, _ptr(losses), _ptr(gx), _ptr(gp),
                                   _stream()), "box_head_loss")
     return losses, gx, gp
+
+
+# ------------------------------------------------------------------ mask-branch training step (csrc/mask_train.hip)
+MASK_SPOT, MASK_LABELS = 0, 1
+
+
+def mask_target_sets(labels, rois, counts, gt_offsets, fg_per_im, resolution, num_classes, cls_specific, spots=None, in_size=None,
+                     gt=None, markers=None, volumes=None, gt_classes=None, gt_crowd=None):
+    """m3d_mask_targets for the B images of a minibatch: labels int32 [B,batch], rois fp32 [B,batch,6], counts int64 [B,8] of
+    box_head_target_sets; host offsets [B+1] into the concatenated objects.  Spot mode: spots CUDA fp32 [sum K,4] (x, y, z, r) and in_size
+    (slices, height, width).  Mask mode: gt CUDA fp32 [sum K,6], markers int32 [sum K], volumes: per image a CUDA uint16 / int32 label
+    volume [D,H,W].  -> (masks int32 [B,fg_per_im,Cm M^3], rois fp32 [B,fg_per_im,6], assign int32 [B,fg_per_im], counts int64 [B,4]),
+    all on the device, no synchronisation."""
+    _need_gpu(labels, rois, counts, spots, gt, markers, gt_classes, gt_crowd)
+    if (spots is None) == (gt is None):
+        raise M3DError("mask_target_sets: either spots (spot mode) or gt boxes, markers and label volumes (mask mode)")
+    if labels.dim() != 2 or labels.dtype != torch.int32 or counts.dtype != torch.int64 or tuple(counts.shape) != (labels.shape[0], 8) or \
+            tuple(rois.shape) != tuple(labels.shape) + (6,) or rois.dtype != torch.float32:
+        raise M3DError("mask_target_sets: labels int32 [B,batch], rois fp32 [B,batch,6], counts int64 [B,8]")
+    labels, rois, counts = labels.contiguous(), rois.contiguous(), counts.contiguous()
+    B, batch, dev = labels.shape[0], labels.shape[1], labels.device
+    off = np.ascontiguousarray(gt_offsets, np.int32)
+    if off.shape != (B + 1,):
+        raise M3DError("mask_target_sets: %d images need %d object offsets" % (B, B + 1))
+    total = int(off[-1])
+    for name, t, dt, width in (("spots", spots, torch.float32, 4), ("gt", gt, torch.float32, 6), ("markers", markers, torch.int32, 1),
+                               ("gt_classes", gt_classes, torch.int32, 1), ("gt_crowd", gt_crowd, torch.uint8, 1)):
+        if t is not None and (t.dtype != dt or t.numel() != total * width or not t.is_contiguous()):
+            raise M3DError("mask_target_sets: %s must be a contiguous %s tensor with %d value(s) per object, %d objects" % (name, dt, width, total))
+    images, size = None, None
+    if spots is not None:
+        size = (C.c_int32 * 3)(*[int(v) for v in in_size])
+        mode = MASK_SPOT
+    else:
+        if markers is None or volumes is None or len(volumes) != B:
+            raise M3DError("mask_target_sets: mask mode needs markers and one label volume per image")
+        images = (MaskImage * B)()
+        for b, v in enumerate(volumes):
+            if v is None:
+                continue
+            _need_gpu(v)
+            if v.dim() != 3 or v.dtype not in (torch.uint16, torch.int32) or not v.is_contiguous():
+                raise M3DError("mask_target_sets: a label volume is a contiguous uint16 or int32 [D,H,W] tensor")
+            images[b].labels, images[b].dtype = v.data_ptr(), 0 if v.dtype == torch.uint16 else 1
+            images[b].depth, images[b].height, images[b].width = (int(x) for x in v.shape)
+        mode = MASK_LABELS
+    M, F = int(resolution), int(fg_per_im)
+    Cm = int(num_classes) if cls_specific else 1
+    shape_ok = 2 <= M <= 32 and 1 <= F <= 4096 and 1 <= Cm <= 64
+    masks = torch.empty((B, F, Cm * M ** 3) if shape_ok else (1,), dtype=torch.int32, device=dev)
+    out_rois = torch.empty((B, F, 6) if shape_ok else (1,), dtype=torch.float32, device=dev)
+    assign = torch.empty((B, F) if shape_ok else (1,), dtype=torch.int32, device=dev)
+    mcounts = torch.empty((B, 4), dtype=torch.int64, device=dev)
+    check(lib().m3d_mask_targets(_ptr(labels), _ptr(rois), _ptr(counts), B, batch, F, M, int(num_classes), int(bool(cls_specific)), mode,
+                                 off.ctypes.data_as(C.c_void_p), _ptr(gt_classes), _ptr(gt_crowd), _ptr(spots), size, _ptr(gt),
+                                 _ptr(markers), images, _ptr(masks), _ptr(out_rois), _ptr(assign), _ptr(mcounts), _stream()),
+          "mask_targets")
+    return masks, out_rois, assign, mcounts
+
+
+def mask_loss_grad(mask_pred, masks, weight_loss_mask=1.0):
+    """m3d_mask_loss: mask_pred fp32 [N,Cm,M,M,M], masks int32 with N Cm M^3 elements (-1 = ignore).
+    -> (loss fp32 [1], number of labelled elements int64 [1], d loss / d mask_pred)."""
+    _need_gpu(mask_pred, masks)
+    x = _f32c(mask_pred)
+    if x.dim() != 5 or x.shape[2] != x.shape[3] or x.shape[3] != x.shape[4] or masks.dtype != torch.int32 or masks.numel() != x.numel():
+        raise M3DError("mask_loss_grad: mask_pred [N,Cm,M,M,M] and int32 masks of the same element count, got %s and %s %s"
+                       % (tuple(x.shape), masks.dtype, tuple(masks.shape)))
+    masks = masks.contiguous()
+    N, Cm, M = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    L = lib()
+    nbytes = int(L.m3d_mask_loss_workspace_bytes(C.c_int64(N), Cm, M))
+    ws = _workspace(max(nbytes, 1), x.device, "mask_loss")
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    num = torch.empty((1,), dtype=torch.int64, device=x.device)
+    gx = torch.empty_like(x)
+    check(L.m3d_mask_loss(_ptr(x), _ptr(masks), C.c_int64(N), Cm, M, C.c_double(float(weight_loss_mask)), _ptr(loss), _ptr(num), _ptr(gx),
+                          _ptr(ws), C.c_size_t(ws.numel()), _stream()), "mask_loss")
+    return loss, num, gx
 
 
 # ------------------------------------------------------------------ BatchNorm3d on batch statistics (csrc/bn_train.hip)

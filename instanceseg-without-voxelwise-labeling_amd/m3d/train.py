@@ -10,7 +10,12 @@ lib/roi_data/fast_rcnn.py:129-248, lib/modeling/fast_rcnn_heads.py:50-66; DESIGN
 
 BatchNorm3d on batch statistics (csrc/bn_train.hip): bn_stats, the fused batch_norm_relu (BatchNorm3d -> ReLU -> MaxPool3d(2,2), forward
 and backward) and DsnBody, the reference's body on it.  Reference: lib/modeling/DSN.py:15-68 under maskRCNN.train(); DESIGN ("BatchNorm
-training")."""
+training").
+
+Mask branch from the sampled fg RoIs (csrc/mask_train.hip): per RoI the M^3 target of its ground-truth sphere or labelled instance, the
+sigmoid cross entropy over the labelled voxels, and MaskHead, the reference's head under its parameter names.  Reference:
+lib/roi_data/mask_rcnn.py:34-135, lib/utils/segms.py:120-225, lib/modeling/mask_rcnn_heads.py:20-68, 90-99, 132-193; DESIGN ("Mask-branch
+training targets")."""
 import math
 
 import numpy as np
@@ -20,7 +25,7 @@ from . import ops
 from .config import generate_anchors_3d
 
 __all__ = ["RpnTrainCfg", "RpnTargets", "rpn_targets", "rpn_losses", "BoxHeadTrainCfg", "BoxHeadTargets", "box_head_targets", "box_head_losses",
-           "bn_stats", "batch_norm_relu", "DsnBody"]
+           "bn_stats", "batch_norm_relu", "DsnBody", "MaskTrainCfg", "MaskTargets", "mask_targets", "mask_losses", "MaskHead"]
 
 
 class RpnTrainCfg:
@@ -217,12 +222,12 @@ class BoxHeadTargets:
                 for b in range(len(c))]
 
 
-def _per_image(values, gt_list, dtype, device, name):
+def _per_image(values, gt_list, dtype, device, name, caller="box_head_targets"):
     """per-image class / crowd arrays -> one device tensor over the concatenated boxes; an image given as None takes the default"""
     if values is None:
         return None
     if len(values) != len(gt_list):
-        raise ops.M3DError("box_head_targets: %s needs one entry per image" % name)
+        raise ops.M3DError("%s: %s needs one entry per image" % (caller, name))
     parts = []
     for v, g in zip(values, gt_list):
         if v is None:
@@ -230,7 +235,7 @@ def _per_image(values, gt_list, dtype, device, name):
         elif not torch.is_tensor(v):
             v = torch.from_numpy(np.ascontiguousarray(v).astype(np.int64).reshape(-1)).to(device)
         if v.numel() != g.shape[0]:
-            raise ops.M3DError("box_head_targets: %s has %d entries for %d boxes" % (name, v.numel(), g.shape[0]))
+            raise ops.M3DError("%s: %s has %d entries for %d boxes" % (caller, name, v.numel(), g.shape[0]))
         parts.append(v.reshape(-1).to(device=device, dtype=dtype))
     return torch.cat(parts).contiguous()
 
@@ -368,3 +373,182 @@ class DsnBody(torch.nn.Module):
                 bn.num_batches_tracked.add_(1)
             x = batch_norm_relu(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.training, bn.momentum, bn.eps, True, pool)
         return x
+
+
+class MaskTrainCfg:
+    """The MRCNN / TRAIN / MODEL keys the mask step reads; defaults = the nuclei YAML merged over lib/core/config.py."""
+
+    def __init__(self, **kw):
+        self.resolution = 14                                # MRCNN.RESOLUTION
+        self.anno_type = "mask"                             # MRCNN.ANNO_TYPE: 'mask' (label volume + markers) or 'spot' (spheres)
+        self.cls_specific = False                           # MRCNN.CLS_SPECIFIC_MASK
+        self.weight_loss_mask = 1.0                         # MRCNN.WEIGHT_LOSS_MASK
+        self.in_size = (64, 256, 256)                       # TRAIN.IN_SIZE: clips the boxes of the spots (segms.py:214)
+        self.num_classes = 2                                # MODEL.NUM_CLASSES
+        self.roi_xform_resolution = 7                       # MRCNN.ROI_XFORM_RESOLUTION
+        self.sampling_ratio = 2                             # MRCNN.ROI_XFORM_SAMPLING_RATIO
+        self.dim_reduced = 256                              # MRCNN.DIM_REDUCED
+        self.num_convs = 3                                  # MRCNN.ROI_MASK_HEAD: mask_rcnn_fcn_head_v1up3convs
+        unknown = sorted(set(kw) - set(self.__dict__))
+        if unknown:
+            raise TypeError("MaskTrainCfg: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(sorted(self.__dict__))))
+        self.__dict__.update(kw)
+        if self.anno_type not in ("mask", "spot"):
+            raise ValueError("MaskTrainCfg: anno_type is 'mask' or 'spot'")
+
+    @staticmethod
+    def nuclei(**kw):
+        return MaskTrainCfg(**kw)
+
+    @staticmethod
+    def soma(**kw):
+        d = dict(anno_type="spot", num_convs=4)
+        d.update(kw)
+        return MaskTrainCfg(**d)
+
+    @property
+    def mask_classes(self):
+        return int(self.num_classes) if self.cls_specific else 1
+
+
+class MaskTargets:
+    """The mask targets of the fg rows of B images, on the device, each image padded to fg_per_im rows:
+      masks int32 [B,fg_per_im,Cm M^3] (1 / 0, -1 = ignore; a padding row is all -1), rois fp32 [B,fg_per_im,6] (0 beyond the count),
+      assign int32 [B,fg_per_im] (the object's index within its image, -1 beyond), counts int64 [B,4] = fg rows, positive voxels,
+      labelled voxels, 0.  `labels` are the box-head labels [B,batch] the targets were made for."""
+
+    def __init__(self, masks, rois, assign, counts, labels, cfg):
+        self.masks, self.rois, self.assign, self.counts, self.labels, self.cfg = masks, rois, assign, counts, labels, cfg
+
+    @property
+    def rois7(self):
+        """fp32 [B fg_per_im, 7] for RoIAlign: the batch index in column 0; a padding row is a zero box on image 0."""
+        B, F = self.assign.shape
+        live = torch.arange(F, device=self.assign.device)[None, :] < self.counts[:, :1]
+        index = torch.arange(B, device=self.assign.device, dtype=torch.float32)[:, None] * live.float()
+        return torch.cat([index[:, :, None], self.rois], 2).reshape(B * F, 7)
+
+    def blobs(self):
+        """The reference's three blobs over the padded rows (mask_rcnn.py:110-112): mask_rois [B fg_per_im, 7], roi_has_mask_int32
+        [B batch] = labels > 0, masks_int32 [B fg_per_im, Cm M^3]."""
+        ops._need_gpu(self.masks, self.labels)
+        return dict(mask_rois=self.rois7, roi_has_mask_int32=(self.labels > 0).to(torch.int32).reshape(-1),
+                    masks_int32=self.masks.reshape(-1, self.masks.shape[2]))
+
+    def numpy(self):
+        """Host copies trimmed to their counts (synchronises): one dict of masks, rois, assign, counts per image."""
+        c = self.counts.cpu().numpy()
+        masks, rois, assign = (t.cpu().numpy() for t in (self.masks, self.rois, self.assign))
+        return [dict(masks=masks[b, :c[b, 0]], rois=rois[b, :c[b, 0]], assign=assign[b, :c[b, 0]], counts=c[b]) for b in range(len(c))]
+
+
+def _objects(values, width, dtype, device, name, B):
+    """per-image object arrays (NumPy or CUDA) -> (list of device tensors [K_b, width], host offsets)"""
+    if values is None or len(values) != B:
+        raise ops.M3DError("mask_targets: %s needs one array per image" % name)
+    out = []
+    for v in values:
+        if not torch.is_tensor(v):
+            v = torch.from_numpy(np.ascontiguousarray(v).astype(np.float32 if dtype == torch.float32 else np.int64)).to(device)
+        out.append(v.reshape(-1, width).to(device=device, dtype=dtype))
+    return out, np.concatenate([[0], np.cumsum([o.shape[0] for o in out])]).astype(np.int32)
+
+
+def mask_targets(box_targets, cfg, spots=None, gt_boxes=None, markers=None, labels=None, gt_classes=None, gt_crowd=None):
+    """The mask targets of the fg rows of `box_targets` (the BoxHeadTargets of the minibatch), on the device and without a host round trip.
+
+    cfg: MaskTrainCfg.  anno_type 'spot': spots = per image a NumPy or CUDA fp32 [K_b,4] array (x, y, z, r) in tile coordinates
+    (Batch.gt_spots).  anno_type 'mask': gt_boxes = per image the roidb boxes [K_b,6], markers = per image the K_b marker ids, labels =
+    per image a CUDA uint16 or int32 label volume [D,H,W] in tile coordinates.  The objects are those box_head_targets saw, in the same
+    order; gt_classes / gt_crowd as there.  A RoI takes the object whose box (for spots: spots_to_boxes of the sphere, not the roidb box)
+    overlaps it most, the first among equals.  Bit-identical run to run.  The target is "resize > 0" with the reference's resize carried
+    out in fp64: where the reference's fp32 resize underflows (extents such as 18, 34, 58) it can hold a few voxels more (DESIGN)."""
+    T = box_targets
+    if not torch.is_tensor(T.labels) or not T.labels.is_cuda:
+        raise ops.M3DError("mask_targets: the box-head targets must live on the device; there is no CPU path")
+    dev, B = T.labels.device, T.labels.shape[0]
+    if (cfg.anno_type == "spot") != (spots is not None) or (cfg.anno_type == "mask") != (gt_boxes is not None):
+        raise ops.M3DError("mask_targets: anno_type '%s' takes %s" % (cfg.anno_type, "spots" if cfg.anno_type == "spot" else
+                                                                      "gt_boxes, markers and labels"))
+    fg_per_im = T.cfg.fg_per_im
+    if cfg.anno_type == "spot":
+        objs, off = _objects(spots, 4, torch.float32, dev, "spots", B)
+        kw = dict(spots=torch.cat(objs).contiguous() if objs else None, in_size=cfg.in_size)
+    else:
+        objs, off = _objects(gt_boxes, 6, torch.float32, dev, "gt_boxes", B)
+        mk, off2 = _objects(markers, 1, torch.int32, dev, "markers", B)
+        if not np.array_equal(off, off2) or labels is None or len(labels) != B:
+            raise ops.M3DError("mask_targets: one marker per box and one label volume per image")
+        kw = dict(gt=torch.cat(objs).contiguous(), markers=torch.cat(mk).reshape(-1).contiguous(), volumes=list(labels))
+    out = ops.mask_target_sets(T.labels, T.rois, T.counts, off, fg_per_im, cfg.resolution, cfg.num_classes, cfg.cls_specific,
+                               gt_classes=_per_image(gt_classes, objs, torch.int32, dev, "gt_classes", "mask_targets"),
+                               gt_crowd=_per_image(gt_crowd, objs, torch.uint8, dev, "gt_crowd", "mask_targets"), **kw)
+    return MaskTargets(*out, labels=T.labels, cfg=cfg)
+
+
+class _MaskLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, masks, weight):
+        loss, _, gx = ops.mask_loss_grad(pred, masks, weight)
+        ctx.save_for_backward(gx)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, = ctx.saved_tensors
+        return gx * g, None, None
+
+
+def mask_losses(mask_pred, targets):
+    """loss_mask of mask_rcnn_losses for mask_pred [B fg_per_im, Cm, M, M, M] computed on `targets.rois7`; `targets`: the MaskTargets of
+    the minibatch.  The mean runs over the labelled voxels (padding rows and, with cls_specific, the other classes' blocks count nowhere
+    and get zero gradients; no labelled voxel at all: loss 0, where the reference divides 0 by 0).  One call computes the loss and the
+    gradient; backward scales the stored gradient."""
+    if not torch.is_tensor(mask_pred) or not mask_pred.is_cuda:
+        raise ops.M3DError("mask_losses: mask_pred must be a CUDA (ROCm) tensor; there is no CPU path")
+    return _MaskLoss.apply(mask_pred, targets.masks, float(targets.cfg.weight_loss_mask))
+
+
+class MaskHead(torch.nn.Module):
+    """mask_rcnn_fcn_head_v1upXconvs followed by mask_rcnn_outputs (mask_rcnn_heads.py:132-193, 20-68; dilation 1, conv classifier, no
+    upsampling) as one module under the reference's parameter names conv_fcn.{0,2,..}, upconv, classify: its state_dict, prefixed
+    Mask_Head. / Mask_Outs. by `detector_state`, is what MaskHeadM3D takes.  RoIAlign3D and the convolutions go through m3d.compat (the
+    library's kernels, forward and backward); ConvTranspose3d is torch's.  forward returns logits, as the reference does in training."""
+
+    def __init__(self, dim_in, cfg, stride):
+        super().__init__()
+        self.cfg, self.spatial_scale = cfg, 1.0 / float(stride)
+        dim = int(cfg.dim_reduced)
+        layers, cin = [], int(dim_in)
+        for _ in range(int(cfg.num_convs)):
+            layers += [torch.nn.Conv3d(cin, dim, 3, 1, 1), torch.nn.ReLU(inplace=True)]
+            cin = dim
+        self.conv_fcn = torch.nn.Sequential(*layers)
+        self.upconv = torch.nn.ConvTranspose3d(dim, dim, 2, 2, 0)
+        self.classify = torch.nn.Conv3d(dim, cfg.mask_classes, 1, 1, 0)
+        for m in list(self.conv_fcn) + [self.upconv]:
+            if not isinstance(m, torch.nn.ReLU):
+                torch.nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")     # MRCNN.CONV_INIT: MSRAFill
+                torch.nn.init.constant_(m.bias, 0.0)
+        if cfg.cls_specific:                                  # mask_rcnn_heads.py:38-46 with CONV_INIT MSRAFill, as both shipped configs set it
+            torch.nn.init.kaiming_normal_(self.classify.weight, mode="fan_out", nonlinearity="relu")
+        else:
+            torch.nn.init.normal_(self.classify.weight, std=0.001)
+        torch.nn.init.constant_(self.classify.bias, 0.0)
+
+    def detector_state(self):
+        """the parameters under the keys of the reference's detector (and of MaskHeadM3D): Mask_Head.*, Mask_Outs.classify.*"""
+        return {("Mask_Outs." if k.startswith("classify") else "Mask_Head.") + k: v for k, v in self.state_dict().items()}
+
+    def load_detector_state(self, params):
+        own = {k.split(".", 1)[1]: v for k, v in params.items() if k.startswith(("Mask_Head.", "Mask_Outs."))}
+        return self.load_state_dict(own)
+
+    def forward(self, feat, rois7):
+        from . import compat
+        r = int(self.cfg.roi_xform_resolution)
+        x = compat.RoIAlignFunction_3d(r, r, r, self.spatial_scale, int(self.cfg.sampling_ratio))(feat, rois7)
+        for m in self.conv_fcn:
+            x = compat.conv3d(x, m.weight, m.bias, 1, 1) if isinstance(m, torch.nn.Conv3d) else torch.relu(x)
+        x = torch.relu(self.upconv(x))
+        return compat.conv3d(x, self.classify.weight, self.classify.bias, 1, 0)

@@ -6,7 +6,10 @@ m3d.generate_proposals3d_batched under no_grad with the TRAIN top-N settings (RP
 RPN_NMS_THRESH 0.7); m3d.box_head_targets on those proposals and the ground-truth boxes; RoIAlign (7^3, sampling ratio 2) -> two FC
 layers -> cls_score / bbox_pred (lib/modeling/fast_rcnn_heads.py:12-47, 74-117) as plain torch.nn modules whose convolutions, linear
 layers and RoIAlign run on libm3d through m3d.compat; m3d.box_head_losses; torch.optim.SGD on the sum of the four losses.
-Prints all four losses per step.  One fixed sample; this is not a training driver (no data loading, schedule or checkpoints)."""
+Prints all four losses per step.  One fixed sample; this is not a training driver (no data loading, schedule or checkpoints).
+
+--mask spot (off by default; without it nothing changes) adds the mask branch: m3d.MaskHead on the same features, m3d.mask_targets from
+the spheres inscribed in the synthetic boxes, m3d.mask_losses; loss_mask joins the printed line and the sum."""
 import argparse
 import os
 import sys
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--hidden", type=int, default=256, help="width of the two FC layers (the reference has 1024)")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--mask", choices=("spot",), default=None, help="also train the mask branch on spheres inscribed in the boxes")
     a = ap.parse_args()
     import torch
     import m3d
@@ -73,7 +77,14 @@ def main():
     for m in net.modules():                       # running statistics; the reference trains on batch statistics (m3d.train.DsnBody does)
         if isinstance(m, torch.nn.BatchNorm3d):
             m.eval()
-    opt = torch.optim.SGD(list(net.parameters()) + list(head.parameters()), lr=a.lr, momentum=0.9)
+    params = list(net.parameters()) + list(head.parameters())
+    if a.mask:
+        mcfg = m3d.MaskTrainCfg.soma(in_size=tile, dim_reduced=4 * a.width, num_convs=2)
+        mask_head = m3d.MaskHead(8 * a.width, mcfg, rcfg.stride).cuda()
+        g = gt.cpu().numpy()                                                       # (x, y, z, r): centre and half the shortest edge
+        spots = torch.from_numpy(np.concatenate([(g[:, :3] + g[:, 3:]) / 2, (g[:, 3:] - g[:, :3]).min(1, keepdims=True) / 2], 1)).cuda()
+        params += list(mask_head.parameters())
+    opt = torch.optim.SGD(params, lr=a.lr, momentum=0.9)
     im_info = np.array([tile[0], tile[1], tile[2], 1.0])
     for step in range(a.steps):
         seed = 1000 * a.seed + step                                                # one sampling seed per step
@@ -87,11 +98,17 @@ def main():
         cls_score, bbox_pred = head(feat, targets.rois7)
         loss_cls, loss_bbox, accuracy = m3d.box_head_losses(cls_score, bbox_pred, targets)
         total = loss_rpn_cls + loss_rpn_bbox + loss_cls + loss_bbox
+        extra = ""
+        if a.mask:
+            mask_targets = m3d.mask_targets(targets, mcfg, spots=[spots])
+            loss_mask = m3d.mask_losses(mask_head(feat, mask_targets.rois7), mask_targets)
+            total = total + loss_mask
+            extra = " loss_mask %.6f" % loss_mask.item()
         opt.zero_grad()
         total.backward()
         opt.step()
-        print("step %d loss_rpn_cls %.6f loss_rpn_bbox %.6f loss_cls %.6f loss_bbox %.6f accuracy_cls %.4f total %.6f" % (
-            step, loss_rpn_cls.item(), loss_rpn_bbox.item(), loss_cls.item(), loss_bbox.item(), accuracy.item(), total.item()), flush=True)
+        print("step %d loss_rpn_cls %.6f loss_rpn_bbox %.6f loss_cls %.6f loss_bbox %.6f accuracy_cls %.4f%s total %.6f" % (
+            step, loss_rpn_cls.item(), loss_rpn_bbox.item(), loss_cls.item(), loss_bbox.item(), accuracy.item(), extra, total.item()), flush=True)
 
 
 if __name__ == "__main__":
