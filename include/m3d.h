@@ -271,6 +271,34 @@ int m3d_conv3d_wgrad(const float* d_in, const float* d_grad_out, float* d_grad_w
                      int depth, int height, int width, int k, void* d_ws, size_t ws_bytes, void* stream);
 int m3d_conv3d_bias_grad(const float* d_grad_out, float* d_grad_bias, int batch, int cout, int depth, int height,
                          int width, void* stream);
+/* The k = 3 weight gradient above on the f16 matrix cores at fp32 accuracy (csrc/conv3d_wgrad_f16.hip): the f16x2 cut of
+ * m3d_conv3d_zw_forward - each operand tensor scaled by ONE power of two (m3d::f16_scale_of of its bound) and cut into two fp16
+ * numbers while it is staged, three v_mfma_f32_32x32x16_f16 products hh + hl + lh per fp32 product, fp32 accumulation, the sum
+ * multiplied by 1 / s_g and 1 / s_x once at the end (exact).  d_in_max / d_gy_max: device arrays of m3d_conv3d_zw_slots() non-negative
+ * floats whose LARGEST is >= max |d_in| / max |d_grad_out| (what m3d_conv3d_zw_forward leaves in d_out_max; m3d_conv3d_zw_bound_of
+ * sweeps a tensor).  An input beyond its bound overflows fp16 (inf / NaN): the caller's contract, as for the zw forward.
+ *   supported   cin and cout multiples of 32 (<= 4096), every extent >= 1, at most 2^30 voxel tiles of 2 x 4 x 16 and (2^32 - 1) / 192
+ *               workgroups (a launch of fewer than 2^32 threads); everything else (and k != 3) stays on m3d_conv3d_wgrad.
+ *   accumulation  no accumulator takes more than `chain` <= 384 consecutive MFMAs (the f16 MFMA truncates when it adds): a split-K slot
+ *               is `tiles_per_slot` <= 16 tiles (24 MFMAs per accumulator and tile) and writes its partial to the workspace; the reduce
+ *               launch adds the `slots` partials with fp32 round-to-nearest adds in a fixed order (8 strided groups, then the 8 group
+ *               sums in order).  slots and tiles_per_slot are functions of the shape only; no atomics: bit-identical run to run and
+ *               from stream to stream.  m3d_conv3d_wgrad_f16x2_plan (host only; any output pointer may be NULL) reports them: `chain`
+ *               the longest MFMA chain of an accumulator, `folds` the fp32 operations behind it on the longest path of an output
+ *               (ceil(slots / 8) + 7 adds, 2 scale multiplies).
+ *   zeros       an all-zero operand (bound 0) gives an exactly zero gradient; an output none of whose products is non-zero is exactly 0
+ *               (the cut of 0 is 0 and voxels outside the volume are staged as zeros).
+ *   writes      d_grad_weight [cout,cin,3,3,3] and slots * cout * cin * 27 floats of d_ws (workspace_bytes; 16-byte aligned), nothing else.
+ * Refusals, before any pointer is followed or anything is launched.  M3D_EINVAL: a NULL pointer, a float pointer that is not 4-byte
+ * aligned, a d_ws that is not 16-byte aligned, a non-positive extent, ws_bytes below workspace_bytes.  M3D_EUNSUPPORTED: whatever
+ * `supported` rejects (workspace_bytes is then 0). */
+int m3d_conv3d_wgrad_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width);
+size_t m3d_conv3d_wgrad_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width);
+int m3d_conv3d_wgrad_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int* slots, int* tiles_per_slot,
+                                int* chain, int* folds);
+int m3d_conv3d_wgrad_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout, int depth,
+                           int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws, size_t ws_bytes,
+                           void* stream);
 
 /* Conv + scale/shift + ReLU + MaxPool3d(2,2) fused (DSN.py:58,60-61: pool1/pool2 directly follow a conv):
  * writes only the pooled tensor [batch,cout,D/2,H/2,W/2] (8x fewer output bytes, no separate pool pass) and,

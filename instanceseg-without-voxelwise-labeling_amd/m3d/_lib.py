@@ -25,6 +25,7 @@ SYMBOLS = [
     "m3d_reduce_min_workspace_bytes", "m3d_reduce_min", "m3d_reduce_min_multi_workspace_bytes", "m3d_reduce_min_multi",
     "m3d_otsu2d_workspace_bytes", "m3d_otsu2d_batch", "m3d_prm_quantize_u8", "m3d_roi_normalize", "m3d_prm_quantize_windows_u8", "m3d_prm_quantize_windows_compact_u8", "m3d_roi_normalize_ws", "m3d_roi_normalize_idx",
     "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wgrad", "m3d_conv3d_bias_grad",
+    "m3d_conv3d_wgrad_f16x2_supported", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_conv3d_wgrad_f16x2_plan", "m3d_conv3d_wgrad_f16x2",
     "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino_pack_weights", "m3d_conv3d_wino_forward", "m3d_conv3d_wino_forward_pool2",
     "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_pack_weights", "m3d_conv3d_wino2_forward", "m3d_conv3d_wino2_forward_pool2", "m3d_conv3d_wino2_forward_pool2_argmax", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_forward_ws", "m3d_conv3d_wino2_score", "m3d_conv3d_wino2_local_score", "m3d_conv3d_wino2_family", "m3d_conv3d_wino2_plan", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_wino2_local_forward_ws",
     "m3d_conv3d_stem_wino_packed_weight_bytes", "m3d_conv3d_stem_wino_pack_weights", "m3d_conv3d_stem_wino_forward", "m3d_conv3d_stem_wino_forward_bound",
@@ -101,7 +102,7 @@ def _load(path):
               "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
               "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes",
               "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes",
-              "m3d_mask_loss_workspace_bytes"):
+              "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

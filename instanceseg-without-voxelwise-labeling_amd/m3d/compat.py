@@ -22,7 +22,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import ops
+from . import conv_plan, ops
 
 
 # ----------------------------------------------------------------------------- RoIAlign3D
@@ -172,6 +172,25 @@ def _packed(weight, mode):
     return pack
 
 
+_conv_wgrad = conv_plan.WGRAD_FP32
+
+
+def set_conv_wgrad(mode):
+    """The weight-gradient kernel of the intercepted convs: "fp32" (the default; install() does not change it) keeps m3d_conv3d_wgrad;
+    "f16x2" takes m3d_conv3d_wgrad_f16x2 (the f16 matrix cores at fp32 accuracy, two operand sweeps included) for the layers
+    conv_plan.wgrad_kernel routes to it - every other layer (the 5^3 stem, k = 1, channel counts that are no multiple of 32) stays on the
+    fp32 kernel.  Forward, dgrad and the bias gradient are the same under both settings.  Returns the previous setting."""
+    global _conv_wgrad
+    if mode not in (conv_plan.WGRAD_FP32, conv_plan.WGRAD_F16X2):
+        raise ValueError("set_conv_wgrad(%r): 'fp32' or 'f16x2'" % (mode,))
+    prev, _conv_wgrad = _conv_wgrad, mode
+    return prev
+
+
+def get_conv_wgrad():
+    return _conv_wgrad
+
+
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -189,7 +208,14 @@ class _Conv3dFn(torch.autograd.Function):
                 gx = ops.conv3d_stem5_dgrad(gy, _packed(weight, STEM_DGRAD))
             else:
                 gx = _packed(weight, ops.W_DGRAD)(gy)
-        gw = ops.conv3d_wgrad(x, gy, weight.shape[2]) if ctx.needs_input_grad[1] else None
+        gw = None
+        if ctx.needs_input_grad[1]:
+            B, cin, D, H, W = x.shape
+            k = weight.shape[2]
+            if conv_plan.wgrad_kernel(B, cin, weight.shape[0], D, H, W, _conv_wgrad, k=k) == conv_plan.WGRAD_F16X2:
+                gw = ops.conv3d_wgrad_f16x2(x, gy)            # sweeps both operands for their bounds
+            else:
+                gw = ops.conv3d_wgrad(x, gy, k)
         gb = ops.conv3d_bias_grad(gy) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         return gx, gw, gb
 

@@ -22,6 +22,30 @@ DIRECT, STEM, ZW = "direct", "winograd F(2,5)x stem", "f16x2 F(2,3)z"         # 
 # its input by the input's operand bound (DetectorM3D._bound: left on the tensor by the launch that produced it, else one sweep)
 Plan = collections.namedtuple("Plan", "kind fused sweep")
 
+WGRAD_FP32, WGRAD_F16X2 = "fp32", "f16x2"            # wgrad kernels: m3d_conv3d_wgrad / m3d_conv3d_wgrad_f16x2 (+ its two bound sweeps)
+# The f16x2 weight gradient pays two sweeps of its operands, a workspace round trip of 27 cin cout floats per slot and a second launch:
+# fixed costs that a layer's work, batch x voxels x cin x cout products per tap, has to carry.  A layer is routed to it from the work of
+# the smallest layer measured to win by more than the spread (profiles/conv_wgrad_f16.txt: conv4a of the stride-8 body on one 128^3
+# volume, 16^3 x 128 x 256 = 2^27, 2.2 x); every measured layer above it wins too (1.3 x .. 2.2 x).  Below it nothing routes.
+WGRAD_F16X2_MIN_WORK = 1 << 27
+
+
+def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3):
+    """Which kernel computes the weight gradient of a stride-1 'same' conv layer with x [batch, cin, D, H, W]: WGRAD_F16X2 or WGRAD_FP32.
+    The one place that says so (m3d.compat asks it in backward).  mode: the caller's setting (compat.set_conv_wgrad): "fp32" keeps every
+    layer on m3d_conv3d_wgrad; "f16x2" moves the layers the f16x2 kernel takes (k = 3, cin and cout multiples of 32:
+    m3d_conv3d_wgrad_f16x2_supported) and was measured to win on by more than the spread of the measurement: layers of at least
+    WGRAD_F16X2_MIN_WORK products per tap.  A function of the shape only."""
+    if mode not in (WGRAD_FP32, WGRAD_F16X2):
+        raise ValueError("wgrad mode %r: 'fp32' or 'f16x2'" % (mode,))
+    if mode == WGRAD_FP32 or int(k) != 3:
+        return WGRAD_FP32
+    if not ops.conv3d_wgrad_f16x2_supported(batch, cin, cout, D, H, W):
+        return WGRAD_FP32
+    if int(batch) * int(D) * int(H) * int(W) * int(cin) * int(cout) < WGRAD_F16X2_MIN_WORK:
+        return WGRAD_FP32
+    return WGRAD_F16X2
+
 
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True):
     """The kernel for `layer` (a LayerConv: cin, cout, k, pool and the packs the switches M3D_WINO / M3D_CONV_F16 gave it) on an input

@@ -57,6 +57,8 @@ def main():
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--mask", choices=("spot",), default=None, help="also train the mask branch on spheres inscribed in the boxes")
+    ap.add_argument("--wgrad", choices=("fp32", "f16x2"), default="fp32",
+                    help="conv weight-gradient kernel (m3d.compat.set_conv_wgrad): f16x2 = the f16 matrix cores where conv_plan.wgrad_kernel routes a layer")
     a = ap.parse_args()
     import torch
     import m3d
@@ -65,6 +67,7 @@ def main():
     from train_rpn import build_model
     assert torch.cuda.is_available(), "train_detector needs a GPU"
     m3d.compat.install()
+    m3d.compat.set_conv_wgrad(a.wgrad)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
