@@ -260,6 +260,9 @@ int m3d_conv3d_stem_wino_forward(const float* d_in, const float* d_packed, float
 int m3d_conv3d_stem_wino_forward_bound(const float* d_in, const float* d_packed, float* d_out, int batch, int cout, int depth,
                                        int height, int width, const float* d_scale, const float* d_shift, int relu, int pool,
                                        float* d_out_max, void* stream);
+/* What the two calls above would launch for this shape: the planes per workgroup of the rows kernel (4, or 8 from a grid that fills
+ * the chip four times over), from the launch's own decision, and the launch's own refusals.  Host only: no launch, no device access. */
+int m3d_conv3d_stem_wino_plan(int batch, int cout, int depth, int height, int width, int pool, int* planes_out);
 
 /* Backward-weights and bias gradient of the same stride-1 "same" convolution (what autograd computes for the
  * F.conv3d calls of lib/prm/peak_backprop_3d.py:40-42 and every nn.Conv3d of lib/modeling/DSN.py:19-36 in training):

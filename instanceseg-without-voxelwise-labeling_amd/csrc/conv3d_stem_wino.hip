@@ -318,17 +318,30 @@ int launch_stem_rows(const float* in, const float* wr, float* out, int B, int co
   return m3d::check_launch("conv3d_stem_wino4");
 }
 
-template <bool POOL>
-int launch_stem_wino(const float* in, const float* wr, float* out, int B, int cout, int D, int H, int W, SEpi ep, hipStream_t st) {
+// Planes per workgroup of the rows kernel (4 / 8), the one decision behind the launch and m3d_conv3d_stem_wino_plan.  Option "tune_stem":
+// 4 / 8 = that many planes per workgroup; any other value: eight planes per workgroup while that still leaves every CU its two
+// workgroups twice over
+int stem_planes(int B, int cout, int D, int H, int W) {
   const int co_tiles = (cout + 31) / 32;
-  if (B > 65535) return M3D_EUNSUPPORTED;
-  // option "tune_stem": 4 / 8 = that many planes per workgroup; any other value: eight planes per workgroup while that still leaves
-  // every CU its two workgroups twice over
   const int tune = m3d::opt(m3d::OPT_TUNE_STEM);
   const long long wg8 = (long long)((W + TXo - 1) / TXo) * ((H + TY4 - 1) / TY4) * ((D + 7) / 8) * co_tiles * B;
-  const bool tz8 = tune == 8 || (tune != 4 && wg8 >= 2 * 512);
-  return tz8 ? launch_stem_rows<POOL, 8>(in, wr, out, B, cout, D, H, W, ep, st)
-             : launch_stem_rows<POOL, 4>(in, wr, out, B, cout, D, H, W, ep, st);
+  return (tune == 8 || (tune != 4 && wg8 >= 2 * 512)) ? 8 : 4;
+}
+
+// what m3d_conv3d_stem_wino_forward_bound refuses, in its order (launch and plan share it as well)
+int stem_check(int batch, int cout, int depth, int height, int width, int pool) {
+  if (batch <= 0 || cout <= 0 || depth <= 0 || height <= 0 || width <= 0) return M3D_EINVAL;
+  if ((size_t)depth * height * width * sizeof(float) >= 0x7FFFFFFFull) return M3D_EUNSUPPORTED;
+  if (width < 32) return M3D_EUNSUPPORTED;           // 64-wide tiles: narrower maps use the direct stem kernel
+  if (pool && (depth < 2 || height < 2 || width < 2)) return M3D_EINVAL;
+  if (batch > 65535) return M3D_EUNSUPPORTED;        // batch is a grid dimension
+  return M3D_OK;
+}
+
+template <bool POOL>
+int launch_stem_wino(const float* in, const float* wr, float* out, int B, int cout, int D, int H, int W, SEpi ep, hipStream_t st) {
+  return stem_planes(B, cout, D, H, W) == 8 ? launch_stem_rows<POOL, 8>(in, wr, out, B, cout, D, H, W, ep, st)
+                                            : launch_stem_rows<POOL, 4>(in, wr, out, B, cout, D, H, W, ep, st);
 }
 
 }  // namespace
@@ -356,10 +369,8 @@ M3D_API int m3d_conv3d_stem_wino_forward(const float* d_in, const float* d_packe
 M3D_API int m3d_conv3d_stem_wino_forward_bound(const float* d_in, const float* d_packed, float* d_out, int batch, int cout, int depth,
                                                int height, int width, const float* d_scale, const float* d_shift, int relu, int pool,
                                                float* d_out_max, void* stream) {
-  if (!d_in || !d_packed || !d_out || batch <= 0 || cout <= 0 || depth <= 0 || height <= 0 || width <= 0) return M3D_EINVAL;
-  if ((size_t)depth * height * width * sizeof(float) >= 0x7FFFFFFFull) return M3D_EUNSUPPORTED;
-  if (width < 32) return M3D_EUNSUPPORTED;           // 64-wide tiles: narrower maps use the direct stem kernel
-  if (pool && (depth < 2 || height < 2 || width < 2)) return M3D_EINVAL;
+  if (!d_in || !d_packed || !d_out) return M3D_EINVAL;
+  if (const int rc = stem_check(batch, cout, depth, height, width, pool); rc != M3D_OK) return rc;
   SEpi ep{d_scale, d_shift, relu, reinterpret_cast<unsigned*>(d_out_max)};
 #ifdef M3D_W2_STAMPS
   ep.stamps = g_stem_stamps;
@@ -367,4 +378,12 @@ M3D_API int m3d_conv3d_stem_wino_forward_bound(const float* d_in, const float* d
   hipStream_t st = m3d::as_stream(stream);
   return pool ? launch_stem_wino<true>(d_in, d_packed, d_out, batch, cout, depth, height, width, ep, st)
               : launch_stem_wino<false>(d_in, d_packed, d_out, batch, cout, depth, height, width, ep, st);
+}
+
+/* Planes per workgroup (4 / 8) of the rows kernel that m3d_conv3d_stem_wino_forward[_bound] would launch for this shape: the launch's own
+ * decision (stem_planes), and its refusals.  Host only: no launch, no device access. */
+M3D_API int m3d_conv3d_stem_wino_plan(int batch, int cout, int depth, int height, int width, int pool, int* planes_out) {
+  if (const int rc = stem_check(batch, cout, depth, height, width, pool); rc != M3D_OK) return rc;
+  if (planes_out) *planes_out = stem_planes(batch, cout, depth, height, width);
+  return M3D_OK;
 }

@@ -1609,6 +1609,26 @@ class WinoConv3d(object):
         return out
 
 
+def conv3d_wino2_plan(batch, cin, cout, depth, height, width, local=False):
+    """(family, tile id, K split) of the 2-D Winograd launch for this shape (m3d_conv3d_wino2_plan, host only): what WinoConv3d(two_d=True,
+    local=local) runs."""
+    f, t, k = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().m3d_conv3d_wino2_plan(int(bool(local)), int(batch), int(cin), int(cout), int(depth), int(height), int(width), C.byref(f),
+                                      C.byref(t), C.byref(k)), "conv3d_wino2_plan")
+    return f.value, t.value, k.value
+
+
+def conv3d_stem_wino_plan(batch, cout, depth, height, width, pool=False):
+    """planes per workgroup (4 / 8) of the stem's rows kernel for this shape (m3d_conv3d_stem_wino_plan, host only), or None where the
+    launch would return M3D_EUNSUPPORTED"""
+    p = C.c_int(-1)
+    rc = lib().m3d_conv3d_stem_wino_plan(int(batch), int(cout), int(depth), int(height), int(width), int(bool(pool)), C.byref(p))
+    if rc == -4:                                            # M3D_EUNSUPPORTED
+        return None
+    check(rc, "conv3d_stem_wino_plan")
+    return p.value
+
+
 class StemWinoConv3d(object):
     """conv1a (5x5x5, Cin = 1, stride 1, pad 2) through the Winograd F(2,5)-along-x MFMA kernel, optionally fused with
     MaxPool3d(2,2); maps >= 32 voxels wide (else use PackedConv3d)."""
@@ -1625,6 +1645,11 @@ class StemWinoConv3d(object):
     @staticmethod
     def supports(width):
         return width >= 32
+
+    def plan(self, shape, pool=False):
+        """planes per workgroup (4 / 8) of the kernel the library would launch for an input [B, 1, D, H, W] (m3d_conv3d_stem_wino_plan,
+        host only) - or None where the launch would return M3D_EUNSUPPORTED"""
+        return conv3d_stem_wino_plan(int(shape[0]), self.cout, *(int(v) for v in shape[-3:]), pool=pool)
 
     def _run(self, x, scale, shift, relu, pool, out, bound=False):
         _need_gpu(x)
