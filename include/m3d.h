@@ -481,6 +481,17 @@ int m3d_linear_f16x2_forward_bounds(const float* d_x, const void* d_packed, cons
                                     int relu, const float* d_x_bound, int x_bound_slots, float* d_out_bound, void* d_ws, size_t ws_bytes,
                                     void* stream);
 
+/* What the forward linear entry points launch for a shape (host only: nothing is launched, no device is touched).  kind 0:
+ * m3d_linear_forward, 1: m3d_linear_bf16x3_forward, 2: m3d_linear_bf16x3_w32_forward, 3: m3d_linear_f16x2_forward(_bounds).  The answer
+ * comes from the function the launch and its workspace query plan with, under the library's current options (tuning build: tune_fc_slices,
+ * tune_fc_slices_tail, tune_fc_x3_rows): tile_rows x tile_cols = the workgroup tile, which names the kernel instantiation (kind 0: 128 x
+ * 128; kinds 1 and 3: 128 x 128 or 256 x 128 on the packed planes; kinds 2 and 3: 256 x 256), slices = the K slices of every full row
+ * tile, and for kind 0 slices_tail = those of the ragged last row tile (one or two 32-row blocks, run by the kernel's tail path; 1 where
+ * there is none) and full_row_tiles = the row tiles in front of it; the other kinds have no tail path: slices_tail = slices and
+ * full_row_tiles = all row tiles.  Any output pointer may be NULL.  M, N, K < 1 or an unknown kind: M3D_EINVAL; K % 4 != 0 (kind 0) or
+ * K % 32 != 0 (the others): M3D_EUNSUPPORTED, as the launches. */
+int m3d_linear_plan(int kind, int M, int N, int K, int* tile_rows, int* tile_cols, int* slices, int* slices_tail, int* full_row_tiles);
+
 /* f-1 A/B: the fc1 GEMM with the RoIAlign gather in its A-operand loader - the [M, C * 343] RoIAlign output is never
  * written.  m3d_roi_align3d_tap_tables: the RoIs' per-axis sample tables (7^3 bins, sampling grid 2 - the shipped geometry) -> d_tab
  * (16 bytes x 3 axes x 14 samples per RoI) and d_roi_batch [num_rois]; m3d_linear_bf16x3_roi_forward: out[M, N] = act(RoIAlign3D(features,

@@ -1037,7 +1037,48 @@ Plan make_plan(int M, int N, int K) {
   return p;
 }
 
+// ---- one plan helper per entry point: its workspace query, its launch and m3d_linear_plan all ask the same function
+// 256 x 256 tiles (fc_x3b_gemm_kernel; wr = 8 marks them)
+X3Plan x3b_plan(int M, int N, int K) {
+  X3Plan p{8, (M + 255) / 256, (N + 255) / 256, x3b_slices(M, N, K), 0};
+  p.per_xcd = (p.mt * p.nt * p.slices + 7) / 8;
+  return p;
+}
+
+// 256 x 256 tiles (fc_x3b_gemm_kernel<1>) from 384 rows and 256 columns on: 64 KB of loads per chunk and workgroup for 48 MFMAs per wave,
+// against 48 KB for 24 on 256 x 128 - the f16x2 GEMM has half the matrix work of bf16x3 per byte, so the bytes per MFMA decide earlier.
+// Option tune_fc_x3_rows (tuning build): 128 / 256 force the 128-column kernels, 512 the 256 x 256 tiles.
+inline bool f16x2_big_tiles(int M, int N) {
+  const int w = m3d::opt(m3d::OPT_TUNE_FC_X3_ROWS);
+  if (w == 128 || w == 256) return false;
+  if (w == 512) return true;
+  return M >= 384 && N >= 256;
+}
+X3Plan f16x2_plan(int M, int N, int K) { return f16x2_big_tiles(M, N) ? x3b_plan(M, N, K) : x3_plan(M, N, K); }
+
 }  // namespace
+
+/* What the matching m3d_linear_*_forward launches for this shape under the library's current options (host only, launches nothing).
+ * kind 0: m3d_linear_forward, 1: m3d_linear_bf16x3_forward, 2: m3d_linear_bf16x3_w32_forward, 3: m3d_linear_f16x2_forward. */
+M3D_API int m3d_linear_plan(int kind, int M, int N, int K, int* tile_rows, int* tile_cols, int* slices, int* slices_tail,
+                            int* full_row_tiles) {
+  if (kind < 0 || kind > 3 || M <= 0 || N <= 0 || K <= 0) return M3D_EINVAL;
+  if (K % (kind == 0 ? 4 : 32) != 0) return M3D_EUNSUPPORTED;
+  int tr, tc, s, st, fm;
+  if (kind == 0) {
+    const Plan p = make_plan(M, N, K);
+    tr = BM; tc = BN; s = p.slices; st = p.slices_tail; fm = p.mt_full;
+  } else {
+    const X3Plan p = kind == 1 ? x3_plan(M, N, K) : (kind == 2 ? x3b_plan(M, N, K) : f16x2_plan(M, N, K));
+    tr = p.wr == 8 ? 256 : 64 * p.wr; tc = p.wr == 8 ? 256 : BN; s = st = p.slices; fm = p.mt;
+  }
+  if (tile_rows) *tile_rows = tr;
+  if (tile_cols) *tile_cols = tc;
+  if (slices) *slices = s;
+  if (slices_tail) *slices_tail = st;
+  if (full_row_tiles) *full_row_tiles = fm;
+  return M3D_OK;
+}
 
 M3D_API size_t m3d_linear_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
@@ -1154,22 +1195,9 @@ M3D_API int m3d_linear_f16x2_pack(const float* d_weight, int N, int K, void* d_p
   return m3d::check_launch("linear_f16x2_pack");
 }
 
-namespace {
-// 256 x 256 tiles (fc_x3b_gemm_kernel<1>) from 384 rows and 256 columns on: 64 KB of loads per chunk and workgroup for 48 MFMAs per wave,
-// against 48 KB for 24 on 256 x 128 - the f16x2 GEMM has half the matrix work of bf16x3 per byte, so the bytes per MFMA decide earlier.
-// Option tune_fc_x3_rows (tuning build): 128 / 256 force the 128-column kernels, 512 the 256 x 256 tiles.
-inline bool f16x2_big_tiles(int M, int N) {
-  const int w = m3d::opt(m3d::OPT_TUNE_FC_X3_ROWS);
-  if (w == 128 || w == 256) return false;
-  if (w == 512) return true;
-  return M >= 384 && N >= 256;
-}
-inline int f16x2_slices(int M, int N, int K) { return f16x2_big_tiles(M, N) ? x3b_slices(M, N, K) : x3_plan(M, N, K).slices; }
-}
-
 M3D_API size_t m3d_linear_f16x2_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0) return 0;
-  const int s = f16x2_slices(M, N, K);
+  const int s = f16x2_plan(M, N, K).slices;
   return (s > 1 ? (size_t)s * M * N * sizeof(float) : 0) + 256;    // split-K partials + the bound of |x| when the caller gives none
 }
 
@@ -1189,9 +1217,8 @@ M3D_API int m3d_linear_f16x2_forward_bounds(const float* d_x, const void* d_pack
   if (!d_x || !d_packed || !d_out || !d_ws) return M3D_EINVAL;
   if (d_x_bound && (x_bound_slots < 1 || x_bound_slots > 1024)) return M3D_EINVAL;
   if (K % 32 != 0 || ((uintptr_t)d_x & 15) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_ws & 15)) return M3D_EUNSUPPORTED;
-  const bool big = f16x2_big_tiles(M, N);
-  X3Plan p = x3_plan(M, N, K);
-  if (big) { p.wr = 8; p.mt = (M + 255) / 256; p.nt = (N + 255) / 256; p.slices = x3b_slices(M, N, K); p.per_xcd = (p.mt * p.nt * p.slices + 7) / 8; }
+  const X3Plan p = f16x2_plan(M, N, K);
+  const bool big = p.wr == 8;
   const int s = p.slices;
   const size_t part_bytes = s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
   if (ws_bytes < part_bytes + 256) return M3D_EWORKSPACE;
@@ -1286,7 +1313,7 @@ M3D_API int m3d_linear_bf16x3_roi_forward(const float* d_features, int batch, in
 /* 256 x 256 tiles on the nn.Linear weight itself (fp32, cut in the kernel): the variant for many rows, no packed copy */
 M3D_API size_t m3d_linear_bf16x3_w32_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0) return 0;
-  const int s = x3b_slices(M, N, K);
+  const int s = x3b_plan(M, N, K).slices;
   return s > 1 ? (size_t)s * M * N * sizeof(float) : 16;
 }
 
@@ -1296,10 +1323,10 @@ M3D_API int m3d_linear_bf16x3_w32_forward(const float* d_x, const float* d_weigh
   if (M == 0) return M3D_OK;
   if (!d_x || !d_weight || !d_out) return M3D_EINVAL;
   if (K % 32 != 0 || ((uintptr_t)d_x & 15) || ((uintptr_t)d_weight & 15)) return M3D_EUNSUPPORTED;
-  const int s = x3b_slices(M, N, K);
+  const X3Plan p = x3b_plan(M, N, K);
+  const int s = p.slices;
   if (s > 1 && (!d_ws || ws_bytes < (size_t)s * M * N * sizeof(float))) return M3D_EWORKSPACE;
-  FcX3Args a{d_x, (const u32x4*)d_weight, d_bias, d_out, (float*)d_ws, M, N, K, (M + 255) / 256, (N + 255) / 256, s, K / 32, relu, 0};
-  a.per_xcd = (a.mt * a.nt * s + 7) / 8;
+  FcX3Args a{d_x, (const u32x4*)d_weight, d_bias, d_out, (float*)d_ws, M, N, K, p.mt, p.nt, s, K / 32, relu, p.per_xcd};
   a.x_alias = 0; a.feat = nullptr; a.taps = nullptr; a.roi_batch = nullptr; a.fC = a.fS = a.fH = a.fW = 0;
   hipStream_t st = m3d::as_stream(stream);
   const size_t lds = sizeof(unsigned) * 6 * 256 * X3_RSW;

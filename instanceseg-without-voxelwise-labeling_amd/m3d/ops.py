@@ -12,7 +12,7 @@ from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage, MaskImag
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -574,6 +574,24 @@ def linear(x, weight, bias=None, relu=False, out=None):
     check(lib().m3d_linear_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), M, N, K, int(bool(relu)), _ptr(ws),
                                    C.c_size_t(wsb), _stream()), "linear_forward")
     return out
+
+
+LINEAR_KINDS = ("fp32", "bf16x3", "bf16x3_w32", "f16x2")
+
+
+def linear_plan(kind, M, N, K):
+    """What the forward linear launch of `kind` (0 `linear`, 1 SplitLinear's packed kernels, 2 its "w32" kernel, 3 SplitLinearF16; or the
+    name in LINEAR_KINDS) runs for x [M, K], weight [N, K] (m3d_linear_plan, host only): dict(tile_rows, tile_cols, slices, slices_tail,
+    full_row_tiles) - the workgroup tile names the kernel instantiation; slices_tail / full_row_tiles: the fp32 kernel's ragged last row
+    tile.  None where the launch would refuse the shape (K % 4, K % 32)."""
+    if isinstance(kind, str):
+        kind = LINEAR_KINDS.index(kind)
+    v = [C.c_int(0) for _ in range(5)]
+    rc = lib().m3d_linear_plan(int(kind), int(M), int(N), int(K), *[C.byref(a) for a in v])
+    if rc == -4:
+        return None
+    check(rc, "linear_plan")
+    return dict(zip(("tile_rows", "tile_cols", "slices", "slices_tail", "full_row_tiles"), (a.value for a in v)))
 
 
 def linear_dgrad(gy, weight, out=None):
