@@ -302,6 +302,20 @@ int m3d_conv3d_wgrad_f16x2_plan(int batch, int cin, int cout, int depth, int hei
 int m3d_conv3d_wgrad_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout, int depth,
                            int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws, size_t ws_bytes,
                            void* stream);
+/* One pass over a conv layer's output gradient d_gy [batch, cout, depth, height, width] (csrc/conv3d_gy_reduce.hip) for the bias gradient
+ * and the operand bound the f16x2 dgrad (m3d_conv3d_zw_forward on an m3d_conv3d_zw_pack_dgrad pack) and m3d_conv3d_wgrad_f16x2 take:
+ *   d_grad_bias  (or NULL) [cout]: gb[c] = fp32(S), S = the sum of d_gy[:, c] taken in fp64 over spans of one (image, channel) slab whose
+ *                boundaries depend on the shape only, a fixed order inside a span and an ascending (image, span) loop over a channel's
+ *                partials; one rounding to fp32.  No floating-point atomics: bit-identical run to run and stream to stream.
+ *                |gb - S_exact| <= 2^-24 |S_exact| + n 2^-53 sum |gy|, n = batch depth height width.
+ *   d_gy_max     m3d_conv3d_zw_slots() floats, written here (no need to zero them): the LARGEST equals max |d_gy| exactly (what
+ *                m3d_conv3d_zw_bound_of gives); a non-finite value in d_gy makes it non-finite.
+ * Workspace: the convention of m3d_bn_*: with d_ws == NULL the call launches nothing and stores the bytes it needs in *ws_bytes; otherwise
+ * *ws_bytes is the capacity of d_ws (8-byte aligned; M3D_EWORKSPACE if too small).  Refusals, before any pointer is followed: M3D_EINVAL for
+ * a non-positive extent, a NULL or misaligned d_gy / d_gy_max, a misaligned d_grad_bias, a NULL ws_bytes; M3D_EUNSUPPORTED for a slab of 2^31
+ * elements or more, or 2^24 spans (16384 elements of one slab each) or more. */
+int m3d_conv3d_gy_reduce(const float* d_gy, int batch, int cout, int depth, int height, int width, float* d_grad_bias, float* d_gy_max,
+                         void* d_ws, size_t* ws_bytes, void* stream);
 
 /* Conv + scale/shift + ReLU + MaxPool3d(2,2) fused (DSN.py:58,60-61: pool1/pool2 directly follow a conv):
  * writes only the pooled tensor [batch,cout,D/2,H/2,W/2] (8x fewer output bytes, no separate pool pass) and,
@@ -691,6 +705,12 @@ long long m3d_conv3d_x3_launch_units(int batch, int cin, int cout, int depth, in
 int m3d_conv3d_zw_supported(int cin, int cout, int depth, int height, int width, int pool);
 size_t m3d_conv3d_zw_packed_bytes(int cin, int cout);
 int m3d_conv3d_zw_pack(const float* d_weight, int cin, int cout, void* d_packed, void* stream);
+/* The pack of the BACKWARD-DATA conv of a layer, straight from the layer's own parameter d_weight [cout, cin, 3, 3, 3] (the FORWARD
+ * layout): taps flipped and channel roles swapped while packing, so the pack's input channels are `cout` and its output channels `cin`.
+ * d_packed: m3d_conv3d_zw_packed_bytes(cout, cin) bytes, equal to m3d_conv3d_zw_pack of the flipped, transposed, contiguous copy
+ * (w.flip(2, 3, 4).transpose(0, 1)) byte for byte, the largest magnitude behind the fragments included.  M3D_EINVAL, before any pointer
+ * is followed: a NULL pointer, a non-positive count, cout % 16 != 0. */
+int m3d_conv3d_zw_pack_dgrad(const float* d_weight, int cin, int cout, void* d_packed, void* stream);
 int m3d_conv3d_zw_slots(void);
 /* Workgroup units of an m3d_conv3d_zw_forward launch on this shape ((64 output channels) x (32 x 4 x 2 voxels, or 16 x 8 x 2 on maps
  * narrower than 24) per unit): the library's own tile choice, for callers that choose between this kernel and the fp32 ones by how well a

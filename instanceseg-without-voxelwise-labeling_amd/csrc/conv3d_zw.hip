@@ -85,6 +85,10 @@ __device__ __forceinline__ void col_xy16(int c, int* x, int* y) {
 }
 
 // packed[cout group 64][step = chunk * 9 + dy * 3 + dx][point][block][hi / lo][k half][row 32] <- weight [cout][cin][3][3][3] fp32
+// DGRAD: `w` is the FORWARD conv's parameter [cin][cout][3][3][3] as it lies in memory and the pack is the backward-data conv's (cin / cout
+// are the PACK's: the forward layer's cout / cin): element (co, ci, dz, dy, dx) of the packed conv is w[ci][co][2 - dz][2 - dy][2 - dx] -
+// what packing w.flip(2, 3, 4).transpose(0, 1).contiguous() reads, without that copy.
+template <bool DGRAD>
 __global__ __launch_bounds__(256) void zw_pack_kernel(const float* __restrict__ w, int cin, int cout, u32x4* __restrict__ packed,
                                                       const float* __restrict__ wamax) {
   float sw, inv;
@@ -105,8 +109,9 @@ __global__ __launch_bounds__(256) void zw_pack_kernel(const float* __restrict__ 
       for (int u = 0; u < 2; ++u) {
         float v = 0.f;
         if (co < cout) {
-          const float* g = w + ((size_t)co * cin + ch * 16 + 8 * kh + 2 * j + u) * 27 + tap;
-          const double g0 = g[0], g1 = g[9], g2 = g[18];
+          const int ci = ch * 16 + 8 * kh + 2 * j + u;
+          const float* g = DGRAD ? w + ((size_t)ci * cout + co) * 27 + (8 - tap) : w + ((size_t)co * cin + ci) * 27 + tap;
+          const double g0 = g[DGRAD ? 18 : 0], g1 = g[9], g2 = g[DGRAD ? 0 : 18];
           const double t = point == 0 ? g0 : point == 1 ? 0.5 * (g0 + g1 + g2) : point == 2 ? 0.5 * (g0 - g1 + g2) : g2;
           v = (float)t * sw;
         }
@@ -665,8 +670,18 @@ M3D_API int m3d_conv3d_zw_pack(const float* d_weight, int cin, int cout, void* d
   if (!d_weight || !d_packed || cin <= 0 || cout <= 0 || cin % 16 != 0) return M3D_EINVAL;
   float* wamax = reinterpret_cast<float*>(static_cast<char*>(d_packed) + zw_plane_bytes(cin, cout));
   if (const int rc = m3d_absmax(d_weight, (long long)cout * cin * 27, wamax, stream)) return rc;
-  hipLaunchKernelGGL(zw_pack_kernel, dim3(1024), dim3(256), 0, m3d::as_stream(stream), d_weight, cin, cout, (u32x4*)d_packed, (const float*)wamax);
+  hipLaunchKernelGGL(zw_pack_kernel<false>, dim3(1024), dim3(256), 0, m3d::as_stream(stream), d_weight, cin, cout, (u32x4*)d_packed, (const float*)wamax);
   return m3d::check_launch("conv3d_zw_pack");
+}
+
+/* The pack of the BACKWARD-DATA conv of a forward layer [cout, cin, 3, 3, 3], straight from the parameter: m3d_conv3d_zw_pack of
+ * w.flip(2, 3, 4).transpose(0, 1).contiguous() byte for byte (the largest magnitude is the same set's), m3d_conv3d_zw_packed_bytes(cout, cin) bytes. */
+M3D_API int m3d_conv3d_zw_pack_dgrad(const float* d_weight, int cin, int cout, void* d_packed, void* stream) {
+  if (!d_weight || !d_packed || cin <= 0 || cout <= 0 || cout % 16 != 0) return M3D_EINVAL;
+  float* wamax = reinterpret_cast<float*>(static_cast<char*>(d_packed) + zw_plane_bytes(cout, cin));
+  if (const int rc = m3d_absmax(d_weight, (long long)cout * cin * 27, wamax, stream)) return rc;
+  hipLaunchKernelGGL(zw_pack_kernel<true>, dim3(1024), dim3(256), 0, m3d::as_stream(stream), d_weight, cout, cin, (u32x4*)d_packed, (const float*)wamax);
+  return m3d::check_launch("conv3d_zw_pack_dgrad");
 }
 
 M3D_API int m3d_conv3d_zw_slots(void) { return ZW_SLOTS; }

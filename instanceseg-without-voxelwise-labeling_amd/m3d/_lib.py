@@ -40,6 +40,7 @@ SYMBOLS = [
     "m3d_train_sample",
     "m3d_linear_dgrad_workspace_bytes", "m3d_linear_dgrad", "m3d_linear_wgrad_workspace_bytes", "m3d_linear_wgrad",
     "m3d_mask_targets", "m3d_mask_loss_workspace_bytes", "m3d_mask_loss",
+    "m3d_conv3d_zw_pack_dgrad", "m3d_conv3d_gy_reduce",
 ]
 
 

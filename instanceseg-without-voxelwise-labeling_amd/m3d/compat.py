@@ -147,10 +147,15 @@ class _Legacy2D(object):
 _orig_conv3d = None
 _pack_cache = {}          # (id(parameter), mode) -> (weakref to the parameter, _version, data_ptr, pack)
 STEM_DGRAD = "stem-dgrad"  # pseudo-mode: tap-flipped [C,125] weights of the 5^3 / Cin = 1 stem's backward-data
+ZW_PLAIN, ZW_DGRAD = "zw-plain", "zw-dgrad"     # pseudo-modes: the f16x2 kernel's packs of the forward / backward-data conv (set_conv_train)
 
 
 def _make_pack(weight, mode):
     w = weight.detach()
+    if mode == ZW_PLAIN:
+        return ops.ZwConv3d(w)
+    if mode == ZW_DGRAD:
+        return ops.ZwConv3d.dgrad_of(w)
     return ops.conv3d_stem5_dgrad_weights(w) if mode == STEM_DGRAD else ops.PackedConv3d(w, mode)
 
 
@@ -191,32 +196,92 @@ def get_conv_wgrad():
     return _conv_wgrad
 
 
+_conv_train = conv_plan.TRAIN_FP32
+_conv_train_min_units = None          # None: conv_plan.ZW_MIN_UNITS
+
+
+def set_conv_train(mode, min_units=None):
+    """The forward and backward-data kernels of the intercepted convs: "fp32" (the default; install() does not change it) keeps the direct
+    fp32 MFMA kernel for both; "f16x2" takes m3d_conv3d_zw_forward (the f16 matrix cores at fp32 accuracy, Winograd F(2,3) along z) for the
+    layers and directions conv_plan.train_conv_kernel routes to it - every other layer (the 5^3 stem, k = 1, input channels that are no
+    multiple of 16, small maps, fewer than 32 output channels) stays on the fp32 kernel.  In mode "f16x2" the bias gradient of
+    every layer comes from m3d_conv3d_gy_reduce (fp64 sums, one rounding), whichever kernels the layer routes to, and that one pass over gy
+    also gives the operand bound the f16x2 dgrad and the f16x2 wgrad (set_conv_wgrad) share; the forward sweeps x once and keeps the bound
+    for the wgrad.  min_units: the routing threshold in launch units (None: conv_plan.ZW_MIN_UNITS; 0 routes every supported layer - tests
+    and A/B runs; a call without it puts the default back).  Returns the previous mode.
+    As set_conv_wgrad("f16x2") already implies for its kernel: with a non-finite value in an operand the operand's bound is non-finite and
+    the WHOLE result is, not only the elements the fp32 kernel's element-wise propagation would reach; Solver(stats=True).nonfinite is
+    the guard."""
+    global _conv_train, _conv_train_min_units
+    if mode not in (conv_plan.TRAIN_FP32, conv_plan.TRAIN_F16X2):
+        raise ValueError("set_conv_train(%r): 'fp32' or 'f16x2'" % (mode,))
+    if min_units is not None and int(min_units) < 0:
+        raise ValueError("set_conv_train(min_units=%r): None or a count >= 0" % (min_units,))
+    prev = _conv_train
+    _conv_train, _conv_train_min_units = mode, (None if min_units is None else int(min_units))
+    return prev
+
+
+def get_conv_train():
+    return _conv_train
+
+
+def _train_kernel(direction, setting, xshape, wshape):
+    """conv_plan.train_conv_kernel for a layer with weight `wshape` on a map `xshape` under setting = (mode, min_units)"""
+    mode, mu = setting
+    if mode == conv_plan.TRAIN_FP32:
+        return conv_plan.TRAIN_FP32
+    B, _, D, H, W = xshape
+    return conv_plan.train_conv_kernel(direction, B, wshape[1], wshape[0], D, H, W, mode,
+                                       min_units=conv_plan.ZW_MIN_UNITS if mu is None else mu, k=wshape[2])
+
+
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(weight, x if weight.requires_grad else None)
         ctx.has_bias = bias is not None
-        return _packed(weight, ops.W_PLAIN)(x, shift=bias.detach().contiguous() if bias is not None else None)
+        ctx.train = (_conv_train, _conv_train_min_units)      # the backward of this call follows the setting its forward ran under
+        ctx.x_max = None
+        shift = bias.detach().contiguous() if bias is not None else None
+        if _train_kernel("forward", ctx.train, x.shape, weight.shape) == conv_plan.TRAIN_F16X2:
+            ctx.x_max = ops.ZwConv3d.bound_of(x)
+            return _packed(weight, ZW_PLAIN)(x, ctx.x_max, shift=shift, out_max=False)[0]
+        return _packed(weight, ops.W_PLAIN)(x, shift=shift)
 
     @staticmethod
     def backward(ctx, gy):
         weight, x = ctx.saved_tensors
         gy = gy.contiguous()
+        f16 = ctx.train[0] == conv_plan.TRAIN_F16X2
+        k = weight.shape[2]
+        B, _, D, H, W = gy.shape
+        cout, cin = weight.shape[0], weight.shape[1]
+        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
+        dgrad_zw = f16 and ctx.needs_input_grad[0] and _train_kernel("dgrad", ctx.train, gy.shape, weight.shape) == conv_plan.TRAIN_F16X2
+        wgrad_zw = ctx.needs_input_grad[1] and conv_plan.wgrad_kernel(B, cin, cout, D, H, W, _conv_wgrad, k=k) == conv_plan.WGRAD_F16X2
+        gb = gy_max = None
+        if f16 and (dgrad_zw or wgrad_zw or want_gb):
+            # one pass over gy: the bias gradient and the bound both f16x2 kernels scale gy by.  In f16x2 mode gb ALWAYS comes from here, so
+            # that a change of route (another batch size, min_units) never changes gb
+            gb, gy_max = ops.conv3d_gy_reduce(gy, bias=want_gb)
         gx = None
         if ctx.needs_input_grad[0]:
-            if weight.shape[2] == 5:          # conv1a: one input channel -> VALU dgrad kernel (csrc/prm.hip)
+            if k == 5:          # conv1a: one input channel -> VALU dgrad kernel (csrc/prm.hip)
                 gx = ops.conv3d_stem5_dgrad(gy, _packed(weight, STEM_DGRAD))
+            elif dgrad_zw:
+                gx = _packed(weight, ZW_DGRAD)(gy, gy_max, out_max=False)[0]
             else:
                 gx = _packed(weight, ops.W_DGRAD)(gy)
         gw = None
         if ctx.needs_input_grad[1]:
-            B, cin, D, H, W = x.shape
-            k = weight.shape[2]
-            if conv_plan.wgrad_kernel(B, cin, weight.shape[0], D, H, W, _conv_wgrad, k=k) == conv_plan.WGRAD_F16X2:
-                gw = ops.conv3d_wgrad_f16x2(x, gy)            # sweeps both operands for their bounds
+            if wgrad_zw:
+                # mode "fp32": sweeps both operands for their bounds; "f16x2": x's bound from the forward (if it ran on f16x2), gy's shared
+                gw = ops.conv3d_wgrad_f16x2(x, gy, ctx.x_max, gy_max)
             else:
                 gw = ops.conv3d_wgrad(x, gy, k)
-        gb = ops.conv3d_bias_grad(gy) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        if want_gb and gb is None:
+            gb = ops.conv3d_bias_grad(gy)
         return gx, gw, gb
 
 

@@ -47,6 +47,44 @@ def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3):
     return WGRAD_F16X2
 
 
+TRAIN_FP32, TRAIN_F16X2 = "fp32", "f16x2"            # forward / dgrad kernels of a training conv: the direct fp32 MFMA kernel / conv3d_zw.hip
+# Output channels of the launched conv (forward: cout; dgrad: the forward cin) from which a direction routes to the f16x2 kernel.  Its
+# units are 64 channels wide: with 32 output channels half of every unit's matrix work is spent on channels that do not exist.  The PRM
+# engine keeps such a dgrad off the kernel (PRMEngine._dgrad_zw: >= 64, measured against the fp32 Winograd strips); against the DIRECT
+# fp32 kernel of the training path the half-idle 64 -> 32 launch (conv2a's dgrad) still won 3.5 x .. 4.6 x on every map that fills the
+# chip (profiles/conv_train_f16.txt), so 32 is admitted in both directions.  Nothing narrower was measured: it stays on fp32.
+# The unit threshold is ZW_MIN_UNITS as for the detection path: every measured launch of 256 units or more won (2.2 x .. 5.6 x with the
+# per-step pack inside the window), the two of 128 units won too (2.1 x, 2.3 x), those of 64 were mixed (0.89 x .. 2.9 x), none of 16 or fewer was faster than 1.03 x.
+TRAIN_F16X2_MIN_COUT = {"forward": 32, "dgrad": 32}
+
+
+def train_conv_kernel(direction, batch, cin, cout, D, H, W, mode, min_units=ZW_MIN_UNITS, k=3):
+    """Which kernel runs the forward ("forward") or the backward-data ("dgrad") conv of a stride-1 'same' training layer with weight
+    [cout, cin, k, k, k] on a map [batch, ., D, H, W]: TRAIN_F16X2 (m3d_conv3d_zw_forward; dgrad on an m3d_conv3d_zw_pack_dgrad pack) or
+    TRAIN_FP32 (the direct fp32 MFMA kernel, ops.PackedConv3d).  The one place that says so (m3d.compat asks it, as it asks wgrad_kernel).
+    mode: the caller's setting (compat.set_conv_train).  TRAIN_FP32 for mode "fp32", k != 3, channel counts or a map the zw kernel has no
+    configuration for (m3d_conv3d_zw_supported on the launched conv: a dgrad swaps the channel roles), a batch item of ITEM_LIMIT bytes
+    or more, fewer launched output channels than TRAIN_F16X2_MIN_COUT[direction], fewer than min_units launch units.  A function of the
+    shape only."""
+    if direction not in TRAIN_F16X2_MIN_COUT:
+        raise ValueError("direction %r: 'forward' or 'dgrad'" % (direction,))
+    if mode not in (TRAIN_FP32, TRAIN_F16X2):
+        raise ValueError("conv train mode %r: 'fp32' or 'f16x2'" % (mode,))
+    if mode == TRAIN_FP32 or int(k) != 3:
+        return TRAIN_FP32
+    batch, D, H, W = int(batch), int(D), int(H), int(W)
+    ci, co = (int(cin), int(cout)) if direction == "forward" else (int(cout), int(cin))     # of the conv that is launched
+    L = ops.lib()
+    if batch < 1 or ci < 1 or co < 1 or not L.m3d_conv3d_zw_supported(ci, co, D, H, W, 0):
+        return TRAIN_FP32
+    # (m3d_conv3d_zw_forward itself refuses an item from 0x7FFFFF00 bytes: the 255 bytes below ITEM_LIMIT stay on fp32 too)
+    if ci * D * H * W * 4 >= ITEM_LIMIT - 0xFF or co < TRAIN_F16X2_MIN_COUT[direction]:
+        return TRAIN_FP32
+    if L.m3d_conv3d_zw_launch_units(batch, ci, co, D, H, W) < int(min_units):
+        return TRAIN_FP32
+    return TRAIN_F16X2
+
+
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True):
     """The kernel for `layer` (a LayerConv: cin, cout, k, pool and the packs the switches M3D_WINO / M3D_CONV_F16 gave it) on an input
     [B, cin, D, H, W], shape = (B, D, H, W).  Host queries of the library only.  The caller's needs:

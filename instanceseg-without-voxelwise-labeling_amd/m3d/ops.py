@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1406,6 +1406,21 @@ class ZwConv3d(object):
         self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
         check(lib().m3d_conv3d_zw_pack(_ptr(w), self.cin, self.cout, _ptr(self.packed), _stream()), "conv3d_zw_pack")
 
+    @classmethod
+    def dgrad_of(cls, weight):
+        """The BACKWARD-DATA conv of a forward layer `weight` [cout, cin, 3, 3, 3] (cout % 16 == 0) as a ZwConv3d: cin = the layer's cout,
+        cout = the layer's cin.  The pack comes straight from the parameter's own layout (m3d_conv3d_zw_pack_dgrad): the bytes of
+        ZwConv3d(weight.flip(2, 3, 4).transpose(0, 1).contiguous()).packed without that copy."""
+        _need_gpu(weight)
+        w = _f32c(weight)
+        assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and int(w.shape[0]) % 16 == 0
+        self = cls.__new__(cls)
+        self.cout, self.cin = int(w.shape[1]), int(w.shape[0])
+        nbytes = lib().m3d_conv3d_zw_packed_bytes(self.cin, self.cout)
+        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        check(lib().m3d_conv3d_zw_pack_dgrad(_ptr(w), self.cout, self.cin, _ptr(self.packed), _stream()), "conv3d_zw_pack_dgrad")
+        return self
+
     def supports(self, shape, pool=False):
         D, H, W = (int(v) for v in shape[-3:])
         return bool(lib().m3d_conv3d_zw_supported(self.cin, self.cout, D, H, W, int(bool(pool))))
@@ -1751,6 +1766,24 @@ def conv3d_bias_grad(grad_out):
     db = torch.empty((cout,), dtype=torch.float32, device=grad_out.device)
     check(lib().m3d_conv3d_bias_grad(_ptr(grad_out), _ptr(db), B, cout, D, H, W, _stream()), "conv3d_bias_grad")
     return db
+
+
+def conv3d_gy_reduce(grad_out, bias=True):
+    """(gb or None, gy_max) from ONE pass over grad_out [B, cout, D, H, W] (m3d_conv3d_gy_reduce): gb [cout] = fp32 of the fp64 sum over
+    (B, D, H, W) (fixed order: bit-identical run to run), gy_max [ZwConv3d.SLOTS] device floats whose largest is max |grad_out| exactly -
+    the operand bound ZwConv3d.dgrad_of(w)(grad_out, gy_max) and conv3d_wgrad_f16x2(.., gy_max=) take.  No host read."""
+    _need_gpu(grad_out)
+    grad_out = _f32c(grad_out)
+    B, cout, D, H, W = (int(v) for v in grad_out.shape)
+    gb = torch.empty((cout,), dtype=torch.float32, device=grad_out.device) if bias else None
+    gy_max = torch.empty((ZwConv3d.SLOTS,), dtype=torch.float32, device=grad_out.device)
+    wsb = C.c_size_t(0)
+    check(lib().m3d_conv3d_gy_reduce(None, B, cout, D, H, W, None, None, None, C.byref(wsb), None), "conv3d_gy_reduce")
+    ws = torch.empty((max(wsb.value, 8),), dtype=torch.uint8, device=grad_out.device)
+    wsb = C.c_size_t(ws.numel())
+    check(lib().m3d_conv3d_gy_reduce(_ptr(grad_out), B, cout, D, H, W, _ptr(gb) if bias else None, _ptr(gy_max), _ptr(ws), C.byref(wsb),
+                                     _stream()), "conv3d_gy_reduce")
+    return gb, gy_max
 
 
 # ------------------------------------------------------------------ volume pre-filters (binarization_nuclei.py:44-45)

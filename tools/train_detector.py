@@ -59,6 +59,8 @@ def main():
     ap.add_argument("--mask", choices=("spot",), default=None, help="also train the mask branch on spheres inscribed in the boxes")
     ap.add_argument("--wgrad", choices=("fp32", "f16x2"), default="fp32",
                     help="conv weight-gradient kernel (m3d.compat.set_conv_wgrad): f16x2 = the f16 matrix cores where conv_plan.wgrad_kernel routes a layer")
+    ap.add_argument("--conv", choices=("fp32", "f16x2"), default="fp32",
+                    help="conv forward / backward-data kernel (m3d.compat.set_conv_train): f16x2 = the f16 matrix cores where conv_plan.train_conv_kernel routes a layer")
     a = ap.parse_args()
     import torch
     import m3d
@@ -68,6 +70,7 @@ def main():
     assert torch.cuda.is_available(), "train_detector needs a GPU"
     m3d.compat.install()
     m3d.compat.set_conv_wgrad(a.wgrad)
+    m3d.compat.set_conv_train(a.conv)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
