@@ -1223,6 +1223,48 @@ size_t m3d_linear_wgrad_workspace_bytes(int M, int N, int K);
 int m3d_linear_wgrad(const float* d_gy, const float* d_x, float* d_gw, float* d_gb, int M, int N, int K, void* d_ws, size_t ws_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Peak stimulation (peak_stim.hip; DESIGN, "Peak stimulation"): lib/prm/peak_stimulation_3d.py:6-52 on a response map
+ * d_x fp32 [B,C,S,H,W], contiguous; win odd, o = win / 2.
+ *   peak map     voxel v is a peak iff it is the arg-max of its window [z-o,z+o] x [y-o,y+o] x [x-o,x+o] clipped to the volume; ties go
+ *                to the first maximum in raster order (z outer, x inner); a NaN beats everything and among NaNs the last in raster order
+ *                wins (what max_pool3d + `indices == element_map` give, :15-25).  -inf is an ordinary, smallest value (the reference's
+ *                answer there depends on its -inf padding).  An all-equal volume has one peak per (b,c), at (0,0,0).
+ *   filter       filter_kind != NONE: a peak must also satisfy x >= d_thresh[b,c] (false for a NaN on either side, :29).  MEDIAN =
+ *                torch.median's lower median (rank (n-1)/2 ascending of the n = S H W values, NaN if the channel holds a NaN, by a radix
+ *                select; of -0.0 / +0.0 it returns +0.0); MEAN = the fp64 sum in a fixed order / n, rounded to fp32 once; MAX (NaN if
+ *                the channel holds one); CONST = filter_value; TENSOR = d_thresh_in [B*C] as given.  d_thresh [B*C] is always written
+ *                (-inf for NONE).
+ *   peak list    d_peaks int32 [cap,5] = rows (b,c,z,y,x) in raster order over the whole tensor (torch.nonzero's order, :31); *d_num
+ *                (and *h_num, a device-accessible pinned HOST mirror written by the same launch, may be NULL - as
+ *                m3d_prm_select_peaks has) = the true count, even above cap; rows beyond cap are not written.  cap may be 0.
+ *   aggregation  d_agg [B*C] (may be NULL) = (float)(sum of x * peak over the channel / count) (:38-39): fp64, the 1024-voxel raster
+ *                chunks of a channel each summed by a fixed tree and the chunks added in raster order; count == 0 gives NaN; a NaN or
+ *                inf voxel that is no peak gives NaN as well (0 * NaN), as in the reference.
+ *   d_peak_map   uint8 [B,C,S,H,W] (may be NULL: the map then lives in the workspace): 1 at every peak that passed the filter.
+ * Five small launches, no global atomics, no host synchronisation; bit-identical run to run.
+ * m3d_peak_stimulation3d_backward (:43-48): d_gx [B,C,S,H,W] = d_peak_map * d_gy[b,c], every element written.
+ * Refusals, before any device pointer is followed or anything is launched.  M3D_EINVAL: win even or < 1, an unknown filter_kind, B or
+ * C < 0, S, H or W < 1, cap < 0, a NULL required pointer (d_x, d_num, d_thresh, d_ws; d_peaks with cap > 0; d_thresh_in with TENSOR),
+ * ws_bytes below m3d_peak_stimulation3d_workspace_bytes.  M3D_EUNSUPPORTED: win > 9, S H W >= 2^31, more tiles or chunks than one grid
+ * dimension holds.  B * C == 0: nothing is launched or written.  The workspace size is 0 for arguments the call would refuse.
+ * ------------------------------------------------------------------------------------------------------- */
+#define M3D_PEAK_FILTER_NONE 0
+#define M3D_PEAK_FILTER_MEDIAN 1
+#define M3D_PEAK_FILTER_MEAN 2
+#define M3D_PEAK_FILTER_MAX 3
+#define M3D_PEAK_FILTER_CONST 4
+#define M3D_PEAK_FILTER_TENSOR 5
+/* peak_stimulation_3d.py:6-52: bytes of d_ws for one m3d_peak_stimulation3d call of these dimensions */
+size_t m3d_peak_stimulation3d_workspace_bytes(int B, int C, int S, int H, int W, int win);
+/* peak_stimulation_3d.py:6-52 (forward, :8-41) */
+int m3d_peak_stimulation3d(const float* d_x, int B, int C, int S, int H, int W, int win, int filter_kind, float filter_value,
+                           const float* d_thresh_in, uint8_t* d_peak_map, int32_t* d_peaks, int cap, int64_t* d_num, int64_t* h_num,
+                           float* d_thresh, float* d_agg, void* d_ws, size_t ws_bytes, void* stream);
+/* peak_stimulation_3d.py:6-52 (backward, :43-48) */
+int m3d_peak_stimulation3d_backward(const uint8_t* d_peak_map, const float* d_gy, int B, int C, int S, int H, int W, float* d_gx,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,3 +10,4 @@ from .train import (RpnTrainCfg, RpnTargets, rpn_targets, rpn_losses, BoxHeadTra
                     MaskHead)
 from .solver import SolverCfg, Solver, save_ckpt, load_ckpt  # noqa: E402,F401
 from .data import SampleCfg, Annotations, read_soma_annotations, read_nuclei_annotations, epoch_order, TrainSet, Batch  # noqa: E402,F401
+from .peaks import peak_stimulation_3d, peak_stimulation_3d_dev, PeakStimulation  # noqa: E402,F401

@@ -4,7 +4,8 @@
                             (lib/modeling/model_builder.py:140-240, eval branch :228-238)
   PeakResponseMapping_3d    model(data=[T], im_info=[T], im_scale=[1.0]) ->
                             (None, class_response_maps [1,A,s,h,w], valid_peak_list int64 [P,5], peak_response_maps
-                            [P,S,H,W], dets float64 [P,7])   or   (None,)*5
+                            [P,S,H,W], dets float64 [P,7])   or   (None,)*5;
+                            with enable_peak_stimulation=True, enable_peak_backprop=False: (aggregation [B,A], class_response_maps)
                             (lib/prm/peak_response_mapping_3d.py:85-193; driver tools/infer_simple.py:217-226)
   im_detect_bbox / im_detect_all   lib/core/test.py:194-263 / :54-177 with the reference signatures and NumPy returns
 
@@ -128,8 +129,28 @@ class PeakResponseMapping_3d(Generalized_RCNN):
 
     def __init__(self, state_dict, cfg, device="cuda", **kargs):
         super().__init__(state_dict, cfg, device)
-        if kargs.get("enable_peak_stimulation", False):
-            raise NotImplementedError("peak stimulation is disabled by default in the reference (:25) and not on the path")
+        # the reference's kwargs (:25-43)
+        self.enable_peak_stimulation = bool(kargs.get("enable_peak_stimulation", False))
+        self.enable_peak_backprop = bool(kargs.get("enable_peak_backprop", True))
+        self.win_size = kargs.get("win_size", 3)
+        self.sub_pixel_locating_factor = kargs.get("sub_pixel_locating_factor", 1)
+        self.filter_type = kargs.get("filter_type", "median")
+        if self.filter_type in ("median", "mean", "max"):                                   # :33-39, on the library's own kernels
+            self.peak_filter = self.filter_type
+        elif isinstance(self.filter_type, (int, float)) and not isinstance(self.filter_type, bool):
+            self.peak_filter = float(self.filter_type)                                      # :40-41
+        else:
+            self.peak_filter = None                                                         # :42-43
+        if self.enable_peak_stimulation:
+            if self.sub_pixel_locating_factor > 1:
+                raise NotImplementedError("sub_pixel_locating_factor > 1: the reference up-samples the 5-D class response maps with "
+                                          "mode='bilinear' (:132), which raises for a 5-D tensor - there is no behaviour to reproduce")
+            if self.enable_peak_backprop:
+                raise NotImplementedError(
+                    "enable_peak_stimulation with enable_peak_backprop: the reference's loop (:157-172) pairs the idx-th detection's "
+                    "score and box with the idx-th STIMULATED peak - unrelated rows of two different lists.  To back-propagate from "
+                    "the local maxima of the response map use PRMEngine.prm_tile_stimulated (m3d/prm.py), which thresholds each "
+                    "peak by its own response (the RPN_ONLY branch, :158-162)")
         self.engine = PRMEngine(self.det)
         self.inferencing = True
 
@@ -147,6 +168,11 @@ class PeakResponseMapping_3d(Generalized_RCNN):
         if scale != 1.0:
             raise NotImplementedError("im_scale is always 1.0 on the reference path (infer_simple.py:219)")
         x = self._data(data)
+        if self.enable_peak_stimulation:                                                                  # :129-145 (back-propagation off)
+            from .peaks import peak_stimulation_3d
+            crm, _ = self.det.rpn(self.det.conv_body(x))                                                  # :94-97, any batch size
+            _, aggregation = peak_stimulation_3d(crm, win_size=self.win_size, peak_filter=self.peak_filter)   # :134
+            return (aggregation, crm) if self.inferencing else aggregation                                # :142-145 / :193
         assert x.shape[0] == 1, "Currently inference mode (with peak backpropagation) only supports one image at a time."   # :148
         out = self.engine.prm_tile(x, peak_threshold=float(peak_threshold), dense=True)
         if out is None:

@@ -397,6 +397,56 @@ class PRMEngine:
         except StopIteration as e:
             return e.value
 
+    def prm_tile_stimulated(self, data, peak_threshold=0.1, win_size=3, peak_filter='median', dense=True, cap=1 << 14):
+        """One tile back-propagated from the LOCAL MAXIMA of its class response map (what the original PRM does) instead of from the box
+        head's detections: forward_response, forward_norms, peak stimulation of `prob` (lib/prm/peak_stimulation_3d.py:6-52 with
+        `win_size` / `peak_filter`), the peaks whose own response is > peak_threshold in list order (the RPN_ONLY branch of
+        peak_response_mapping_3d.py:158-162), backward_windows.  Returns prm_tile's dict without `dets` - crm, peaks int64 [P,5]
+        (b,a,s,h,w; on the device), peaks_dev int32 [P,4], windows / sums / origins, num_live and, with dense, prms - or None when no
+        peak is kept.
+
+        `x > t` is `x >= nextafter(t)` in fp32, so both conditions are one per-channel threshold, max(filter threshold, nextafter(t)),
+        and the kept list comes out of the op itself, in order: a named filter costs one more run of the op for its thresholds (no peak
+        list, no host read).  One host wait, for the count; a tile with more than `cap` kept peaks runs the op once more."""
+        from . import peaks as pk
+        feat, prob, deltas, saved, top = self.forward_response(data)
+        self.forward_norms(saved, top)
+        crm = prob if prob.is_contiguous() else prob.contiguous()
+        B, A = crm.shape[:2]
+        assert B == 1, "one tile at a time"
+        if callable(peak_filter):
+            peak_filter = peak_filter(crm)
+        if isinstance(peak_filter, str):
+            thr = pk.peak_stimulation_3d_dev(crm, win_size, peak_filter, cap=0, aggregation=False)["thresh"]
+        elif peak_filter is None:
+            thr = None
+        elif torch.is_tensor(peak_filter):
+            thr = peak_filter.to(device=crm.device, dtype=torch.float32).reshape(B, A)
+        else:
+            thr = torch.full((B, A), float(peak_filter), dtype=torch.float32, device=crm.device)
+        above = float(np.nextafter(np.float32(peak_threshold), np.float32(np.inf)))
+        thr = torch.full((B, A), above, dtype=torch.float32, device=crm.device) if thr is None else \
+            torch.maximum(thr, torch.full_like(thr, above))                      # a NaN threshold stays NaN: no peak passes
+        cap = min(int(cap), crm.numel())
+        for _ in range(2):
+            out = pk.peak_stimulation_3d_dev(crm, win_size, thr, cap=cap, aggregation=False, mirror=True)
+            out["event"].synchronize()                                           # the host wait (behind the norm convs queued above)
+            P = int(out["host_num"][0])
+            out["release"]()
+            if P <= cap:
+                break
+            cap = P
+        if P == 0:
+            return None
+        rows = out["peaks"][:P]
+        pk32 = rows[:, 1:].contiguous()
+        with self.span("backward"):
+            win, sums, origins = self.backward_windows(pk32, saved, top, data)
+        res = dict(crm=prob, peaks=rows.to(torch.int64), peaks_dev=pk32, windows=win, sums=sums, origins=origins, num_live=P)
+        if dense:
+            res["prms"] = ops.prm_scatter(win, sums, origins, tuple(data.shape[-3:]))
+        return res
+
     def prm_tile_phases(self, data, peak_threshold=0.1, dense=True):
         """prm_tile as a generator that yields in front of each host wait ("rois": the forward and the proposals are enqueued; "peaks":
         box head and peak selection are enqueued) and returns prm_tile's result; a tile on the per-stage path returns at the first
