@@ -97,6 +97,24 @@ int m3d_roi_align3d_backward(int aligned_slices, int aligned_height, int aligned
                              int sampling_ratio, const float* d_top_grad, const float* d_rois, int num_rois,
                              int roi_cols, float* d_bottom_grad, int batch, int channels, int slices, int height,
                              int width, void* stream);
+/* The same gradient in gather form (csrc/roi_align3d_bwd.hip; DESIGN, "RoIAlign3D backward, ordered"): no atomics, EVERY element of
+ * d_bottom_grad written exactly once whatever it held (images without a RoI and num_rois == 0 included: zeros, so no zero fill before the
+ * call), the result a pure function of (d_top_grad, d_rois, shapes) - bit-identical from call to call, image b's gradient independent of
+ * the other images' RoIs.  Same semantics as m3d_roi_align3d_backward; only the order of the fp32 operations differs
+ * (|result - exact| <= (n_e + 8) 2^-24 A_e per element, n_e and A_e as in tests/roi_align_backward_cases.py).  Two launches on `stream`, no host synchronisation, allocation or read: graph
+ * capturable.  d_workspace: m3d_roi_align3d_backward_ordered_workspace_bytes(num_rois, batch) bytes, 4-byte aligned, contents arbitrary.
+ * Returns, before any pointer is followed or anything is launched: M3D_EINVAL for roi_cols != 7, num_rois < 0, a non-positive dimension
+ * or bin count, a NULL d_bottom_grad or d_workspace, NULL d_top_grad / d_rois with num_rois > 0, a workspace that is too small;
+ * M3D_EUNSUPPORTED for a fixed sampling_ratio with bins * sampling_ratio > 64 on an axis (the rule of m3d_roi_align3d_backward) and for
+ * more than 64 bins on an axis.  An ADAPTIVE grid (sampling_ratio <= 0) that needs more than 64 table entries on an axis of ANY RoI is
+ * found on the device: the call then writes NOTHING to d_bottom_grad and leaves 1 in the first int32 of d_workspace (0 otherwise); the
+ * caller reads that word after the stream has reached it (m3d.ops.roi_align3d_backward_ordered does, and raises).  With a fixed ratio the
+ * word is always 0 and need not be read. */
+size_t m3d_roi_align3d_backward_ordered_workspace_bytes(int num_rois, int batch);
+int m3d_roi_align3d_backward_ordered(int aligned_slices, int aligned_height, int aligned_width, float spatial_scale,
+                                     int sampling_ratio, const float* d_top_grad, const float* d_rois, int num_rois,
+                                     int roi_cols, float* d_bottom_grad, int batch, int channels, int slices, int height,
+                                     int width, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Greedy 3D NMS.  Replaces utils.cython_nms_3d.nms_3d / nms_3d_volume

@@ -17,6 +17,7 @@ SYMBOLS = [
     "m3d_fused_max_boxes", "m3d_compact_rows", "m3d_compact_rows2", "m3d_box_head_outputs", "m3d_conv3d_forward_split_sigmoid", "m3d_generate_proposals3d_batched_workspace_bytes", "m3d_generate_proposals3d_batched",
     "m3d_box_results3d_batched_workspace_bytes", "m3d_box_results3d_batched", "m3d_nms3d_batched_workspace_bytes", "m3d_nms3d_batched",
     "m3d_roi_align3d_forward", "m3d_roi_align3d_forward_exact", "m3d_roi_align3d_backward", "m3d_roi_align3d_workspace_bytes", "m3d_roi_align3d_forward_ws", "m3d_roi_align3d_forward_ws2", "m3d_roi_align3d_forward_ws3",
+    "m3d_roi_align3d_backward_ordered_workspace_bytes", "m3d_roi_align3d_backward_ordered",
     "m3d_nms3d_workspace_bytes", "m3d_nms3d", "m3d_bbox_overlaps3d", "m3d_bbox_transform3d",
     "m3d_generate_proposals3d_workspace_bytes", "m3d_generate_proposals3d",
     "m3d_conv3d_packed_weight_bytes", "m3d_conv3d_pack_weights", "m3d_conv3d_forward", "m3d_conv3d_forward_dilated", "m3d_conv3d_forward_windowed", "m3d_conv3d_forward_pool2", "m3d_conv3d_direct_plan", "m3d_conv3d_direct_plan_count",
@@ -97,7 +98,7 @@ def _load(path):
     L.m3d_prm_strip_geometry.restype = C.c_int64
     L.m3d_conv3d_x3_launch_units.restype = C.c_longlong
     L.m3d_conv3d_zw_launch_units.restype = C.c_longlong
-    for n in ("m3d_roi_align3d_workspace_bytes", "m3d_nms3d_workspace_bytes", "m3d_generate_proposals3d_workspace_bytes",
+    for n in ("m3d_roi_align3d_workspace_bytes", "m3d_roi_align3d_backward_ordered_workspace_bytes","m3d_nms3d_workspace_bytes", "m3d_generate_proposals3d_workspace_bytes",
               "m3d_conv3d_packed_weight_bytes", "m3d_conv3d_x3_packed_bytes", "m3d_conv3d_x3f_packed_bytes", "m3d_conv3d_zw_packed_bytes", "m3d_reduce_minmax_multi_workspace_bytes", "m3d_conv3d_x3_workspace_bytes", "m3d_reduce_min_workspace_bytes", "m3d_reduce_min_multi_workspace_bytes", "m3d_norm1_workspace_bytes", "m3d_prm_small_dgrad_packed_bytes", "m3d_prm_small_dgrad_f16_packed_bytes", "m3d_prm_small_dgrad_f16_workspace_bytes", "m3d_linear_workspace_bytes", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_workspace_bytes", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_bf16x3_w32_workspace_bytes", "m3d_linear_bf16x3_roi_workspace_bytes", "m3d_mask_paste3d_workspace_bytes", "m3d_generate_proposals3d_batched_workspace_bytes",
               "m3d_box_results3d_batched_workspace_bytes", "m3d_nms3d_batched_workspace_bytes", "m3d_otsu2d_workspace_bytes",
               "m3d_cc_workspace_bytes", "m3d_conv3d_wgrad_workspace_bytes", "m3d_conv3d_wino_packed_weight_bytes", "m3d_conv3d_wino2_packed_weight_bytes", "m3d_conv3d_wino2_workspace_bytes", "m3d_conv3d_wino2_local_workspace_bytes", "m3d_conv3d_stem_wino_packed_weight_bytes",

@@ -26,6 +26,27 @@ from . import conv_plan, ops
 
 
 # ----------------------------------------------------------------------------- RoIAlign3D
+ROI_BACKWARD_ATOMIC, ROI_BACKWARD_ORDERED = "atomic", "ordered"
+_roi_align_backward = ROI_BACKWARD_ATOMIC
+
+
+def set_roi_align_backward(mode):
+    """The backward kernel of the RoIAlign Function (RoIAlign_3d / RoIAlignAvg_3d / RoIAlignMax_3d / RoIAlignFunction_3d): "atomic" (the
+    default; install() does not change it) keeps m3d_roi_align3d_backward, whose fp32 atomic adds meet in an order nobody chooses;
+    "ordered" takes m3d_roi_align3d_backward_ordered (no atomics, bit-identical from run to run; DESIGN, "RoIAlign3D backward, ordered").
+    The forward is the same under both.  In "ordered" mode a configuration that kernel does not take (an adaptive grid beyond the tables)
+    raises M3DError; it does not fall back.  Returns the previous mode."""
+    global _roi_align_backward
+    if mode not in (ROI_BACKWARD_ATOMIC, ROI_BACKWARD_ORDERED):
+        raise ValueError("set_roi_align_backward(%r): 'atomic' or 'ordered'" % (mode,))
+    prev, _roi_align_backward = _roi_align_backward, mode
+    return prev
+
+
+def get_roi_align_backward():
+    return _roi_align_backward
+
+
 class _RoIAlign3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, rois, AS, AH, AW, scale, ratio):
@@ -37,7 +58,8 @@ class _RoIAlign3dFn(torch.autograd.Function):
     def backward(ctx, grad_output):
         rois, = ctx.saved_tensors
         AS, AH, AW, scale, ratio, fshape = ctx.cfg
-        g = ops.roi_align3d_backward(grad_output.contiguous(), rois, fshape, AS, AH, AW, scale, ratio)
+        fn = ops.roi_align3d_backward_ordered if _roi_align_backward == ROI_BACKWARD_ORDERED else ops.roi_align3d_backward
+        g = fn(grad_output.contiguous(), rois, fshape, AS, AH, AW, scale, ratio)
         return g, None, None, None, None, None, None
 
 

@@ -11,7 +11,7 @@ from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage, MaskImag
 
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
-__all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
+__all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
@@ -87,6 +87,29 @@ def roi_align3d_backward(top_grad, rois, feature_size, AS, AH, AW, spatial_scale
     check(lib().m3d_roi_align3d_backward(int(AS), int(AH), int(AW), C.c_float(spatial_scale), int(sampling_ratio),
                                          _ptr(top_grad), _ptr(rois), rois.shape[0], int(rois.shape[1]), _ptr(grad),
                                          B, Cc, S, H, W, _stream()), "roi_align3d_backward")
+    return grad
+
+
+def roi_align3d_backward_ordered(top_grad, rois, feature_size, AS, AH, AW, spatial_scale, sampling_ratio):
+    """roi_align3d_backward in gather form (m3d_roi_align3d_backward_ordered; DESIGN, "RoIAlign3D backward, ordered"): no atomics, the
+    result bit-identical from call to call, every element written by the kernel (no zero fill).  Same arguments and return.  With a fixed
+    sampling_ratio nothing is read back and the call can be captured into a graph; with an adaptive one (sampling_ratio <= 0) the status
+    word is read - a synchronisation - and a RoI whose grid is beyond the tables raises M3DError: there is no fall-back to the atomic
+    kernel."""
+    _need_gpu(top_grad, rois)
+    top_grad, rois = _f32c(top_grad), _f32c(rois)
+    B, Cc, S, H, W = feature_size
+    R = rois.shape[0]
+    grad = torch.empty((B, Cc, S, H, W), dtype=torch.float32, device=top_grad.device)
+    wsb = int(lib().m3d_roi_align3d_backward_ordered_workspace_bytes(R, B))
+    ws = torch.empty((max(wsb, 4) + 3) // 4, dtype=torch.int32, device=top_grad.device)
+    cols = int(rois.shape[1]) if rois.dim() == 2 else 0
+    check(lib().m3d_roi_align3d_backward_ordered(int(AS), int(AH), int(AW), C.c_float(spatial_scale), int(sampling_ratio),
+                                                 _ptr(top_grad), _ptr(rois), R, cols, _ptr(grad), B, Cc, S, H, W,
+                                                 _ptr(ws), C.c_size_t(wsb), _stream()), "roi_align3d_backward_ordered")
+    if int(sampling_ratio) <= 0 and int(ws[0]) != 0:
+        raise M3DError("roi_align3d_backward_ordered: an adaptive sampling grid needs more than 64 table entries on an axis of some RoI "
+                       "(bins * ceil(roi / bins) > 64); the ordered backward does not take it - nothing was written")
     return grad
 
 

@@ -61,6 +61,9 @@ def main():
                     help="conv weight-gradient kernel (m3d.compat.set_conv_wgrad): f16x2 = the f16 matrix cores where conv_plan.wgrad_kernel routes a layer")
     ap.add_argument("--conv", choices=("fp32", "f16x2"), default="fp32",
                     help="conv forward / backward-data kernel (m3d.compat.set_conv_train): f16x2 = the f16 matrix cores where conv_plan.train_conv_kernel routes a layer")
+    ap.add_argument("--roi-backward", choices=("atomic", "ordered"), default="atomic",
+                    help="RoIAlign backward kernel (m3d.compat.set_roi_align_backward) of the box head and, with --mask spot, of the mask "
+                         "branch: ordered = the gather form without atomics, bit-identical from run to run")
     a = ap.parse_args()
     import torch
     import m3d
@@ -71,6 +74,7 @@ def main():
     m3d.compat.install()
     m3d.compat.set_conv_wgrad(a.wgrad)
     m3d.compat.set_conv_train(a.conv)
+    m3d.compat.set_roi_align_backward(a.roi_backward)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
