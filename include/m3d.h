@@ -1283,6 +1283,40 @@ int m3d_peak_stimulation3d(const float* d_x, int B, int C, int S, int H, int W, 
 int m3d_peak_stimulation3d_backward(const uint8_t* d_peak_map, const float* d_gy, int B, int C, int S, int H, int W, float* d_gx,
                                     void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Mask-head up-conv (upconv3d.hip; DESIGN, "Mask-head up-conv"): nn.ConvTranspose3d(kernel 2, stride 2, padding 0) at
+ * lib/modeling/mask_rcnn_heads.py:156 with the ReLU of :193, and their autograd.  d_x fp32 [R,Cin,D,H,W], d_weight [Cin,Cout,2,2,2] (the
+ * layout of nn.ConvTranspose3d.weight), d_bias [Cout] or NULL, d_y / d_gy / d_y_mask [R,Cout,2D,2H,2W], all contiguous.
+ *   m3d_upconv3d_2x_forward  d_y[r,co,2z+a,2y+b,2x+c] = d_bias[co] + sum_ci d_x[r,ci,z,y,x] d_weight[ci,co,a,b,c], then max(., 0) if relu
+ *   with g = d_gy where d_y_mask is NULL, else d_gy where d_y_mask > 0 and 0 elsewhere (d_y_mask: the d_y a relu forward wrote):
+ *   m3d_upconv3d_2x_dgrad    d_gx[r,ci,z,y,x] = sum over (co,a,b,c) of g[r,co,2z+a,2y+b,2x+c] d_weight[ci,co,a,b,c]
+ *   m3d_upconv3d_2x_wgrad    d_gw[ci,co,a,b,c] = sum over (r,z,y,x) of d_x[r,ci,z,y,x] g[r,co,2z+a,2y+b,2x+c];
+ *                            d_gb[co] (or NULL) = sum of g[r,co,.,.,.], out of the same launch
+ * The outputs never overlap, so each is one fp32-input MFMA GEMM (v_mfma_f32_32x32x2_f32), fp32 accumulation, that addresses the 2x
+ * tensor directly: no [R, 8 Cout, D H W] intermediate, no separate bias, ReLU or ReLU-backward pass.  Every element of d_y, d_gx, d_gw
+ * and d_gb is written by the call.  Where the output of dgrad / wgrad has few tiles the reduction is cut into at most 64 slices, a
+ * function of the shape only; the partial sums live in d_ws and are added in slice order, and d_gb is summed in a fixed order without
+ * atomics: results are bit-identical run to run.  Error bound per element, with L the reduction length (Cin forward, 8 Cout dgrad,
+ * R D H W wgrad, 8 R D H W for d_gb) and S the partials added (1 where nothing is split; the forward counts its bias instead):
+ * |out - out64| <= gamma_n sum |a_k b_k| + 2^-24 |out64|, n = L + S, gamma_n = n 2^-24 / (1 - n 2^-24), the sums taken in fp64 from the
+ * fp32 inputs (the forward's include |bias|); a g element with d_y_mask <= 0 contributes exactly nothing.
+ * Limits, checked before any device pointer is followed or anything is launched.  M3D_EINVAL: a NULL required pointer (d_x, d_weight,
+ * d_y; d_gy, d_gx, d_gw), a pointer that is not 4-byte aligned, Cin, Cout, D, H or W < 1, R < 0, d_ws NULL or ws_bytes smaller than the
+ * matching *_workspace_bytes (which may be 0: then d_ws may be NULL).  M3D_EUNSUPPORTED: d_x, d_weight, d_y, d_gy, d_y_mask, d_gx, d_gw
+ * or a needed d_ws not 16-byte aligned, an operand of 2^31 elements or more.  R == 0: forward and dgrad do nothing (no pointer is
+ * looked at); wgrad zero-fills d_gw, and d_gb if given.  The workspace sizes are multiples of 16 and non-decreasing in R.
+ * ------------------------------------------------------------------------------------------------------- */
+/* host only: the partial sums S one output element is added up from; kind 0 forward (always 1), 1 dgrad, 2 wgrad; 0: a refused shape */
+int m3d_upconv3d_2x_slices(int kind, int R, int Cin, int Cout, int D, int H, int W);
+int m3d_upconv3d_2x_forward(const float* d_x, const float* d_weight, const float* d_bias, float* d_y, int R, int Cin, int Cout, int D,
+                            int H, int W, int relu, void* stream);
+size_t m3d_upconv3d_2x_dgrad_workspace_bytes(int R, int Cin, int Cout, int D, int H, int W);
+int m3d_upconv3d_2x_dgrad(const float* d_gy, const float* d_y_mask, const float* d_weight, float* d_gx, int R, int Cin, int Cout, int D,
+                          int H, int W, void* d_ws, size_t ws_bytes, void* stream);
+size_t m3d_upconv3d_2x_wgrad_workspace_bytes(int R, int Cin, int Cout, int D, int H, int W);
+int m3d_upconv3d_2x_wgrad(const float* d_gy, const float* d_y_mask, const float* d_x, float* d_gw, float* d_gb, int R, int Cin, int Cout,
+                          int D, int H, int W, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

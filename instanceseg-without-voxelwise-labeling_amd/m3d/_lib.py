@@ -43,6 +43,8 @@ SYMBOLS = [
     "m3d_mask_targets", "m3d_mask_loss_workspace_bytes", "m3d_mask_loss",
     "m3d_conv3d_zw_pack_dgrad", "m3d_conv3d_gy_reduce",
     "m3d_peak_stimulation3d_workspace_bytes", "m3d_peak_stimulation3d", "m3d_peak_stimulation3d_backward",
+    "m3d_upconv3d_2x_forward", "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_dgrad", "m3d_upconv3d_2x_wgrad_workspace_bytes",
+    "m3d_upconv3d_2x_wgrad", "m3d_upconv3d_2x_slices",
 ]
 
 
@@ -105,7 +107,8 @@ def _load(path):
               "m3d_label_overlap_workspace_bytes", "m3d_box_union_overlap_workspace_bytes", "m3d_label_components_workspace_bytes",
               "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes",
               "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes",
-              "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_peak_stimulation3d_workspace_bytes"):
+              "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_peak_stimulation3d_workspace_bytes",
+              "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -458,6 +458,67 @@ def uninstall_batch_norm():
         _orig_batch_norm = None
 
 
+# ----------------------------------------------------------------------------- mask-head up-conv (opt-in; install() leaves it alone)
+UPCONV_TORCH, UPCONV_M3D = "torch", "m3d"
+_upconv = UPCONV_TORCH
+_orig_conv_transpose3d = None
+
+
+def set_upconv(mode):
+    """The ConvTranspose3d(2, 2) + ReLU of the mask heads (train.MaskHead.forward, mask_head.MaskHeadM3D.up): "torch" (the default;
+    install() does not change it) keeps torch's ConvTranspose3d and a separate ReLU in training, and the 1x1x1 conv to 8 Cout channels
+    plus voxel shuffle at inference; "m3d" takes csrc/upconv3d.hip in both (m3d.upconv3d_2x: bias and ReLU in the epilogue, no
+    intermediate, the library's dgrad / wgrad behind it; DESIGN, "Mask-head up-conv").  Returns the previous mode."""
+    global _upconv
+    if mode not in (UPCONV_TORCH, UPCONV_M3D):
+        raise ValueError("set_upconv(%r): 'torch' or 'm3d'" % (mode,))
+    prev, _upconv = _upconv, mode
+    return prev
+
+
+def get_upconv():
+    return _upconv
+
+
+def _upconv_qualifies(x, weight, bias, stride, padding, output_padding, groups, dilation):
+    def tup(v):
+        return (v,) * 3 if isinstance(v, int) else tuple(v)
+    if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda and x.dtype == torch.float32
+            and weight.dtype == torch.float32 and x.dim() == 5 and x.is_contiguous() and weight.dim() == 5):
+        return False
+    if tuple(weight.shape[2:]) != (2, 2, 2) or weight.shape[0] != x.shape[1] or groups != 1:
+        return False
+    if bias is not None and not (torch.is_tensor(bias) and bias.is_cuda and bias.dtype == torch.float32
+                                 and tuple(bias.shape) == (weight.shape[1],)):
+        return False
+    return (tup(stride) == (2, 2, 2) and not isinstance(padding, str) and tup(padding) == (0, 0, 0) and tup(output_padding) == (0, 0, 0)
+            and tup(dilation) == (1, 1, 1))
+
+
+def conv_transpose3d(input, weight, bias=None, stride=1, padding=0, output_padding=0, groups=1, dilation=1):
+    """Contiguous fp32 CUDA [R,Cin,D,H,W] inputs with a 2^3 kernel, stride 2, padding 0, output_padding 0, groups 1, dilation 1 go to
+    m3d.upconv3d_2x (csrc/upconv3d.hip, forward and backward); everything else to torch's own with the original arguments."""
+    if _upconv_qualifies(input, weight, bias, stride, padding, output_padding, groups, dilation):
+        from .train import upconv3d_2x
+        return upconv3d_2x(input, weight, bias, relu=False)
+    orig = _orig_conv_transpose3d if _orig_conv_transpose3d is not None else torch.nn.functional.conv_transpose3d
+    return orig(input, weight, bias, stride, padding, output_padding, groups, dilation)
+
+
+def install_conv_transpose3d():
+    global _orig_conv_transpose3d
+    if _orig_conv_transpose3d is None:
+        _orig_conv_transpose3d = torch.nn.functional.conv_transpose3d
+        torch.nn.functional.conv_transpose3d = conv_transpose3d
+
+
+def uninstall_conv_transpose3d():
+    global _orig_conv_transpose3d
+    if _orig_conv_transpose3d is not None:
+        torch.nn.functional.conv_transpose3d = _orig_conv_transpose3d
+        _orig_conv_transpose3d = None
+
+
 # ----------------------------------------------------------------------------- registration
 def _mod(name, **attrs):
     m = types.ModuleType(name)

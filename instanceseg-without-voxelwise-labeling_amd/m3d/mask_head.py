@@ -9,7 +9,8 @@ M^3 masks into the volume on the device (csrc/mask_paste.hip: skimage.transform.
 Every convolution runs in the HIP library:
   * the dilated 3x3x3 convs through m3d_conv3d_forward_dilated (direct MFMA kernel, halo = dilation);
   * ConvTranspose3d(kernel 2, stride 2) never overlaps its outputs, so it is a 1x1x1 conv to 8*Cout channels
-    (one per output parity (a,b,c)) followed by a voxel shuffle to the 2x grid; bias + ReLU ride in the conv epilogue;
+    (one per output parity (a,b,c)) followed by a voxel shuffle to the 2x grid; bias + ReLU ride in the conv epilogue.
+    Under compat.set_upconv("m3d") it is one m3d_upconv3d_2x_forward instead, whose epilogue writes the 2x grid directly;
   * the 1x1x1 classifier through m3d_conv3d_forward."""
 import numpy as np
 import torch
@@ -44,8 +45,10 @@ class MaskHeadM3D:
         cin, cout = int(wu.shape[0]), int(wu.shape[1])
         self.up_cout = cout
         # out[co, 2z+a, 2y+b, 2x+c] = bias[co] + sum_ci in[ci,z,y,x] * W[ci,co,a,b,c]: channel (co,a,b,c) of a 1x1x1 conv
-        self.up = ops.PackedConv3d(wu.permute(1, 2, 3, 4, 0).reshape(cout * 8, cin, 1, 1, 1).contiguous())
+        self.up_pack = ops.PackedConv3d(wu.permute(1, 2, 3, 4, 0).reshape(cout * 8, cin, 1, 1, 1).contiguous())
         self.up_bias = params["Mask_Head.upconv.bias"].repeat_interleave(8).contiguous()
+        # compat.set_upconv("m3d"): the weight and bias as stored (csrc/upconv3d.hip reads nn.ConvTranspose3d's layout)
+        self.up_weight, self.up_bias_raw = wu.contiguous(), params["Mask_Head.upconv.bias"].contiguous()
         wc = params["Mask_Outs.classify.weight"]                                    # [n_classes or 1, C, 1, 1, 1] (:31)
         assert tuple(wc.shape[2:]) == (1, 1, 1) and wc.shape[0] == (cfg.num_classes if self.cls_specific else 1)
         self.classify = ops.PackedConv3d(wc)
@@ -58,16 +61,28 @@ class MaskHeadM3D:
             t = self._ones[n] = torch.ones((n,), dtype=torch.float32, device=device)
         return t
 
-    def head(self, feat, mask_rois):
-        """Mask_Head.forward (mask_rcnn_heads.py:181-193): [R, C, 2M', 2M', 2M'] with M' = roi_res."""
+    def trunk(self, feat, mask_rois):
+        """RoIAlign3D and the dilated convs of Mask_Head.forward (mask_rcnn_heads.py:181-192): [R, C, M', M', M'] with M' = roi_res."""
         c = self.cfg
         x = ops.roi_align3d_forward(feat, mask_rois, self.roi_res, self.roi_res, self.roi_res, 1.0 / c.stride, self.sampling_ratio)
         for conv, bias in self.convs:
             x = conv(x, scale=self._one(conv.cout, x.device), shift=bias, relu=True, dilation=self.dilation)
-        y = self.up(x, scale=self._one(self.up.cout, x.device), shift=self.up_bias, relu=True)        # :193 (ReLU is pointwise)
-        R, r = y.shape[0], self.roi_res
-        y = y.view(R, self.up_cout, 2, 2, 2, r, r, r).permute(0, 1, 5, 2, 6, 3, 7, 4)
-        return y.reshape(R, self.up_cout, 2 * r, 2 * r, 2 * r)
+        return x
+
+    def up(self, x):
+        """upconv + ReLU (mask_rcnn_heads.py:193): [R, C, M', M', M'] -> [R, Cout, 2M', 2M', 2M'].  compat.set_upconv("m3d"): one
+        m3d_upconv3d_2x_forward on the weight as stored; "torch" (the default): the 1x1x1 conv to 8 Cout channels + voxel shuffle."""
+        from . import compat
+        if compat.get_upconv() == compat.UPCONV_M3D:
+            return ops.upconv3d_2x_forward(x, self.up_weight, self.up_bias_raw, relu=True)
+        y = self.up_pack(x, scale=self._one(self.up_pack.cout, x.device), shift=self.up_bias, relu=True)   # ReLU is pointwise
+        R, d, h, w = y.shape[0], x.shape[2], x.shape[3], x.shape[4]
+        y = y.view(R, self.up_cout, 2, 2, 2, d, h, w).permute(0, 1, 5, 2, 6, 3, 7, 4)
+        return y.reshape(R, self.up_cout, 2 * d, 2 * h, 2 * w)
+
+    def head(self, feat, mask_rois):
+        """Mask_Head.forward (mask_rcnn_heads.py:181-193): [R, C, 2M', 2M', 2M'] with M' = roi_res."""
+        return self.up(self.trunk(feat, mask_rois))
 
     def outputs(self, x):
         """Mask_Outs.forward in eval mode (mask_rcnn_heads.py:62-68, UPSAMPLE_RATIO 1, USE_FC_OUTPUT False)."""

@@ -12,7 +12,7 @@ from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage, MaskImag
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -652,6 +652,97 @@ def linear_wgrad(gy, x, bias=True, out=None):
     wsb = lib().m3d_linear_wgrad_workspace_bytes(M, N, K)
     ws = torch.empty((wsb // 4,), dtype=torch.float32, device=gy.device) if wsb else None
     check(lib().m3d_linear_wgrad(_ptr(gy), _ptr(x), _ptr(out), _ptr(gb), M, N, K, _ptr(ws), C.c_size_t(wsb), _stream()), "linear_wgrad")
+    return out, gb
+
+
+def _upconv_dims(what, weight, x=None, g=None):
+    """(R, Cin, Cout, D, H, W) of an up-conv call from weight [Cin,Cout,2,2,2] and x [R,Cin,D,H,W] and / or g [R,Cout,2D,2H,2W]"""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (2, 2, 2):
+        raise ValueError("%s: weight must be [Cin, Cout, 2, 2, 2], got %s" % (what, tuple(weight.shape)))
+    cin, cout = int(weight.shape[0]), int(weight.shape[1])
+    if x is not None:
+        if x.dim() != 5 or x.shape[1] != cin:
+            raise ValueError("%s: x is %s but weight is %s" % (what, tuple(x.shape), tuple(weight.shape)))
+        R, D, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), int(x.shape[4])
+    else:
+        if g.dim() != 5 or any(int(s) % 2 for s in g.shape[2:]):
+            raise ValueError("%s: gy must be [R, Cout, 2D, 2H, 2W], got %s" % (what, tuple(g.shape)))
+        R, D, H, W = int(g.shape[0]), int(g.shape[2]) // 2, int(g.shape[3]) // 2, int(g.shape[4]) // 2
+    if g is not None and tuple(g.shape) != (R, cout, 2 * D, 2 * H, 2 * W):
+        raise ValueError("%s: gy is %s, expected %s" % (what, tuple(g.shape), (R, cout, 2 * D, 2 * H, 2 * W)))
+    return R, cin, cout, D, H, W
+
+
+UPCONV_KINDS = ("forward", "dgrad", "wgrad")
+
+
+def upconv3d_2x_slices(kind, R, Cin, Cout, D, H, W):
+    """The partial sums an output element of the up-conv launch `kind` (a name in UPCONV_KINDS) is added up from at this shape
+    (m3d_upconv3d_2x_slices, host only): 1 where the reduction is not split; 0 for a shape the launch refuses."""
+    return int(lib().m3d_upconv3d_2x_slices(UPCONV_KINDS.index(kind), int(R), int(Cin), int(Cout), int(D), int(H), int(W)))
+
+
+def upconv3d_2x_forward(x, weight, bias=None, relu=False, out=None):
+    """ConvTranspose3d(kernel 2, stride 2, padding 0) with bias and ReLU in the epilogue (m3d_upconv3d_2x_forward): x [R,Cin,D,H,W],
+    weight [Cin,Cout,2,2,2] as nn.ConvTranspose3d stores it, bias [Cout] or None -> [R,Cout,2D,2H,2W].  mask_rcnn_heads.py:156,193."""
+    _need_gpu(x, weight, bias)
+    x, weight = _f32c(x), _f32c(weight)
+    R, cin, cout, D, H, W = _upconv_dims("upconv3d_2x_forward", weight, x=x)
+    if bias is not None:
+        bias = _f32c(bias)
+        if bias.numel() != cout:
+            raise ValueError("upconv3d_2x_forward: bias has %d elements, Cout is %d" % (bias.numel(), cout))
+    _claim(out)
+    if out is None:
+        out = torch.empty((R, cout, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+    check(lib().m3d_upconv3d_2x_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), R, cin, cout, D, H, W, int(bool(relu)), _stream()),
+          "upconv3d_2x_forward")
+    return out
+
+
+def upconv3d_2x_dgrad(gy, weight, y=None, out=None):
+    """The input gradient of upconv3d_2x_forward (m3d_upconv3d_2x_dgrad): gy [R,Cout,2D,2H,2W], weight [Cin,Cout,2,2,2] -> [R,Cin,D,H,W].
+    y: the output of a relu forward - gy counts only where y > 0, applied while gy is staged (None: no ReLU)."""
+    _need_gpu(gy, weight, y)
+    gy, weight = _f32c(gy), _f32c(weight)
+    R, cin, cout, D, H, W = _upconv_dims("upconv3d_2x_dgrad", weight, g=gy)
+    if y is not None:
+        y = _f32c(y)
+        if y.shape != gy.shape:
+            raise ValueError("upconv3d_2x_dgrad: y is %s but gy is %s" % (tuple(y.shape), tuple(gy.shape)))
+    _claim(out)
+    if out is None:
+        out = torch.empty((R, cin, D, H, W), dtype=torch.float32, device=gy.device)
+    wsb = lib().m3d_upconv3d_2x_dgrad_workspace_bytes(R, cin, cout, D, H, W)
+    ws = _workspace(wsb, gy.device, "upconv") if wsb else None
+    check(lib().m3d_upconv3d_2x_dgrad(_ptr(gy), _ptr(y), _ptr(weight), _ptr(out), R, cin, cout, D, H, W, _ptr(ws), C.c_size_t(wsb),
+                                      _stream()), "upconv3d_2x_dgrad")
+    return out
+
+
+def upconv3d_2x_wgrad(gy, x, y=None, bias=True, out=None):
+    """The weight and bias gradients of upconv3d_2x_forward out of one launch (m3d_upconv3d_2x_wgrad): gy [R,Cout,2D,2H,2W], x
+    [R,Cin,D,H,W] -> ([Cin,Cout,2,2,2], [Cout] or None without `bias`); an empty batch gives zeros.  y: as upconv3d_2x_dgrad."""
+    _need_gpu(gy, x, y)
+    gy, x = _f32c(gy), _f32c(x)
+    if gy.dim() != 5 or x.dim() != 5:
+        raise ValueError("upconv3d_2x_wgrad: gy is %s, x is %s" % (tuple(gy.shape), tuple(x.shape)))
+    cin, cout = int(x.shape[1]), int(gy.shape[1])
+    R, D, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), int(x.shape[4])
+    if tuple(gy.shape) != (R, cout, 2 * D, 2 * H, 2 * W):
+        raise ValueError("upconv3d_2x_wgrad: gy is %s, expected %s" % (tuple(gy.shape), (R, cout, 2 * D, 2 * H, 2 * W)))
+    if y is not None:
+        y = _f32c(y)
+        if y.shape != gy.shape:
+            raise ValueError("upconv3d_2x_wgrad: y is %s but gy is %s" % (tuple(y.shape), tuple(gy.shape)))
+    _claim(out)
+    if out is None:
+        out = torch.empty((cin, cout, 2, 2, 2), dtype=torch.float32, device=gy.device)
+    gb = torch.empty((cout,), dtype=torch.float32, device=gy.device) if bias else None
+    wsb = lib().m3d_upconv3d_2x_wgrad_workspace_bytes(R, cin, cout, D, H, W)
+    ws = _workspace(wsb, gy.device, "upconv") if wsb else None
+    check(lib().m3d_upconv3d_2x_wgrad(_ptr(gy), _ptr(y), _ptr(x), _ptr(out), _ptr(gb), R, cin, cout, D, H, W, _ptr(ws), C.c_size_t(wsb),
+                                      _stream()), "upconv3d_2x_wgrad")
     return out, gb
 
 

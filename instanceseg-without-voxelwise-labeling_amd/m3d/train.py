@@ -509,11 +509,49 @@ def mask_losses(mask_pred, targets):
     return _MaskLoss.apply(mask_pred, targets.masks, float(targets.cfg.weight_loss_mask))
 
 
+class _UpConv3d2x(torch.autograd.Function):
+    """ConvTranspose3d(kernel 2, stride 2, padding 0) (+ ReLU) on csrc/upconv3d.hip.  With relu the forward's own output is saved and
+    handed to both backward kernels as the mask: no ReLU-backward pass over the 2x tensor.  Only the gradients autograd asks for are
+    computed; the bias gradient comes out of the wgrad launch."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        y = ops.upconv3d_2x_forward(x, weight.detach(), None if bias is None else bias.detach(), relu=relu)
+        ctx.relu, ctx.has_bias = bool(relu), bias is not None
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.upconv3d_2x_dgrad(gy, weight.detach(), y=y)
+        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_gb:
+            gw, gb = ops.upconv3d_2x_wgrad(gy, x.detach(), y=y, bias=want_gb)
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        return gx, gw, gb, None
+
+
+def upconv3d_2x(x, weight, bias=None, relu=False):
+    """torch.nn.functional.conv_transpose3d(x, weight, bias, stride=2) for a [Cin,Cout,2,2,2] weight, followed by ReLU if `relu`, forward
+    and backward on the library's kernels (mask_rcnn_heads.py:156,193).  x [R,Cin,D,H,W] -> [R,Cout,2D,2H,2W], fp32."""
+    for t in (x, weight, bias):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise ops.M3DError("upconv3d_2x: x, weight and bias must be CUDA (ROCm) tensors; there is no CPU path")
+    return _UpConv3d2x.apply(x.contiguous(), weight.contiguous(), bias, bool(relu))
+
+
 class MaskHead(torch.nn.Module):
     """mask_rcnn_fcn_head_v1upXconvs followed by mask_rcnn_outputs (mask_rcnn_heads.py:132-193, 20-68; dilation 1, conv classifier, no
     upsampling) as one module under the reference's parameter names conv_fcn.{0,2,..}, upconv, classify: its state_dict, prefixed
     Mask_Head. / Mask_Outs. by `detector_state`, is what MaskHeadM3D takes.  RoIAlign3D and the convolutions go through m3d.compat (the
-    library's kernels, forward and backward); ConvTranspose3d is torch's.  forward returns logits, as the reference does in training."""
+    library's kernels, forward and backward).  The up-conv follows compat.set_upconv: "torch" (the default) is torch's ConvTranspose3d
+    and a separate ReLU; "m3d" is upconv3d_2x with the bias and the ReLU in its epilogue and the library's dgrad / wgrad kernels behind
+    it - the same module, parameters and state_dict under both.  forward returns logits, as the reference does in training."""
 
     def __init__(self, dim_in, cfg, stride):
         super().__init__()
@@ -550,5 +588,8 @@ class MaskHead(torch.nn.Module):
         x = compat.RoIAlignFunction_3d(r, r, r, self.spatial_scale, int(self.cfg.sampling_ratio))(feat, rois7)
         for m in self.conv_fcn:
             x = compat.conv3d(x, m.weight, m.bias, 1, 1) if isinstance(m, torch.nn.Conv3d) else torch.relu(x)
-        x = torch.relu(self.upconv(x))
+        if compat.get_upconv() == compat.UPCONV_M3D:
+            x = upconv3d_2x(x, self.upconv.weight, self.upconv.bias, relu=True)
+        else:
+            x = torch.relu(self.upconv(x))
         return compat.conv3d(x, self.classify.weight, self.classify.bias, 1, 0)

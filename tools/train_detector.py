@@ -64,6 +64,9 @@ def main():
     ap.add_argument("--roi-backward", choices=("atomic", "ordered"), default="atomic",
                     help="RoIAlign backward kernel (m3d.compat.set_roi_align_backward) of the box head and, with --mask spot, of the mask "
                          "branch: ordered = the gather form without atomics, bit-identical from run to run")
+    ap.add_argument("--upconv", choices=("torch", "m3d"), default="torch",
+                    help="with --mask: the mask head's ConvTranspose3d + ReLU (m3d.compat.set_upconv): m3d = csrc/upconv3d.hip, forward and "
+                         "backward, bias and ReLU fused")
     a = ap.parse_args()
     import torch
     import m3d
@@ -75,6 +78,7 @@ def main():
     m3d.compat.set_conv_wgrad(a.wgrad)
     m3d.compat.set_conv_train(a.conv)
     m3d.compat.set_roi_align_backward(a.roi_backward)
+    m3d.compat.set_upconv(a.upconv)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
