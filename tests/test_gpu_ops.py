@@ -151,6 +151,13 @@ def test_generate_proposals_vs_oracle_full_size_with_ties(m3d):
 
 
 # ------------------------------------------------------------------ RoIAlign3D
+def roi_forward_within_its_bound(f, rois, res, scale, ratio, got):
+    """the per-element bound of the fp32 forward (tests/roi_align_forward_cases.py) on top of a test's own tolerance"""
+    import roi_align_forward_cases as Fc
+    v = Fc.compare(got, Fc.reference(f, rois, f.shape, (res, res, res), scale, ratio))
+    assert v.outside == 0 and v.nonzero == 0, Fc.describe(v)
+
+
 @pytest.mark.parametrize("shape,R,res,ratio", [((1, 8, 8, 8, 8), 5, 7, 2), ((2, 16, 6, 9, 11), 33, 7, 2),
                                                 ((1, 4, 5, 6, 7), 9, 3, 0), ((1, 256, 16, 16, 16), 200, 7, 2)])
 def test_roi_align_forward_bit_exact(m3d, shape, R, res, ratio):
@@ -167,6 +174,8 @@ def test_roi_align_forward_bit_exact(m3d, shape, R, res, ratio):
     fast = m3d.roi_align3d_forward(dev(f), dev(rois), res, res, res, 0.125, ratio).cpu().numpy()
     assert np.abs(fast - ref).max() <= 1e-5 * np.abs(f).max()            # separable form: tolerance 1e-5 * max|f|
     assert np.array_equal(fast == 0, ref == 0) or np.abs(fast[ref == 0]).max() < 1e-6
+    if R * shape[1] <= 1024:                 # the fp64 reference is cheap here
+        roi_forward_within_its_bound(f, rois, res, 0.125, ratio, fast)
 
 
 @pytest.mark.parametrize("B,C,dims,R", [(4, 256, (16, 16, 16), 400), (1, 128, (16, 40, 40), 300), (2, 64, (8, 25, 25), 150), (1, 96, (12, 14, 16), 80)])
@@ -222,6 +231,7 @@ def test_roi_align_fast_and_complement_kernels_share_the_rois(m3d, C):
     fast = m3d.roi_align3d_forward(dev(f), dev(rois), 7, 7, 7, 0.125, 2).cpu().numpy()
     assert not np.isnan(fast).any()
     assert np.abs(fast - ref).max() <= 1e-5 * np.abs(f).max()
+    roi_forward_within_its_bound(f, rois, 7, 0.125, 2, fast)
     # the heavy-first launch order (m3d_roi_align3d_forward_ws: RoIs taken by descending work) changes WHICH workgroup computes a row,
     # nothing of the row: bit-identical with the index-order launch, duplicated RoIs (equal cost: ties by index) included
     rois2 = np.vstack((rois, rois[:7], rois[::-1][:5])).astype(np.float32)
@@ -821,6 +831,7 @@ def test_roi_align_adaptive_grid_large_rois(m3d, res):
     assert np.array_equal(got, ref)
     fast = m3d.roi_align3d_forward(dev(f), dev(rois), res, res, res, 1.0, 0).cpu().numpy()
     assert np.abs(fast - ref).max() <= 1e-5 * np.abs(f).max()
+    roi_forward_within_its_bound(f, rois, res, 1.0, 0, fast)
     top = rs.randn(*ref.shape).astype(np.float32)
     gref = O.roi_align_3d_backward(top, rois, f.shape, res, res, res, 1.0, 0)
     ggot = m3d.roi_align3d_backward(dev(top), dev(rois), f.shape, res, res, res, 1.0, 0).cpu().numpy()
