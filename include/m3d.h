@@ -1181,6 +1181,50 @@ int m3d_sgd_step(const m3d_sgd_tensor* tensors, int count, float momentum, float
                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The solver's other optimiser and the gradient clip (csrc/adam.hip; m3d_sgd_step_scaled in csrc/sgd.hip).  Chunking, descriptor
+ * passing, 16-byte accesses, statistics, workspace convention and the M3D_EUNSUPPORTED cases are those of m3d_sgd_step.
+ *
+ * m3d_adam_step: the single-tensor torch.optim.Adam of torch 2.10 (amsgrad and maximize off, coupled weight decay, betas = (beta1,
+ * beta2)) which tools/train_net_step.py:330-333 builds, over a whole parameter list, 64 descriptors per launch.  `tensors` is a HOST
+ * array of `count` descriptors: p, g, m (exp_avg), v (exp_avg_sq) device fp32 [n], and per tensor the two scalars of its step count t,
+ * which the caller computes in doubles as torch does and rounds to fp32: lr_step = lr / (1 - beta1^t), bc2_sqrt = (1 - beta2^t)^0.5.
+ * 1 - beta1, beta2, 1 - beta2 and eps are rounded to fp32 from the doubles given here, again as torch rounds them.  Per element, in
+ * fp32, every operation rounded once, nothing contracted, square root and division correctly rounded:
+ *     d = s g  (only with d_gscale) ;  d = (wd == 0) ? d : d + wd p ;  m' = m + (1 - beta1) (d - m) ;
+ *     v' = beta2 v + (1 - beta2) (d d) ;  q = sqrt(v') / bc2_sqrt + eps ;  p' = p - lr_step (m' / q)
+ * p, m and v are updated in place, g is never written.  Zero-filled m and v with the scalars of t = 1 give torch's first step.
+ * d_gscale: NULL, or a device fp32 scalar s that the kernel reads (never a host value): the clip coefficient of m3d_grad_clip_coef.
+ * d_stats as in m3d_sgd_step: the statistics of the RAW gradients.  A thread adds its squares in the order of m3d_sgd_step's 16-byte
+ * path for the residue modulo 16 of g, also where p, m or v lie at another residue and the chunk is updated element by element: the two
+ * numbers are a function of the sizes, order, values and pointer residues of the gradients alone, and equal m3d_grad_clip_coef's.
+ * Limits, checked before any device pointer is followed: the rules of m3d_sgd_step for the four pointers (NULL, alignment, overlap of
+ * any two of p, g, m, v); beta1 or beta2 outside [0, 1); eps not positive as fp32; bc2_sqrt outside (0, 1]; a misaligned d_gscale:
+ * M3D_EINVAL.
+ *
+ * m3d_grad_clip_coef: clip_gradient of lib/utils/net.py:35-47 as a device scalar.  A read-only pass over the gradients (`tensors`: a
+ * HOST array of {g, n}) that writes the two statistics to d_stats (required) and
+ *     *d_coef = (float)(clip_norm / max(sqrt(d_stats[0]), clip_norm)),   square root and division in fp64,
+ * 1.0f exactly when the norm does not exceed clip_norm.  The norm is the fp64 sum the solver defines; the reference adds per-parameter
+ * fp32 norms on the host.  max() keeps a NaN norm, as Python's does there: a NaN gradient makes the coefficient NaN, an infinite one
+ * makes it 0 and the scaled element NaN; d_stats[1] is the guard.  Limits: the rules of m3d_sgd_step for g; clip_norm not positive or
+ * not finite, d_stats or d_coef NULL or misaligned: M3D_EINVAL.
+ *
+ * m3d_sgd_step_scaled: m3d_sgd_step with d = s g in front of the decay term, s read from d_gscale on the device; the statistics stay
+ * those of the raw gradients.  d_gscale == NULL runs the kernels of m3d_sgd_step.
+ *
+ * A clipped step is the coefficient pass (one launch per 64 tensors and the finish) followed by the update (one launch per 64 tensors,
+ * d_stats == NULL): no host read, allocation or copy, so it can be captured into a graph.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct { float* p; const float* g; float* m; float* v; long long n; float lr_step; float bc2_sqrt; float wd; } m3d_adam_tensor;
+typedef struct { const float* g; long long n; } m3d_grad_tensor;
+int m3d_adam_step(const m3d_adam_tensor* tensors, int count, double beta1, double beta2, double eps, const float* d_gscale,
+                  double* d_stats, void* d_ws, size_t* ws_bytes, void* stream);
+int m3d_grad_clip_coef(const m3d_grad_tensor* tensors, int count, double clip_norm, double* d_stats, float* d_coef, void* d_ws,
+                       size_t* ws_bytes, void* stream);
+int m3d_sgd_step_scaled(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, const float* d_gscale, double* d_stats,
+                        void* d_ws, size_t* ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Training samples (train_sample.hip; DESIGN, "Training samples"): the minibatch of lib/roi_data/minibatch.py built on the device from
  * volumes that stay resident there - prep_im_for_blob(..., 'train') and crop_data_3d of lib/utils/blob.py:97-202.
  * `images` is a HOST array of `count` descriptors (they travel as kernel arguments): the device volume [depth,height,width] (dtype 0 =

@@ -4,19 +4,14 @@
 //
 // fp32, built with -ffp-contract=off; per element, every operation rounded once:
 //   c = mscale m ; d = (wd == 0) ? g : g + wd p ; m' = momentum c + d ; p' = p - lr m'          (m == NULL: p' = p - lr d)
+// m3d_sgd_step_scaled: the same with g replaced by s g, s one fp32 read from device memory (the clip coefficient of adam.hip); the
+// statistics stay those of the raw gradients.  Without s it runs the very kernels of m3d_sgd_step.
 // Work is cut into chunks of kChunk elements of one tensor (a function of the tensors' sizes and order only); one workgroup per chunk.
 // The tensors' descriptors travel as kernel arguments: a step copies nothing to the device, allocates nothing and never waits.
 // Statistics: one fp64 partial and one count per chunk, summed by a finish kernel in a fixed order - no floating-point atomics.
-#include "m3d_common.h"
+#include "solver_common.h"
 
 namespace {
-
-constexpr int kTPB = 256;
-constexpr int kChunk = 8192;            // elements per workgroup: 8 quads per thread
-constexpr int kMaxSeg = 64;             // descriptors per launch (40 bytes each: the kernel-argument space holds 4 KB)
-constexpr int kMaxBlocks = 1 << 22;     // workgroups per launch (2^35 elements)
-constexpr int kMaxCount = 65536;
-constexpr long long kMaxN = 1ll << 40;
 
 // a run of whole chunks of one tensor (a tensor of more than kMaxBlocks chunks takes several)
 struct Seg {
@@ -33,7 +28,7 @@ struct Args {
   float momentum, mscale;
   long long part0;          // index of the launch's first chunk among the chunks of the call
 };
-static_assert(sizeof(Args) <= 4096, "the descriptors must fit the kernel-argument space");
+static_assert(sizeof(Args) <= 4096 - 16, "the descriptors must fit the kernel-argument space");
 
 __device__ __forceinline__ float sgd_d(float p, float g, float wd) { return wd == 0.f ? g : g + wd * p; }
 
@@ -49,30 +44,8 @@ __device__ __forceinline__ void sgd_one(float& p, float g, float& m, float lr, f
   }
 }
 
-__device__ __forceinline__ void stat_of(float g, double& s, double& bad) {
-  const double v = (double)g;
-  s += v * v;
-  bad += (__float_as_uint(g) & 0x7f800000u) == 0x7f800000u ? 1.0 : 0.0;
-}
-
-// (a, b) summed over the workgroup in a fixed tree; valid in thread 0
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* sm) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off, 64);
-    b += __shfl_down(b, off, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[2 * w] = a; sm[2 * w + 1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = (sm[0] + sm[2]) + (sm[4] + sm[6]);
-    b = (sm[1] + sm[3]) + (sm[5] + sm[7]);
-  }
-}
-
-template <bool HAS_M, bool STATS>
-__global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __restrict__ part) {
+template <bool HAS_M, bool STATS, bool SCALED>
+__global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __restrict__ part, const float* __restrict__ gscale) {
   __shared__ double sm[8];
   const int b = blockIdx.x;
   int lo = 0, hi = a.nseg;          // first[lo] <= b < first[hi]
@@ -88,6 +61,7 @@ __global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __
   const float* g = sg.g + off;
   float* m = HAS_M ? sg.m + off : nullptr;
   const float lr = sg.lr, wd = sg.wd, mu = a.momentum, ms = a.mscale;
+  const float gs = SCALED ? *gscale : 1.f;
   double s = 0.0, bad = 0.0;
 
   // 16-byte accesses from the first common 16-byte boundary; a tensor whose pointers differ modulo 16 goes element by element
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __
     float pv = p[i], mv = HAS_M ? m[i] : 0.f;
     const float gv = g[i];
     if (STATS) stat_of(gv, s, bad);
-    sgd_one<HAS_M>(pv, gv, mv, lr, wd, mu, ms);
+    sgd_one<HAS_M>(pv, SCALED ? gs * gv : gv, mv, lr, wd, mu, ms);
     p[i] = pv;
     if (HAS_M) m[i] = mv;
   }
@@ -116,10 +90,10 @@ __global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __
     const float4 gv = g4[i];
     float4 mv = HAS_M ? m4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     if (STATS) { stat_of(gv.x, s, bad); stat_of(gv.y, s, bad); stat_of(gv.z, s, bad); stat_of(gv.w, s, bad); }
-    sgd_one<HAS_M>(pv.x, gv.x, mv.x, lr, wd, mu, ms);
-    sgd_one<HAS_M>(pv.y, gv.y, mv.y, lr, wd, mu, ms);
-    sgd_one<HAS_M>(pv.z, gv.z, mv.z, lr, wd, mu, ms);
-    sgd_one<HAS_M>(pv.w, gv.w, mv.w, lr, wd, mu, ms);
+    sgd_one<HAS_M>(pv.x, SCALED ? gs * gv.x : gv.x, mv.x, lr, wd, mu, ms);
+    sgd_one<HAS_M>(pv.y, SCALED ? gs * gv.y : gv.y, mv.y, lr, wd, mu, ms);
+    sgd_one<HAS_M>(pv.z, SCALED ? gs * gv.z : gv.z, mv.z, lr, wd, mu, ms);
+    sgd_one<HAS_M>(pv.w, SCALED ? gs * gv.w : gv.w, mv.w, lr, wd, mu, ms);
     p4[i] = pv;
     if (HAS_M) m4[i] = mv;
   }
@@ -128,7 +102,7 @@ __global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __
     float pv = p[t], mv = HAS_M ? m[t] : 0.f;
     const float gv = g[t];
     if (STATS) stat_of(gv, s, bad);
-    sgd_one<HAS_M>(pv, gv, mv, lr, wd, mu, ms);
+    sgd_one<HAS_M>(pv, SCALED ? gs * gv : gv, mv, lr, wd, mu, ms);
     p[t] = pv;
     if (HAS_M) m[t] = mv;
   }
@@ -141,20 +115,11 @@ __global__ __launch_bounds__(kTPB) void sgd_step_kernel(const Args a, double* __
   }
 }
 
-// thread t adds the partials t, t + kTPB, ... in ascending order, then the fixed tree: a function of the number of chunks only
 __global__ __launch_bounds__(kTPB) void sgd_stats_finish_kernel(const double* __restrict__ part, long long chunks, double* __restrict__ stats) {
   __shared__ double sm[8];
-  double s = 0.0, bad = 0.0;
-  for (long long i = threadIdx.x; i < chunks; i += kTPB) { s += part[2 * i]; bad += part[2 * i + 1]; }
-  block_sum2(s, bad, sm);
+  double s, bad;
+  finish_sum2(part, chunks, s, bad, sm);
   if (threadIdx.x == 0) { stats[0] = s; stats[1] = bad; }
-}
-
-inline long long chunks_of(long long n) { return (n + kChunk - 1) / kChunk; }
-
-inline bool apart(const void* a, const void* b, long long n) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * 4;
-  return x < y ? y - x >= bytes : x - y >= bytes;
 }
 
 // M3D_OK and the number of chunks of the call, or the refusal; no device pointer is followed and nothing is launched
@@ -178,36 +143,32 @@ int validate(const m3d_sgd_tensor* t, int count, float momentum, long long* chun
   return M3D_OK;
 }
 
-void launch(const Args& a, bool has_m, double* part, hipStream_t st) {
+template <bool SCALED>
+void launch_as(const Args& a, bool has_m, double* part, const float* gscale, hipStream_t st) {
   const dim3 grid((unsigned)a.first[a.nseg]), block(kTPB);
   if (has_m) {
-    if (part) hipLaunchKernelGGL((sgd_step_kernel<true, true>), grid, block, 0, st, a, part);
-    else hipLaunchKernelGGL((sgd_step_kernel<true, false>), grid, block, 0, st, a, part);
+    if (part) hipLaunchKernelGGL((sgd_step_kernel<true, true, SCALED>), grid, block, 0, st, a, part, gscale);
+    else hipLaunchKernelGGL((sgd_step_kernel<true, false, SCALED>), grid, block, 0, st, a, part, gscale);
   } else {
-    if (part) hipLaunchKernelGGL((sgd_step_kernel<false, true>), grid, block, 0, st, a, part);
-    else hipLaunchKernelGGL((sgd_step_kernel<false, false>), grid, block, 0, st, a, part);
+    if (part) hipLaunchKernelGGL((sgd_step_kernel<false, true, SCALED>), grid, block, 0, st, a, part, gscale);
+    else hipLaunchKernelGGL((sgd_step_kernel<false, false, SCALED>), grid, block, 0, st, a, part, gscale);
   }
 }
 
-}  // namespace
+void launch(const Args& a, bool has_m, double* part, const float* gscale, hipStream_t st) {
+  if (gscale) launch_as<true>(a, has_m, part, gscale, st);
+  else launch_as<false>(a, has_m, part, gscale, st);
+}
 
-M3D_API int m3d_sgd_chunk(void) { return kChunk; }
-
-M3D_API int m3d_sgd_step(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, double* d_stats, void* d_ws,
-                         size_t* ws_bytes, void* stream) {
+int sgd_step(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, const float* d_gscale, double* d_stats, void* d_ws,
+             size_t* ws_bytes, void* stream) {
   long long chunks = 0;
-  const int rc = validate(tensors, count, momentum, &chunks);
+  int rc = validate(tensors, count, momentum, &chunks);
   if (rc != M3D_OK) return rc;
-  const size_t need = d_stats ? sizeof(double) * 2 * (size_t)chunks : 0;
-  if (!d_ws && ws_bytes) {           // the size query
-    *ws_bytes = need;
-    return M3D_OK;
-  }
-  if (d_stats) {
-    if (((uintptr_t)d_stats | (uintptr_t)d_ws) & 7) return M3D_EINVAL;
-    if (need > 0 && (!d_ws || !ws_bytes)) return M3D_EINVAL;
-    if (need > 0 && *ws_bytes < need) return M3D_EWORKSPACE;
-  }
+  if ((uintptr_t)d_gscale & 3) return M3D_EINVAL;
+  bool query = false;
+  rc = stats_workspace(d_stats, d_ws, ws_bytes, chunks, &query);
+  if (rc != M3D_OK || query) return rc;
   if (chunks == 0 && !d_stats) return M3D_OK;   // nothing to do: the runtime is not touched
   hipStream_t st = m3d::as_stream(stream);
   double* part = d_stats ? (double*)d_ws : nullptr;
@@ -243,19 +204,33 @@ M3D_API int m3d_sgd_step(const m3d_sgd_tensor* tensors, int count, float momentu
           ++a.nseg;
           done += take;
           if (a.nseg == kMaxSeg || a.first[a.nseg] == kMaxBlocks) {
-            launch(a, has_m, part, st);
+            launch(a, has_m, part, d_gscale, st);
             a.nseg = 0;
           }
         }
       } else if (a.nseg > 0 && nc > 0) {
         // a tensor of the other kind lies between: its chunks keep their place in the call's order, so this launch ends here
-        launch(a, has_m, part, st);
+        launch(a, has_m, part, d_gscale, st);
         a.nseg = 0;
       }
       at += nc;
     }
-    if (a.nseg > 0) launch(a, has_m, part, st);
+    if (a.nseg > 0) launch(a, has_m, part, d_gscale, st);
   }
   if (d_stats) hipLaunchKernelGGL(sgd_stats_finish_kernel, dim3(1), dim3(kTPB), 0, st, (const double*)part, chunks, d_stats);
   return m3d::check_launch("sgd_step");
+}
+
+}  // namespace
+
+M3D_API int m3d_sgd_chunk(void) { return kChunk; }
+
+M3D_API int m3d_sgd_step(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, double* d_stats, void* d_ws,
+                         size_t* ws_bytes, void* stream) {
+  return sgd_step(tensors, count, momentum, mscale, nullptr, d_stats, d_ws, ws_bytes, stream);
+}
+
+M3D_API int m3d_sgd_step_scaled(const m3d_sgd_tensor* tensors, int count, float momentum, float mscale, const float* d_gscale,
+                                double* d_stats, void* d_ws, size_t* ws_bytes, void* stream) {
+  return sgd_step(tensors, count, momentum, mscale, d_gscale, d_stats, d_ws, ws_bytes, stream);
 }

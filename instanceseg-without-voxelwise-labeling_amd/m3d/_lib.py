@@ -37,7 +37,7 @@ SYMBOLS = [
     "m3d_rpn_targets_workspace_bytes", "m3d_rpn_targets", "m3d_rpn_targets_wide", "m3d_rpn_loss",
     "m3d_box_head_targets_workspace_bytes", "m3d_box_head_targets", "m3d_box_head_target_blobs", "m3d_box_head_loss",
     "m3d_bn_stats", "m3d_bn_invstd", "m3d_bn_apply", "m3d_bn_backward",
-    "m3d_sgd_chunk", "m3d_sgd_step",
+    "m3d_sgd_chunk", "m3d_sgd_step", "m3d_sgd_step_scaled", "m3d_adam_step", "m3d_grad_clip_coef",
     "m3d_train_sample",
     "m3d_linear_dgrad_workspace_bytes", "m3d_linear_dgrad", "m3d_linear_wgrad_workspace_bytes", "m3d_linear_wgrad",
     "m3d_mask_targets", "m3d_mask_loss_workspace_bytes", "m3d_mask_loss",
@@ -51,6 +51,17 @@ SYMBOLS = [
 class SgdTensor(C.Structure):
     """m3d_sgd_tensor of include/m3d.h: one parameter of an m3d_sgd_step call"""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("n", C.c_longlong), ("lr", C.c_float), ("wd", C.c_float)]
+
+
+class AdamTensor(C.Structure):
+    """m3d_adam_tensor of include/m3d.h: one parameter of an m3d_adam_step call"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_longlong), ("lr_step", C.c_float),
+                ("bc2_sqrt", C.c_float), ("wd", C.c_float)]
+
+
+class GradTensor(C.Structure):
+    """m3d_grad_tensor of include/m3d.h: one gradient of an m3d_grad_clip_coef call"""
+    _fields_ = [("g", C.c_void_p), ("n", C.c_longlong)]
 
 
 class TrainImage(C.Structure):

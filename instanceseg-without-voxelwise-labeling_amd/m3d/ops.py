@@ -7,13 +7,13 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import lib, check, M3DError, SgdTensor, BoxHead, TrainImage, MaskImage
+from ._lib import lib, check, M3DError, SgdTensor, AdamTensor, GradTensor, BoxHead, TrainImage, MaskImage
 
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -2601,3 +2601,108 @@ def sgd_step(params, grads, bufs, lrs, wds, momentum, mscale=1.0, stats=None):
     if stats.dtype != torch.float64 or stats.numel() != 2 or not stats.is_contiguous():
         raise M3DError("sgd_step: stats must be a contiguous fp64 [2] tensor")
     _bn_ws(lambda ws, nb: L.m3d_sgd_step(arr, n, mom, msc, _ptr(stats), ws, nb, st), stats.device, "sgd_step")
+
+
+def _step_lists(tag, named, scalars):
+    """the argument checks of sgd_step for `named` = ((name, list of tensors or None entries), ...), the first of which gives the sizes,
+    and `scalars` = lists with one float per tensor"""
+    n = len(named[0][1])
+    if not all(len(l) == n for _, l in named) or not all(len(s) == n for s in scalars):
+        raise M3DError("%s: %s and the per-tensor scalars must have one entry per tensor" % (tag, ", ".join(k for k, _ in named)))
+    for i in range(n):
+        p = named[0][1][i]
+        for name, l in named:
+            t = l[i]
+            if t is None and name == "bufs":
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise M3DError("%s: %s[%d] must be a CUDA (ROCm) tensor; there is no CPU path" % (tag, name, i))
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                raise M3DError("%s: %s[%d] must be a contiguous fp32 tensor of %d elements" % (tag, name, i, p.numel()))
+    return n
+
+
+def _step_scalar(tag, name, t, dtype):
+    """a device scalar argument (stats fp64 [2], gscale / coef fp32 [1]) -> its pointer, or NULL for None"""
+    if t is None:
+        return None
+    count = 2 if dtype == torch.float64 else 1
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise M3DError("%s: %s must be a CUDA (ROCm) tensor; there is no CPU path" % (tag, name))
+    if t.dtype != dtype or t.numel() != count or not t.is_contiguous():
+        raise M3DError("%s: %s must be a contiguous %s [%d] tensor" % (tag, name, "fp64" if dtype == torch.float64 else "fp32", count))
+    return _ptr(t)
+
+
+def sgd_step_scaled(params, grads, bufs, lrs, wds, momentum, mscale=1.0, stats=None, gscale=None):
+    """m3d_sgd_step_scaled: sgd_step with d = s g in front of the decay term, s = gscale, a CUDA fp32 scalar tensor that the kernel reads
+    (the coefficient grad_clip_coef wrote); the statistics stay those of the raw gradients.  gscale=None gives the bits of sgd_step."""
+    if bufs is None:
+        bufs = [None] * len(params)
+    n = _step_lists("sgd_step_scaled", (("params", params), ("grads", grads), ("bufs", bufs)), (lrs, wds))
+    arr = (SgdTensor * max(n, 1))()
+    for i in range(n):
+        p, g, m, e = params[i], grads[i], bufs[i], arr[i]
+        e.p, e.g, e.m, e.n, e.lr, e.wd = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), p.numel(), lrs[i], wds[i]
+    L, st = lib(), _stream()
+    mom, msc = C.c_float(float(momentum)), C.c_float(float(mscale))
+    gs = _step_scalar("sgd_step_scaled", "gscale", gscale, torch.float32)
+    sp = _step_scalar("sgd_step_scaled", "stats", stats, torch.float64)
+    if stats is None:
+        check(L.m3d_sgd_step_scaled(arr, n, mom, msc, gs, None, None, None, st), "sgd_step_scaled")
+        return
+    _bn_ws(lambda ws, nb: L.m3d_sgd_step_scaled(arr, n, mom, msc, gs, sp, ws, nb, st), stats.device, "sgd_step_scaled")
+
+
+def adam_scalars(lr, step, betas):
+    """-> (lr_step, bc2_sqrt) of a parameter at its step count `step` (1 at its first step), in Python doubles exactly as the
+    single-tensor torch.optim.Adam of this torch forms step_size and bias_correction2_sqrt; m3d_adam_step rounds them to fp32"""
+    step = float(step)
+    bias_correction1 = 1 - betas[0] ** step
+    bias_correction2 = 1 - betas[1] ** step
+    return lr / bias_correction1, bias_correction2 ** 0.5
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, wds, steps, betas, eps, stats=None, gscale=None):
+    """m3d_adam_step: one fused torch.optim.Adam update (amsgrad off, maximize off, coupled weight decay) of a whole parameter list, in
+    place and on the current stream.
+
+    params, grads, exp_avgs, exp_avg_sqs: lists of contiguous CUDA fp32 tensors of equal sizes; lrs, wds: one float per tensor; steps:
+    each tensor's step count t INCLUDING this step (1 at its first); betas = (beta1, beta2), eps: floats.  Per element d = s g (with
+    gscale), d = d + wd p (d where wd == 0), m' = m + (1 - beta1)(d - m), v' = beta2 v + (1 - beta2)(d d), q = sqrt(v') / sqrt(1 -
+    beta2^t) + eps, p' = p - lr / (1 - beta1^t) (m' / q), every fp32 operation rounded once.  stats as in sgd_step (of the raw
+    gradients); gscale: None, or a CUDA fp32 scalar tensor the kernel reads.  Like sgd_step the update does not bump `_version`."""
+    n = _step_lists("adam_step", (("params", params), ("grads", grads), ("exp_avgs", exp_avgs), ("exp_avg_sqs", exp_avg_sqs)),
+                    (lrs, wds, steps))
+    arr = (AdamTensor * max(n, 1))()
+    for i in range(n):
+        p, e = params[i], arr[i]
+        if not steps[i] >= 1:
+            raise M3DError("adam_step: steps[%d] must be at least 1" % i)
+        lr_step, bc2_sqrt = adam_scalars(lrs[i], steps[i], betas)
+        e.p, e.g, e.m, e.v, e.n = p.data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(), p.numel()
+        e.lr_step, e.bc2_sqrt, e.wd = lr_step, bc2_sqrt, wds[i]
+    L, st = lib(), _stream()
+    b1, b2, ep = C.c_double(float(betas[0])), C.c_double(float(betas[1])), C.c_double(float(eps))
+    gs = _step_scalar("adam_step", "gscale", gscale, torch.float32)
+    sp = _step_scalar("adam_step", "stats", stats, torch.float64)
+    if stats is None:
+        check(L.m3d_adam_step(arr, n, b1, b2, ep, gs, None, None, None, st), "adam_step")
+        return
+    _bn_ws(lambda ws, nb: L.m3d_adam_step(arr, n, b1, b2, ep, gs, sp, ws, nb, st), stats.device, "adam_step")
+
+
+def grad_clip_coef(grads, clip_norm, stats, coef):
+    """m3d_grad_clip_coef: one read-only pass over `grads` (contiguous CUDA fp32 tensors) that writes (sum of g^2 in fp64, number of
+    non-finite elements) to `stats` (CUDA fp64 [2]) and clip_norm / max(sqrt(sum), clip_norm) to `coef` (CUDA fp32 scalar tensor) - the
+    coefficient of the reference's clip_gradient, 1 exactly when the norm does not exceed clip_norm.  Nothing comes back to the host."""
+    n = _step_lists("grad_clip_coef", (("grads", grads),), ())
+    if stats is None or coef is None:
+        raise M3DError("grad_clip_coef: stats and coef are required")
+    arr = (GradTensor * max(n, 1))()
+    for i in range(n):
+        arr[i].g, arr[i].n = grads[i].data_ptr(), grads[i].numel()
+    sp = _step_scalar("grad_clip_coef", "stats", stats, torch.float64)
+    cp = _step_scalar("grad_clip_coef", "coef", coef, torch.float32)
+    L, st, cn = lib(), _stream(), C.c_double(float(clip_norm))
+    _bn_ws(lambda ws, nb: L.m3d_grad_clip_coef(arr, n, cn, sp, cp, ws, nb, st), stats.device, "grad_clip_coef")

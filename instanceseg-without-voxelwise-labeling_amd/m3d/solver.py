@@ -1,9 +1,10 @@
-"""The reference's solver: SGD with its parameter groups, warm-up, step decay and momentum correction, on one fused update launch
-(csrc/sgd.hip), and its checkpoints.
+"""The reference's solver: SGD or Adam with its parameter groups, warm-up, step decay and (SGD) momentum correction, on one fused update
+launch (csrc/sgd.hip, csrc/adam.hip), an optional global-norm gradient clip that stays on the device, and its checkpoints.
 
-Reference: tools/train_net_step.py:286-489 (groups, schedule, loop order, save_ckpt at :122-139) and lib/utils/net.py:67-107
-(update_learning_rate, _CorrectMomentum).  DESIGN ("Solver") has the contract.  Construction, the schedule and the state dicts are host
-logic and work on CPU parameters; only step() needs the device."""
+Reference: tools/train_net_step.py:286-489 (groups, the optimiser choice at :330-333, schedule, loop order, save_ckpt at :122-139) and
+lib/utils/net.py:35-107 (clip_gradient, update_learning_rate, _CorrectMomentum).  DESIGN ("Solver") has the contract.  Construction, the
+schedule and the state dicts are host logic and work on CPU parameters; only step() needs the device."""
+import math
 import os
 
 import torch
@@ -17,7 +18,7 @@ class SolverCfg:
     """The SOLVER keys (and TRAIN.SNAPSHOT_ITERS) the solver reads; defaults = the nuclei YAML merged over lib/core/config.py."""
 
     def __init__(self, **kw):
-        self.TYPE = "SGD"
+        self.TYPE = "SGD"                                   # or "Adam" (train_net_step.py:330-333)
         self.LR_POLICY = "steps_with_decay"
         self.BASE_LR = 0.01
         self.GAMMA = 0.5
@@ -34,44 +35,70 @@ class SolverCfg:
         self.SCALE_MOMENTUM = True                          # config.py:612
         self.SCALE_MOMENTUM_THRESHOLD = 1.1                 # config.py:616
         self.SNAPSHOT_ITERS = 3000                          # TRAIN.SNAPSHOT_ITERS
+        self.BETAS = (0.9, 0.999)                           # Adam: torch.optim.Adam's defaults, which the reference leaves alone
+        self.EPS = 1e-8
+        self.CLIP_NORM = None                               # the clip_norm of clip_gradient (lib/utils/net.py:35-47); None: no clip
         unknown = sorted(set(kw) - set(self.__dict__))
         if unknown:
             raise TypeError("SolverCfg: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(sorted(self.__dict__))))
         self.__dict__.update(kw)
         self.STEPS = tuple(int(s) for s in self.STEPS)
-        if self.TYPE != "SGD":
-            raise ValueError("SolverCfg: SOLVER.TYPE %r is not built (SGD only)" % (self.TYPE,))
+        self.BETAS = tuple(float(b) for b in self.BETAS)
+        if self.TYPE not in ("SGD", "Adam"):
+            raise ValueError("SolverCfg: SOLVER.TYPE %r is not built (SGD and Adam only)" % (self.TYPE,))
         if self.LR_POLICY != "steps_with_decay":
             raise ValueError("SolverCfg: SOLVER.LR_POLICY %r is not built (steps_with_decay only)" % (self.LR_POLICY,))
+        if len(self.BETAS) != 2 or not all(0.0 <= b < 1.0 for b in self.BETAS) or not self.EPS > 0:
+            raise ValueError("SolverCfg: BETAS must be two values in [0, 1) and EPS positive")
+        if self.CLIP_NORM is not None and not (self.CLIP_NORM > 0 and math.isfinite(self.CLIP_NORM)):
+            raise ValueError("SolverCfg: CLIP_NORM must be None or positive and finite")
+
+    # what the soma YAML changes: SolverCfg(TYPE="Adam", **SolverCfg.SOMA) is its schedule under Adam
+    SOMA = dict(STEPS=(0, 3000, 6000, 9000), MAX_ITER=9000)
 
     @staticmethod
-    def nuclei(**kw):
+    def _shipped(name, kw):
+        """nuclei() and soma() are the two shipped YAML files, both SGD runs, and keep refusing another TYPE as they always have; a
+        configuration of another type is built with SolverCfg(TYPE=..., ...) itself"""
+        if kw.get("TYPE", "SGD") != "SGD":
+            raise ValueError("SolverCfg.%s: the shipped configuration is an SGD run; build SOLVER.TYPE %r with SolverCfg(TYPE=..., ...)"
+                             % (name, kw["TYPE"]))
         return SolverCfg(**kw)
 
     @staticmethod
+    def nuclei(**kw):
+        return SolverCfg._shipped("nuclei", kw)
+
+    @staticmethod
     def soma(**kw):
-        d = dict(STEPS=(0, 3000, 6000, 9000), MAX_ITER=9000)
+        d = dict(SolverCfg.SOMA)
         d.update(kw)
-        return SolverCfg(**d)
+        return SolverCfg._shipped("soma", d)
 
 
-def _group_defaults():
-    """the hyper-parameter keys of a torch.optim.SGD group of this torch, with their defaults"""
-    d = dict(torch.optim.SGD([torch.zeros(1)], lr=0.0).state_dict()["param_groups"][0])
+def _group_defaults(kind="SGD"):
+    """the hyper-parameter keys of a torch.optim.SGD / torch.optim.Adam group of this torch, with their defaults"""
+    d = dict(getattr(torch.optim, kind)([torch.zeros(1)], lr=0.0).state_dict()["param_groups"][0])
     d.pop("params")
     return d
 
 
+_ADAM_REFUSED = ("amsgrad", "maximize", "decoupled_weight_decay")
+
+
 class Solver:
-    """torch.optim.SGD as the reference builds and drives it.
+    """torch.optim.SGD, or with cfg.TYPE == "Adam" torch.optim.Adam, as the reference builds and drives it.
 
     named_parameters: (name, parameter) pairs, e.g. model.named_parameters().  requires_grad parameters with `bias` in the name form the
     bias group (twice the rate if BIAS_DOUBLE_LR, no decay unless BIAS_WEIGHT_DECAY), the rest the non-bias group; the GroupNorm group is
     kept and empty.  Loop order: begin_step(step), zero_grad(), forward, backward, step().  stats=True also fills `grad_sq` (sum of g^2
-    over the gradients of the step, fp64) and `nonfinite` (their non-finite elements) on the device."""
+    over the gradients of the step, fp64) and `nonfinite` (their non-finite elements) on the device.  With cfg.CLIP_NORM the gradients
+    enter the update scaled by `clip_coef` = CLIP_NORM / max(sqrt(grad_sq), CLIP_NORM), a device scalar that a pass over the gradients
+    writes in front of the update; nothing is read back, and the two statistics are there whatever `stats` says."""
 
     def __init__(self, named_parameters, cfg, start_step=0, stats=False):
         self.cfg = cfg
+        self.adam = cfg.TYPE == "Adam"
         nonbias, bias = [], []
         for name, p in named_parameters:
             if p.requires_grad:
@@ -82,8 +109,12 @@ class Solver:
         dev = params[0].device
         if any(p.device != dev or p.dtype != torch.float32 for p in params):
             raise ValueError("Solver: the parameters must be fp32 on one device")
-        hyper = _group_defaults()
-        hyper.update(momentum=cfg.MOMENTUM, dampening=0, nesterov=False)
+        hyper = _group_defaults(cfg.TYPE)
+        if self.adam:
+            hyper.update(betas=cfg.BETAS, eps=cfg.EPS)
+            assert not any(hyper.get(k) for k in _ADAM_REFUSED)
+        else:
+            hyper.update(momentum=cfg.MOMENTUM, dampening=0, nesterov=False)
 
         def group(ps, lr, wd):
             g = dict(hyper)
@@ -98,12 +129,20 @@ class Solver:
         for p in params:
             offs.append(at)
             at += (p.numel() + 3) // 4 * 4
-        self._flat = torch.zeros((at,), dtype=torch.float32, device=dev)
-        self._bufs = [self._flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
+
+        def flat():
+            f = torch.zeros((at,), dtype=torch.float32, device=dev)
+            return f, [f[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
+        self._flat, self._bufs = flat()          # SGD: the momentum buffers; Adam: exp_avg
+        if self.adam:
+            self._flat2, self._bufs2 = flat()    # exp_avg_sq
         self._live = [False] * len(params)       # torch creates a parameter's buffer at its first step with a gradient
-        self._stats = torch.zeros((2,), dtype=torch.float64, device=dev) if stats else None
+        self._steps = [0] * len(params)          # Adam: torch's state['step'], the steps at which the parameter had a gradient
+        clip = cfg.CLIP_NORM is not None
+        self._stats = torch.zeros((2,), dtype=torch.float64, device=dev) if (stats or clip) else None
+        self._coef = torch.ones((1,), dtype=torch.float32, device=dev) if clip else None
         self.lr = self.param_groups[0]["lr"]
-        self.mscale = 1.0                        # pending momentum correction: handed to the next launch, then 1 again
+        self.mscale = 1.0                        # pending momentum correction: handed to the next launch, then 1 again (SGD only)
         self.start_step = start_step
 
     # ------------------------------------------------------------------ schedule
@@ -128,7 +167,7 @@ class Solver:
         ratio = max(new / max(lr, 1e-10), lr / max(new, 1e-10))
         for i, g in enumerate(self.param_groups):
             g["lr"] = new * 2 if (i == 1 and c.BIAS_DOUBLE_LR) else new
-        if c.SCALE_MOMENTUM and lr > 1e-7 and ratio > c.SCALE_MOMENTUM_THRESHOLD:
+        if not self.adam and c.SCALE_MOMENTUM and lr > 1e-7 and ratio > c.SCALE_MOMENTUM_THRESHOLD:      # net.py:81: SGD only
             self.mscale *= new / lr
         self.lr = new
 
@@ -160,15 +199,21 @@ class Solver:
     def nonfinite(self):
         return None if self._stats is None else self._stats[1]
 
+    @property
+    def clip_coef(self):
+        """the coefficient the last step() scaled its gradients by: a 0-d device tensor, None without CLIP_NORM"""
+        return None if self._coef is None else self._coef[0]
+
     def zero_grad(self):
         for p in self._params:
             p.grad = None
 
     def step(self):
-        """One ops.sgd_step launch on the current stream over every parameter that has a gradient, then the cached conv / linear packs
-        are dropped: the kernel writes through raw pointers and does not bump `_version`."""
-        ps, gs, ms, lrs, wds = [], [], [], [], []
-        momentum = self.param_groups[0]["momentum"]
+        """With CLIP_NORM one ops.grad_clip_coef pass, then one ops.sgd_step / ops.adam_step launch, on the current stream over every
+        parameter that has a gradient; then the cached conv / linear packs are dropped: the kernels write through raw pointers and do
+        not bump `_version`."""
+        ps, gs, ms, vs, lrs, wds, steps, stepped = [], [], [], [], [], [], [], []
+        momentum = 0 if self.adam else self.param_groups[0]["momentum"]
         i = 0
         for g in self.param_groups:
             for p in g["params"]:
@@ -180,16 +225,33 @@ class Solver:
                     ms.append(self._bufs[i])
                     lrs.append(g["lr"])
                     wds.append(g["weight_decay"])
-                    self._live[i] = momentum != 0            # torch keeps no buffer without momentum
-                elif self._live[i] and self.mscale != 1.0:
+                    stepped.append(i)
+                    if self.adam:
+                        vs.append(self._bufs2[i])
+                        steps.append(self._steps[i] + 1)
+                    else:
+                        self._live[i] = momentum != 0            # torch keeps no buffer without momentum
+                elif not self.adam and self._live[i] and self.mscale != 1.0:
                     self._bufs[i].mul_(self.mscale)          # the correction reaches a buffer whose parameter sits this step out
                 i += 1
-        ops.sgd_step(ps, gs, ms if momentum != 0 else None, lrs, wds, momentum, self.mscale, self._stats)
+        clip = self._coef is not None
+        if clip:
+            ops.grad_clip_coef(gs, self.cfg.CLIP_NORM, self._stats, self._coef)
+        if self.adam:
+            g0 = self.param_groups[0]
+            ops.adam_step(ps, gs, ms, vs, lrs, wds, steps, g0["betas"], g0["eps"], None if clip else self._stats, self._coef)
+            for i in stepped:
+                self._steps[i] += 1
+                self._live[i] = True
+        elif clip:
+            ops.sgd_step_scaled(ps, gs, ms if momentum != 0 else None, lrs, wds, momentum, self.mscale, None, self._coef)
+        else:
+            ops.sgd_step(ps, gs, ms if momentum != 0 else None, lrs, wds, momentum, self.mscale, self._stats)
         self.mscale = 1.0
         from . import compat
         compat.invalidate_packs()
 
-    # ------------------------------------------------------------------ torch.optim.SGD's state dict
+    # ------------------------------------------------------------------ torch.optim.SGD's / torch.optim.Adam's state dict
     def state_dict(self):
         state, groups, at = {}, [], 0
         for g in self.param_groups:
@@ -198,7 +260,12 @@ class Solver:
             at += len(g["params"])
             groups.append(d)
         for i, b in enumerate(self._bufs):
-            if self._live[i]:
+            if not self._live[i]:
+                continue
+            if self.adam:
+                state[i] = {"step": torch.tensor(float(self._steps[i]), dtype=torch.float32), "exp_avg": b.clone(),
+                            "exp_avg_sq": self._bufs2[i].clone()}
+            else:
                 state[i] = {"momentum_buffer": b * self.mscale if self.mscale != 1.0 else b.clone()}
         return {"state": state, "param_groups": groups}
 
@@ -206,15 +273,36 @@ class Solver:
         groups = sd["param_groups"]
         if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"]) for a, b in zip(groups, self.param_groups)):
             raise ValueError("Solver.load_state_dict: the saved parameter groups do not match this model's")
-        if len({float(g.get("momentum", 0)) for g in groups}) != 1:
+        if any(("betas" in g) != self.adam for g in groups):
+            raise ValueError("Solver.load_state_dict: the saved state is %s's, this solver is %s"
+                             % (("torch.optim.SGD", "Adam") if self.adam else ("torch.optim.Adam", "SGD")))
+        if self.adam:
+            if any(g.get(k) for g in groups for k in _ADAM_REFUSED):
+                raise ValueError("Solver.load_state_dict: %s are not built" % ", ".join(_ADAM_REFUSED))
+            if len({(tuple(float(b) for b in g["betas"]), float(g["eps"])) for g in groups}) != 1:
+                raise ValueError("Solver.load_state_dict: one betas and eps for all groups")
+        elif len({float(g.get("momentum", 0)) for g in groups}) != 1:
             raise ValueError("Solver.load_state_dict: one momentum for all groups")
         for mine, saved in zip(self.param_groups, groups):
             mine.update({k: v for k, v in saved.items() if k != "params"})
+            if self.adam:
+                mine["betas"] = tuple(float(b) for b in mine["betas"])
         order = [j for g in groups for j in g["params"]]       # saved index of our parameter i
         with torch.no_grad():
             for i, j in enumerate(order):
                 st = sd["state"].get(j)
-                if st is not None and st.get("momentum_buffer") is not None:
+                if self.adam:
+                    if st is not None and st.get("exp_avg") is not None:
+                        self._bufs[i].copy_(st["exp_avg"].reshape(self._bufs[i].shape))
+                        self._bufs2[i].copy_(st["exp_avg_sq"].reshape(self._bufs[i].shape))
+                        self._steps[i] = int(round(float(st["step"])))
+                        self._live[i] = True
+                    else:
+                        self._bufs[i].zero_()
+                        self._bufs2[i].zero_()
+                        self._steps[i] = 0
+                        self._live[i] = False
+                elif st is not None and st.get("momentum_buffer") is not None:
                     self._bufs[i].copy_(st["momentum_buffer"].reshape(self._bufs[i].shape))
                     self._live[i] = True
                 else:
