@@ -42,7 +42,9 @@ const char* m3d_last_hip_error(void);
  * "tune_fc_x_alias" (> 0: m3d_linear_bf16x3_forward reads row m of x from row m % value - a cache-resident operand, WRONG results:
  * the GEMM's cost with a free operand, tools/f1_ab.py), "tune_stem" (4 / 8: the stem's rows kernel with that many planes per workgroup; any other value: planes by
  * grid size), "tune_fc_x3_rows" = 512 (the 256 x 256 tiles of m3d_linear_f16x2_forward), "tune_roi_xcd" (1: RoIAlign3D's XCD-aware
- * channel split - every XCD one eighth of every RoI's channels; an A/B that removed the L2 misses and not the time, round 6).
+ * channel split - every XCD one eighth of every RoI's channels; an A/B that removed the L2 misses and not the time, round 6),
+ * "tune_zw_grid" (> 0: the m3d_conv3d_zw_* launches start min(value, units) persistent workgroups instead of the library's count, so that
+ * each walks more units - the same results bit for bit; for the walk tests and A/B tools, -1 = library chooses).
  * Unknown name -> M3D_EINVAL. */
 int m3d_set_option(const char* name, int value);
 int m3d_get_option(const char* name, int* value);

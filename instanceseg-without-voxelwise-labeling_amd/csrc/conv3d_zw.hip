@@ -632,7 +632,11 @@ int launch_zw(ZwArgs a, hipStream_t st) {
     if (cus <= 0) cus = 256;
   }
   const long long rounds = (units + cus - 1) / cus;
-  const long long blocks = (units + rounds - 1) / rounds;
+  long long blocks = (units + rounds - 1) / rounds;
+  // option tune_zw_grid (tuning build only; the walk tests and A/B tools): that many workgroups, each walking more units.  The kernel
+  // strides by gridDim.x, so any grid of at most `units` computes the same values
+  const int tune_grid = m3d::opt(m3d::OPT_TUNE_ZW_GRID);
+  if (tune_grid > 0) blocks = tune_grid < units ? tune_grid : units;
 #ifdef M3D_ZW_STAMPS
   a.stamps = g_zw_stamps;
 #endif

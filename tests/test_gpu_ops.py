@@ -862,6 +862,7 @@ def test_library_options_are_explicit(m3d):
     assert _lib.lib().m3d_tuning_build() == 0                                  # the library the product path uses
     assert _lib.lib().m3d_set_option(b"xcd_map", 0) == -4                      # M3D_EUNSUPPORTED
     assert _lib.get_option("xcd_map") == 1 and _lib.get_option("tune_wino2") == -1
+    assert _lib.get_option("tune_zw_grid") == -1 and _lib.lib().m3d_set_option(b"tune_zw_grid", 8) == -4
     with pytest.raises(m3d.M3DError):
         _lib.set_option("tune_stem", 4)
     x = torch.randn(1, 32, 8, 16, 64, device="cuda")
@@ -875,12 +876,15 @@ def test_library_options_are_explicit(m3d):
         _lib.set_option("xcd_map", 1)
         b = conv(x)
         _lib.set_option("tune_stem", 4)
+        _lib.set_option("tune_zw_grid", 8)
+        assert _lib.get_option("tune_zw_grid") == 8
         with pytest.raises(m3d.M3DError):
             _lib.set_option("no_such_option", 1)
     assert torch.equal(a, b) and torch.equal(a, ref)  # the tile order is a speed option, never a result option
     assert _lib.lib().m3d_tuning_build() == 0
     with _lib.tuning():
         assert _lib.get_option("tune_stem") == -1 and _lib.get_option("xcd_map") == 1     # reset when the previous block ended
+        assert _lib.get_option("tune_zw_grid") == -1
 
 
 @pytest.mark.parametrize("shape", [(5, 6, 7), (64, 64, 64), (128, 128, 128)])
