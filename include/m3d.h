@@ -681,6 +681,15 @@ int m3d_prm_stem_dgrad_fused_ex2(const float* d_gup, int gup_strip, int gup_slab
                                  const uint8_t* d_argmax, const float* d_scale, int up_depth, int up_height, int up_width,
                                  const float* d_wa, const float* d_data, const float* d_data_offset, int depth, int height, int width,
                                  float* d_out, float* d_sums, int32_t* d_origins_out, void* stream);
+/* Which kernel a shape runs (host only, no GPU touched; the launchers ask the same functions, so a test can name the path it checks):
+ *   m3d_prm_prepare_plan     the kernel of m3d_prm_prepare_ex3 for a 16-byte-aligned d_out: 0 element (one thread per voxel), 1 / 2 / 3
+ *                            quad (four columns per thread on the quad-aligned strip, 8 / 16 / 32 lanes across a row), 4 pool (one
+ *                            thread per 2x2x2 block); or the negative M3D_E* code the call returns for this shape.  `depth` (> 0) decides
+ *                            with out_slab only.  An unaligned d_out runs the element kernel in place of a quad one.
+ *   m3d_prm_stem_dgrad_plan  the thread layout of m3d_prm_stem_dgrad for win^3 windows: 0 = 32 x 16 x 8 voxels per workgroup,
+ *                            1 = 40 x 12 x 8; M3D_EINVAL for win <= 0. */
+int m3d_prm_prepare_plan(int channels, int num_peaks, int up_size, int pool, int border, int out_strip, int out_slab, int depth);
+int m3d_prm_stem_dgrad_plan(int win);
 
 /* 3x3x3 "same" convolution at fp32 accuracy on the bf16 matrix cores (csrc/conv3d_x3.hip; round 4): out = conv3d(x - *d_in_offset, W',
  * padding = 1) with W' = W or relu(W) chosen at pack time - the norm convolution of lib/prm/peak_backprop_3d.py:37-44 (pr_conv3d's second

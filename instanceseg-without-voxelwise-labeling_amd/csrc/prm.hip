@@ -534,6 +534,43 @@ __global__ __launch_bounds__(256) void prm_scatter_kernel(const float* __restric
   }
 }
 
+// ---- which kernel a shape runs: ONE host function per launcher, asked by the launcher and by the m3d_prm_*_plan queries ----
+enum PrepKernel { PREP_ELEMENT = 0, PREP_QUAD8 = 1, PREP_QUAD16 = 2, PREP_QUAD32 = 3, PREP_POOL = 4 };
+
+// The kernel m3d_prm_prepare_ex3 launches for a 16-byte-aligned d_out (an unaligned one turns a quad id into PREP_ELEMENT), or the
+// M3D_E* code it returns for this shape.
+int prep_plan(int channels, int num_peaks, int up_size, int pool, int border, int out_strip, int out_slab, int depth) {
+  if (num_peaks < 0 || channels <= 0 || up_size <= 0 || border < 0 || depth <= 0) return M3D_EINVAL;
+  if (out_strip < 0 || out_strip > 2 || (out_slab && !out_strip)) return M3D_EINVAL;
+  if (channels > 65535 || num_peaks > 65535) return M3D_EUNSUPPORTED;
+  const int Wn = (pool ? 2 : 1) * up_size + 2 * border, ozn = out_slab ? depth : 0;
+  if (pool) {
+    if (border > 2) return M3D_EUNSUPPORTED;      // the one-block shell covers borders of 1 or 2 voxels
+    if (up_size + 2 > 100 || ozn > 200) return M3D_EUNSUPPORTED;        // float reciprocal index split in the kernel
+    return PREP_POOL;
+  }
+  if (Wn > 100 || ozn > 100) return M3D_EUNSUPPORTED;                   // float reciprocal index split in the kernel
+  if (out_strip == 2) {                                                 // quad-aligned strip: four columns per thread, 16-byte stores
+    int pitch, lead; long long L;
+    m3d::strip_geom(Wn, 2, num_peaks, &pitch, &lead, &L);
+    const int tail = (int)(L - (long long)num_peaks * pitch);
+    const int nq = pitch / 4 + tail / 4;
+    // (L is a multiple of 4, hence so are the row, plane and channel strides n L, L and zn n L of the strip)
+    if (pitch % 4 == 0 && tail % 4 == 0 && nq <= 32 && L % 4 == 0) return nq <= 8 ? PREP_QUAD8 : (nq <= 16 ? PREP_QUAD16 : PREP_QUAD32);
+  }
+  return PREP_ELEMENT;
+}
+
+// thread layout of prm_stem_dgrad_kernel for win^3 windows: 0 = <4,8> (32 x 16 x 8 voxels), 1 = <5,6> (40 x 12 x 8): the useful
+// fraction of the computed tile volume decides (84^3: 32x16x8 -> 73 %, 40x12x8 -> 70 %; 40^3: 52 % vs 78 %)
+int stem_dgrad_plan(int win) {
+  auto eff = [&](int TX, int TY, double threads) {
+    const double cx = (double)((win + TX - 1) / TX) * TX, cy = (double)((win + TY - 1) / TY) * TY, cz = (double)((win + 7) / 8) * 8;
+    return (double)win * win * win / (cx * cy * cz) * threads;
+  };
+  return eff(40, 12, 240.0 / 256.0) > eff(32, 16, 1.0) ? 1 : 0;
+}
+
 }  // namespace
 
 namespace m3d {
@@ -642,34 +679,30 @@ M3D_API int m3d_prm_prepare_ex3(const float* d_gup, const int32_t* d_origin_up, 
       !strides(q.Wn, q.ozn, out_strip, &q.ops, &q.ocs, &q.ozs, &q.oys, &obase, true))
     return M3D_EUNSUPPORTED;
   q.gup = d_gup + ibase; q.out = d_out + obase;
-  if (channels > 65535 || num_peaks > 65535) return M3D_EUNSUPPORTED;
-  if (pool) {
-    if (border > 2) return M3D_EUNSUPPORTED;      // the one-block shell covers borders of 1 or 2 voxels
+  int kern = prep_plan(channels, num_peaks, up_size, pool, border, out_strip, out_slab, depth);
+  if (kern < 0) return kern;
+  if (kern >= PREP_QUAD8 && kern <= PREP_QUAD32 && (((uintptr_t)d_out) & 15) != 0) kern = PREP_ELEMENT;       // 16-byte stores
+  if (kern == PREP_POOL) {
     const int ub = up_size + 2;
-    if (ub > 100 || q.ozn > 200) return M3D_EUNSUPPORTED;        // float reciprocal index split in the kernel
     const int blocks = ((q.ozn ? (q.ozn + 1) / 2 : ub) * ub * ub + 255) / 256;
     int chunks = (int)((16384 + (long long)channels * num_peaks - 1) / ((long long)channels * num_peaks));
     chunks = chunks < 1 ? 1 : (chunks > blocks ? blocks : chunks);
     hipLaunchKernelGGL(prm_prepare_pool_kernel, dim3(chunks, channels, num_peaks), dim3(256), 0, m3d::as_stream(stream), q);
   } else {
-    if (q.Wn > 100 || q.ozn > 100) return M3D_EUNSUPPORTED;        // float reciprocal index split in the kernel
-    if (out_strip == 2) {                                           // quad-aligned strip: four columns per thread, 16-byte stores
+    if (kern != PREP_ELEMENT) {                                     // quad-aligned strip: four columns per thread, 16-byte stores
       int pitch, lead; long long L;
       m3d::strip_geom(q.Wn, 2, num_peaks, &pitch, &lead, &L);
       const int tail = (int)(L - (long long)num_peaks * pitch);
-      const int nq = pitch / 4 + tail / 4;
-      if (pitch % 4 == 0 && tail % 4 == 0 && nq <= 32 && (((uintptr_t)d_out) & 15) == 0 && (q.ozs % 4 == 0) && (q.oys % 4 == 0) && (q.ocs % 4 == 0)) {
-        const int tx = nq <= 8 ? 8 : (nq <= 16 ? 16 : 32);
-        const int rows = (q.ozn ? q.ozn : q.Wn) * q.Wn, rpb = 256 / tx;
-        int chunks = (int)((16384 + (long long)channels * num_peaks - 1) / ((long long)channels * num_peaks));
-        const int maxc = (rows + rpb - 1) / rpb;
-        chunks = chunks < 1 ? 1 : (chunks > maxc ? maxc : chunks);
-        const dim3 grid(chunks, channels, num_peaks);
-        if (tx == 8) hipLaunchKernelGGL(prm_prepare_quad_kernel<8>, grid, dim3(256), 0, m3d::as_stream(stream), q, pitch, lead, tail);
-        else if (tx == 16) hipLaunchKernelGGL(prm_prepare_quad_kernel<16>, grid, dim3(256), 0, m3d::as_stream(stream), q, pitch, lead, tail);
-        else hipLaunchKernelGGL(prm_prepare_quad_kernel<32>, grid, dim3(256), 0, m3d::as_stream(stream), q, pitch, lead, tail);
-        return m3d::check_launch("prm_prepare");
-      }
+      const int tx = kern == PREP_QUAD8 ? 8 : (kern == PREP_QUAD16 ? 16 : 32);
+      const int rows = (q.ozn ? q.ozn : q.Wn) * q.Wn, rpb = 256 / tx;
+      int chunks = (int)((16384 + (long long)channels * num_peaks - 1) / ((long long)channels * num_peaks));
+      const int maxc = (rows + rpb - 1) / rpb;
+      chunks = chunks < 1 ? 1 : (chunks > maxc ? maxc : chunks);
+      const dim3 grid(chunks, channels, num_peaks);
+      if (tx == 8) hipLaunchKernelGGL(prm_prepare_quad_kernel<8>, grid, dim3(256), 0, m3d::as_stream(stream), q, pitch, lead, tail);
+      else if (tx == 16) hipLaunchKernelGGL(prm_prepare_quad_kernel<16>, grid, dim3(256), 0, m3d::as_stream(stream), q, pitch, lead, tail);
+      else hipLaunchKernelGGL(prm_prepare_quad_kernel<32>, grid, dim3(256), 0, m3d::as_stream(stream), q, pitch, lead, tail);
+      return m3d::check_launch("prm_prepare");
     }
     const int blocks = ((q.ozn ? q.ozn : q.Wn) * q.Wn * q.Wn + 255) / 256;
     int chunks = (int)((16384 + (long long)channels * num_peaks - 1) / ((long long)channels * num_peaks));   // >= 16 k workgroups
@@ -687,6 +720,18 @@ M3D_API int64_t m3d_prm_strip_geometry(int window, int mode, int num_peaks, int3
   if (pitch) *pitch = pp;
   if (lead) *lead = ll;
   return (int64_t)L;
+}
+
+/* Host only: the kernel m3d_prm_prepare_ex3 launches for this shape when d_out is 16-byte aligned - 0 element, 1 / 2 / 3 quad<8> / <16> /
+ * <32> (lanes across a row's quads), 4 pool - or the negative M3D_E* code the call returns.  The launcher asks the same function. */
+M3D_API int m3d_prm_prepare_plan(int channels, int num_peaks, int up_size, int pool, int border, int out_strip, int out_slab, int depth) {
+  return prep_plan(channels, num_peaks, up_size, pool, border, out_strip, out_slab, depth);
+}
+
+/* Host only: the thread layout m3d_prm_stem_dgrad launches for win^3 windows - 0 = <4,8> (tile 32 x 16 x 8), 1 = <5,6> (40 x 12 x 8). */
+M3D_API int m3d_prm_stem_dgrad_plan(int win) {
+  if (win <= 0) return M3D_EINVAL;
+  return stem_dgrad_plan(win);
 }
 
 M3D_API int m3d_prm_prepare(const float* d_gup, const int32_t* d_origin_up, int num_peaks, int channels, int up_size, int pool,
@@ -743,12 +788,7 @@ M3D_API int m3d_prm_stem_dgrad(const float* d_gn, const float* d_wf, const float
     hipLaunchKernelGGL(kern, dim3(tx * ty * tz, num_peaks), dim3(256), lds, m3d::as_stream(stream), d_gn, d_wf, d_data,
                        d_data_offset, d_origins, win, win, win, depth, height, width, channels, d_out, d_sums);
   };
-  // useful fraction of the computed tile volume decides the layout (84^3: 32x16x8 -> 73 %, 40x12x8 -> 70 %; 40^3: 52 % vs 78 %)
-  auto eff = [&](int TX, int TY, double threads) {
-    const double cx = (double)((win + TX - 1) / TX) * TX, cy = (double)((win + TY - 1) / TY) * TY, cz = (double)((win + 7) / 8) * 8;
-    return (double)win * win * win / (cx * cy * cz) * threads;
-  };
-  if (eff(40, 12, 240.0 / 256.0) > eff(32, 16, 1.0))
+  if (stem_dgrad_plan(win) == 1)
     launch(prm_stem_dgrad_kernel<5, 6, false>, 40, 12, SDG<5, 6>::TILE);
   else
     launch(prm_stem_dgrad_kernel<4, 8, false>, 32, 16, SDG<4, 8>::TILE);

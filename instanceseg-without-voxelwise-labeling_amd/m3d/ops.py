@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1277,6 +1277,25 @@ def strip_geometry(n, mode, P):
     pitch, lead = C.c_int32(0), C.c_int32(0)
     L = lib().m3d_prm_strip_geometry(int(n), int(mode), int(P), C.byref(pitch), C.byref(lead))
     return pitch.value, lead.value, int(L)
+
+
+PRM_PREPARE_KERNELS = ("element", "quad<8>", "quad<16>", "quad<32>", "pool")
+PRM_STEM_DGRAD_LAYOUTS = ("<4,8>", "<5,6>")
+
+
+def prm_prepare_plan(channels, num_peaks, up_size, pool, border, out_strip=0, out_slab=False, depth=1):
+    """The kernel prm_prepare launches for this shape (m3d_prm_prepare_plan, host only; an output that is 16-byte aligned, as every
+    torch allocation is): one of PRM_PREPARE_KERNELS, or None where the library refuses the shape."""
+    rc = lib().m3d_prm_prepare_plan(int(channels), int(num_peaks), int(up_size), int(bool(pool)), int(border), int(out_strip),
+                                    int(bool(out_slab)), int(depth))
+    return PRM_PREPARE_KERNELS[rc] if rc >= 0 else None
+
+
+def prm_stem_dgrad_plan(win):
+    """The thread layout prm_stem_dgrad launches for win^3 windows (m3d_prm_stem_dgrad_plan, host only): one of PRM_STEM_DGRAD_LAYOUTS."""
+    rc = lib().m3d_prm_stem_dgrad_plan(int(win))
+    check(min(rc, 0), "prm_stem_dgrad_plan")
+    return PRM_STEM_DGRAD_LAYOUTS[rc]
 
 
 def prm_prepare(gup, origin_up, pool, border, argmax, xnext, scale, norm, in_strip=False, out_strip=False, up_off=None, dims=None,
