@@ -191,7 +191,10 @@ int m3d_conv3d_forward(const float* d_in, const float* d_packed, float* d_out, i
 int m3d_conv3d_forward_split_sigmoid(const float* d_in, const float* d_packed, float* d_out_sigmoid, float* d_out_rest, int batch, int cin,
                                      int cout, int split, int depth, int height, int width, int k, const float* d_shift, void* stream);
 /* 3x3x3 "same" convolution with dilation 2 / padding 2 (dilation 1 = m3d_conv3d_forward): the convolutions of the mask head
- * (lib/modeling/mask_rcnn_heads.py:148-151 with MRCNN.DILATION = 2, lib/core/config.py:767).  d_packed: m3d_conv3d_pack_weights. */
+ * (lib/modeling/mask_rcnn_heads.py:148-151 with MRCNN.DILATION = 2, lib/core/config.py:767).  d_packed: m3d_conv3d_pack_weights.
+ * With the M3D_W_DGRAD pack of a layer's weights, that layer's output gradient as d_in, cin and cout exchanged and d_scale = d_shift =
+ * NULL, relu = 0 it is the layer's backward-data (padding = dilation makes the transposed conv the same dilated conv of the flipped,
+ * transposed weights).  k = 3 and dilation 2 only; any other (k, dilation > 1) is M3D_EUNSUPPORTED. */
 int m3d_conv3d_forward_dilated(const float* d_in, const float* d_packed, float* d_out, int batch, int cin, int cout, int depth,
                                int height, int width, int k, int dilation, const float* d_scale, const float* d_shift, int relu,
                                void* stream);
@@ -294,6 +297,33 @@ int m3d_conv3d_wgrad(const float* d_in, const float* d_grad_out, float* d_grad_w
                      int depth, int height, int width, int k, void* d_ws, size_t ws_bytes, void* stream);
 int m3d_conv3d_bias_grad(const float* d_grad_out, float* d_grad_bias, int batch, int cout, int depth, int height,
                          int width, void* stream);
+/* Backward-weights of the dilated "same" convolution of m3d_conv3d_forward_dilated (padding = dilation): what autograd computes for the
+ * nn.Conv3d(dim, dim, 3, 1, padding=d, dilation=d) layers of lib/modeling/mask_rcnn_heads.py:141-151 with MRCNN.DILATION = d in training:
+ *   dW[co,ci,dz,dy,dx] = sum_{b,z,y,x} gy[b,co,z,y,x] * x[b,ci, z+d(dz-1), y+d(dy-1), x+d(dx-1)]          (zero outside the volume)
+ *   dilation 1     m3d_conv3d_wgrad / m3d_conv3d_wgrad_workspace_bytes with the same arguments: bit-equal, every k it takes.
+ *   k 3, dilation 2  csrc/conv3d_wgrad_dilated.hip: the fp32 MFMA implicit GEMM of m3d_conv3d_wgrad (v_mfma_f32_32x32x2_f32, fp32
+ *                  operands and accumulation) on a voxel tile with a 2-voxel halo: 2 x 8 x 8 for maps at most 8 wide (the 7^3 RoI
+ *                  grid), 2 x 4 x 16 beyond.  `slots` split-K partials (a function of the shape only, m3d_conv3d_wgrad_dilated_plan)
+ *                  go to the workspace; a reduce launch adds them in slot order.  No atomics: bit-identical run to run.  Writes every
+ *                  element of d_grad_weight [cout,cin,3,3,3] and at most workspace_bytes of d_ws, nothing else.
+ * Refusals, all before a pointer is followed or anything is launched (so with any non-NULL pointers on a machine without a GPU):
+ * M3D_EINVAL a NULL pointer or a non-positive extent; M3D_EUNSUPPORTED any other (k, dilation), cin or cout * depth * height * width
+ * * 4 bytes >= 2^31 - 1 (one image is addressed with 32-bit offsets), 2^31 voxel tiles or workgroups (workspace_bytes is then 0);
+ * M3D_EWORKSPACE ws_bytes below workspace_bytes.
+ * Backward-data needs no entry point of its own: with padding = dilation, gx is m3d_conv3d_forward_dilated of gy on the M3D_W_DGRAD
+ * pack (cin and cout exchanged, d_scale = d_shift = NULL, relu = 0).
+ * m3d_conv3d_wgrad_dilated_tile (dilation 2 only; dilation 1 is M3D_EUNSUPPORTED): the same with the tile's x extent chosen by the
+ * caller (16: 2 x 4 x 16, 8: 2 x 8 x 8, 0: the library's choice; anything else M3D_EUNSUPPORTED) on the same workspace - the A/B tool
+ * and the tests of both forms.  _plan (host only; any output pointer may be NULL; dilation 2 only) reports the tile and the slot
+ * count of such a call and returns what it would return for its shape. */
+size_t m3d_conv3d_wgrad_dilated_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width, int k, int dilation);
+int m3d_conv3d_wgrad_dilated(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout, int depth,
+                             int height, int width, int k, int dilation, void* d_ws, size_t ws_bytes, void* stream);
+int m3d_conv3d_wgrad_dilated_tile(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                  int depth, int height, int width, int k, int dilation, int tile_x, void* d_ws, size_t ws_bytes,
+                                  void* stream);
+int m3d_conv3d_wgrad_dilated_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int dilation, int tile_x,
+                                  int* tile_x_out, int* tile_y_out, int* slots_out);
 /* The k = 3 weight gradient above on the f16 matrix cores at fp32 accuracy (csrc/conv3d_wgrad_f16.hip): the f16x2 cut of
  * m3d_conv3d_zw_forward - each operand tensor scaled by ONE power of two (m3d::f16_scale_of of its bound) and cut into two fp16
  * numbers while it is staged, three v_mfma_f32_32x32x16_f16 products hh + hl + lh per fp32 product, fp32 accumulation, the sum

@@ -1,0 +1,280 @@
+// Backward-weights of the 3x3x3 "same" convolution with dilation 2 (padding 2) as an fp32 MFMA implicit GEMM for gfx950:
+//   dW[co,ci,dz,dy,dx] = sum_{b,z,y,x} gy[b,co,z,y,x] * x[b,ci,z+2(dz-1),y+2(dy-1),x+2(dx-1)]        (zero outside the volume)
+// Reference: the gradient autograd computes for the nn.Conv3d(dim, dim, 3, 1, padding=d, dilation=d) layers of
+// lib/modeling/mask_rcnn_heads.py:141-151 with MRCNN.DILATION = 2 (lib/core/config.py:767) during training.
+//
+// The scheme of conv3d_wgrad.hip (M = 32 cout, N = 32 cin per tap, K = voxel pairs of v_mfma_f32_32x32x2f32, both operands staged
+// through LDS as [channel][voxel] with an odd channel stride, the 27 taps split over the 4 waves, split-K partials summed by a second
+// launch in slot order) with the halo widened to DIL voxels and the tap offset scaled by DIL.  It lives in a file of its own so that
+// the dilation-1 kernel's code object stays what it was.  Two voxel tiles, both 128 voxels:
+//   2 x 4 x 16  halo 6 x 8 x 20 = 960 floats per channel, LDS 32 * 129 + 32 * 961 floats = 139.5 KB
+//   2 x 8 x 8   halo 6 x 12 x 12 = 864 floats per channel, LDS 127.2 KB; a 7^3 RoI grid is 4 of these tiles, not 8
+// One workgroup per CU either way (160 KiB LDS).  make_plan picks by the width alone; DESIGN, "Dilated conv backward".
+#include "m3d_common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int K = 3, TAPS = 27, TW = 4, NTW = 7;          // taps per wave: 7, 7, 7, 6 (the surplus slot is computed, never stored)
+constexpr int TZ = 2, TV = 128, GS = TV + 1;              // both tiles hold 128 voxels = 64 MFMA k-steps; odd gy channel stride
+
+template <int DIL, int TYL, int TXL>
+struct WD {
+  static constexpr int TY = 1 << TYL, TX = 1 << TXL;
+  static_assert(TZ * TY * TX == TV, "a tile is 128 voxels");
+  static constexpr int P = DIL * (K / 2), HZ = TZ + 2 * P, HY = TY + 2 * P, HX = TX + 2 * P, HV = HZ * HY * HX;
+  static constexpr int XS = HV | 1;                        // odd channel stride of the x halo tile
+  static constexpr int LDS_FLOATS = 32 * GS + 32 * XS;
+};
+
+// partial[slot = s][co][ci][tap]
+template <int DIL, int TYL, int TXL>
+__global__ __launch_bounds__(256) void conv3d_wgrad_dilated_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                                   float* __restrict__ partial, int B, int cin, int cout, int D, int H,
+                                                                   int W, int tiles_x, int tiles_y, int tiles_z, int S) {
+  using C = WD<DIL, TYL, TXL>;
+  constexpr int TY = C::TY, TX = C::TX;
+  extern __shared__ float lds[];
+  float* lds_g = lds;
+  float* lds_x = lds + 32 * GS;
+  const int tid = threadIdx.x, lane = tid & 63, tw = tid >> 6;
+  const int ci_blocks = (cin + 31) / 32;
+  int bid = blockIdx.x;
+  const int ib = bid % ci_blocks; bid /= ci_blocks;
+  const int s = bid % S;
+  const int cb = bid / S;
+  const int NT = B * tiles_z * tiles_y * tiles_x;
+  const size_t DHW = (size_t)D * H * W;
+
+  f32x16 acc[NTW];
+#pragma unroll
+  for (int n = 0; n < NTW; ++n)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+  int tapoff[NTW];
+#pragma unroll
+  for (int n = 0; n < NTW; ++n) {
+    int t = tw + TW * n;
+    if (t >= TAPS) t = TAPS - 1;
+    const int dz = t / (K * K), dy = (t / K) % K, dx = t % K;
+    tapoff[n] = DIL * ((dz * C::HY + dy) * C::HX + dx);
+  }
+  const int cl = lane & 31, kh = lane >> 5;
+
+  for (int t = s; t < NT; t += S) {
+    int q = t;
+    const int tx = q % tiles_x; q /= tiles_x;
+    const int ty = q % tiles_y; q /= tiles_y;
+    const int tz = q % tiles_z;
+    const int b = q / tiles_z;
+    const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
+    __syncthreads();                                   // the previous tile's MFMAs have read the LDS
+    // ---- stage gy[cb*32 + c][tile] and x[ib*32 + c][halo tile] (zero padded) as 16-byte quads of four consecutive x, as
+    // conv3d_wgrad.hip does: the buffer's range check returns 0 past the last channel of this image, rows and columns outside the
+    // volume are masked, and no load starts before or ends behind the cin * DHW (cout * DHW) floats of the image it reads.
+    {
+      const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(gy + (size_t)b * cout * DHW), 0, (unsigned)((size_t)cout * DHW * sizeof(float)), 0x00020000);
+      constexpr int QG = TX / 4, ROWS = TZ * TY;                       // quads per row, rows per channel
+      constexpr int NG = 32 * ROWS * QG / 256;                         // 1024 quads: 4 per thread
+      f32x4 v[NG];
+      int mk[NG], ld[NG];
+#pragma unroll
+      for (int u = 0; u < NG; ++u) {
+        const int e = tid + u * 256;
+        const int q4 = e % QG, row = (e / QG) % ROWS, c = e / (QG * ROWS);
+        const int zz = z0 + row / TY, yy = y0 + row % TY, xf = x0 + 4 * q4;
+        const bool rok = (zz < D) & (yy < H);
+        int m = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m |= (rok && xf + j < W) ? (1 << j) : 0;
+        const long long lin = (long long)(cb * 32 + c) * (long long)DHW + ((long long)zz * H + yy) * W + xf;
+        mk[u] = m; ld[u] = c * GS + row * TX + 4 * q4;
+        v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, m ? (int)(lin * 4) : 0, 0, 0));
+      }
+#pragma unroll
+      for (int u = 0; u < NG; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lds_g[ld[u] + j] = ((mk[u] >> j) & 1) ? v[u][j] : 0.f;
+    }
+    {
+      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(x + (size_t)b * cin * DHW), 0, (unsigned)((size_t)cin * DHW * sizeof(float)), 0x00020000);
+      constexpr int QX = (C::HX + 3) / 4;                              // quads per halo row (x0-P .. x0-P+4*QX-1); HX % 4 == 0 here
+      static_assert(C::HX % 4 == 0, "whole quads per halo row");
+      constexpr int NQX = 32 * C::HZ * C::HY * QX;
+      constexpr int UB = (NQX % (256 * 5) == 0) ? 5 : 3;               // quads per batch: 7680 = 6 * 5 * 256, 6912 = 9 * 3 * 256
+      static_assert(NQX % (256 * UB) == 0, "no ragged batch");
+#pragma unroll 1
+      for (int e0 = 0; e0 < NQX; e0 += 256 * UB) {
+        f32x4 v[UB];
+        int mk[UB], ld[UB];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+          const int e = e0 + u * 256 + tid;
+          const int q4 = e % QX, row = (e / QX) % (C::HZ * C::HY), c = e / (QX * C::HZ * C::HY);
+          const int hz = row / C::HY, hy = row % C::HY;
+          const int zz = z0 + hz - C::P, yy = y0 + hy - C::P, xf = x0 - C::P + 4 * q4;
+          const bool rok = ((unsigned)zz < (unsigned)D) & ((unsigned)yy < (unsigned)H);
+          int m = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) m |= (rok && xf + j >= 0 && xf + j < W) ? (1 << j) : 0;
+          long long lin = (long long)(ib * 32 + c) * (long long)DHW + ((long long)zz * H + yy) * W + xf;
+          // a quad that begins before the image's first float (channel 0, row 0, xf = -P .. -1) would be dropped whole by the range
+          // check: load from offset 0 and shift instead (-lin <= P <= 3)
+          if (m && lin < 0) { m |= (int)(-lin) << 4; lin = 0; }
+          mk[u] = m; ld[u] = c * C::XS + row * C::HX + 4 * q4;
+          v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, m ? (int)(lin * 4) : 0, 0, 0));
+        }
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+          const int sh = mk[u] >> 4;
+          f32x4 w4 = v[u];
+          if (sh == 1) w4 = f32x4{0.f, w4[0], w4[1], w4[2]};
+          else if (sh == 2) w4 = f32x4{0.f, 0.f, w4[0], w4[1]};
+          else if (sh == 3) w4 = f32x4{0.f, 0.f, 0.f, w4[0]};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) lds_x[ld[u] + j] = ((mk[u] >> j) & 1) ? w4[j] : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- MFMA: k-step = voxel pair (v, v+1); A = gy[co = lane%32][v + lane/32], B = x[ci = lane%32][v + lane/32 + DIL * tap]
+    const float* ga = lds_g + cl * GS + kh;
+    const float* xa = lds_x + cl * C::XS + kh;
+#pragma unroll 4
+    for (int i = 0; i < TV / 2; ++i) {
+      const int v = i * 2;
+      const float a = ga[v];
+      const int hb = ((v >> (TYL + TXL)) * C::HY + ((v >> TXL) & (TY - 1))) * C::HX + (v & (TX - 1));
+      float bv[NTW];
+#pragma unroll
+      for (int n = 0; n < NTW; ++n) bv[n] = xa[hb + tapoff[n]];
+#pragma unroll
+      for (int n = 0; n < NTW; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv[n], acc[n], 0, 0, 0);
+    }
+  }
+  // ---- write this workgroup's partial: acc[i = co][j = ci]; col j = lane&31, row i = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  float* pp = partial + (size_t)s * cout * cin * TAPS;
+  const int ci = ib * 32 + cl;
+#pragma unroll
+  for (int n = 0; n < NTW; ++n) {
+    const int tp = tw + TW * n;
+    if (tp >= TAPS) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+      if (co < cout && ci < cin) pp[((size_t)co * cin + ci) * TAPS + tp] = acc[n][r];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void wgrad_dilated_reduce_kernel(const float* __restrict__ partial, int slots, long long n,
+                                                                   float* __restrict__ dw) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float sum = 0.f;
+  for (int s = 0; s < slots; ++s) sum += partial[(size_t)s * n + i];      // slot order: deterministic
+  dw[i] = sum;
+}
+
+struct Plan { int tile_x, tile_y, tiles_x, tiles_y, tiles_z, NT, blocks_c, S; long long n; };
+
+// tile_x: 16 (2 x 4 x 16), 8 (2 x 8 x 8) or 0 = the library's choice, a function of the width alone
+Plan make_plan(int batch, int cin, int cout, int D, int H, int W, int tile_x) {
+  Plan p;
+  if (tile_x == 0) tile_x = (W <= 8) ? 8 : 16;
+  p.tile_x = tile_x; p.tile_y = TV / TZ / tile_x;
+  p.tiles_x = (W + p.tile_x - 1) / p.tile_x; p.tiles_y = (H + p.tile_y - 1) / p.tile_y; p.tiles_z = (D + TZ - 1) / TZ;
+  const long long nt = (long long)batch * p.tiles_x * p.tiles_y * p.tiles_z;
+  p.NT = nt > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)nt;
+  p.blocks_c = ((cout + 31) / 32) * ((cin + 31) / 32);
+  int S = (1024 + p.blocks_c - 1) / p.blocks_c;          // aim at >= 1024 workgroups (4 per CU), as m3d_conv3d_wgrad does
+  if (S > p.NT) S = p.NT;
+  if (S < 1) S = 1;
+  p.S = S;
+  p.n = (long long)cout * cin * TAPS;
+  return p;
+}
+
+bool extents_ok(int batch, int cin, int cout, int D, int H, int W) {
+  return batch > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0;
+}
+
+// what the launch refuses for its shape (M3D_OK: it runs)
+int shape_rc(int batch, int cin, int cout, int D, int H, int W, int k, int dilation, int tile_x) {
+  if (!extents_ok(batch, cin, cout, D, H, W)) return M3D_EINVAL;
+  if (k != 3 || dilation != 2 || !(tile_x == 0 || tile_x == 8 || tile_x == 16)) return M3D_EUNSUPPORTED;
+  const size_t dhw = (size_t)D * H * W;                   // one image of x and of gy is addressed with 32-bit buffer offsets
+  if ((size_t)cin * dhw * sizeof(float) >= 0x7FFFFFFFull || (size_t)cout * dhw * sizeof(float) >= 0x7FFFFFFFull) return M3D_EUNSUPPORTED;
+  const Plan p = make_plan(batch, cin, cout, D, H, W, tile_x);
+  if ((long long)batch * p.tiles_x * p.tiles_y * p.tiles_z > 0x7FFFFFFFll || (long long)p.blocks_c * p.S > 0x7FFFFFFFll)
+    return M3D_EUNSUPPORTED;
+  return M3D_OK;
+}
+
+// the larger of the two tiles' needs, so that one workspace serves m3d_conv3d_wgrad_dilated and m3d_conv3d_wgrad_dilated_tile
+size_t ws_bytes_d2(int batch, int cin, int cout, int D, int H, int W) {
+  const Plan a = make_plan(batch, cin, cout, D, H, W, 16), b = make_plan(batch, cin, cout, D, H, W, 8);
+  return (size_t)(a.S > b.S ? a.S : b.S) * a.n * sizeof(float) + 256;
+}
+
+template <int TYL, int TXL>
+void launch(const float* x, const float* gy, float* partial, int batch, int cin, int cout, int D, int H, int W, const Plan& p,
+            hipStream_t st) {
+  const size_t lds = sizeof(float) * WD<2, TYL, TXL>::LDS_FLOATS;
+  auto kern = conv3d_wgrad_dilated_kernel<2, TYL, TXL>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long long)p.blocks_c * p.S)), dim3(256), lds, st, x, gy, partial, batch, cin, cout, D, H, W,
+                     p.tiles_x, p.tiles_y, p.tiles_z, p.S);
+}
+
+}  // namespace
+
+M3D_API size_t m3d_conv3d_wgrad_dilated_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width, int k,
+                                                        int dilation) {
+  if (dilation == 1) return m3d_conv3d_wgrad_workspace_bytes(batch, cin, cout, depth, height, width, k);
+  if (shape_rc(batch, cin, cout, depth, height, width, k, dilation, 0) != M3D_OK) return 0;
+  return ws_bytes_d2(batch, cin, cout, depth, height, width);
+}
+
+M3D_API int m3d_conv3d_wgrad_dilated_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int dilation, int tile_x,
+                                          int* tile_x_out, int* tile_y_out, int* slots_out) {
+  const int rc = shape_rc(batch, cin, cout, depth, height, width, k, dilation, tile_x);
+  if (rc != M3D_OK) return rc;
+  const Plan p = make_plan(batch, cin, cout, depth, height, width, tile_x);
+  if (tile_x_out) *tile_x_out = p.tile_x;
+  if (tile_y_out) *tile_y_out = p.tile_y;
+  if (slots_out) *slots_out = p.S;
+  return M3D_OK;
+}
+
+M3D_API int m3d_conv3d_wgrad_dilated_tile(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                          int depth, int height, int width, int k, int dilation, int tile_x, void* d_ws, size_t ws_bytes,
+                                          void* stream) {
+  if (!d_in || !d_grad_out || !d_grad_weight || !d_ws || !extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
+  const int rc = shape_rc(batch, cin, cout, depth, height, width, k, dilation, tile_x);
+  if (rc != M3D_OK) return rc;
+  if (ws_bytes < ws_bytes_d2(batch, cin, cout, depth, height, width)) return M3D_EWORKSPACE;
+  const Plan p = make_plan(batch, cin, cout, depth, height, width, tile_x);
+  float* partial = (float*)m3d::align_up((size_t)d_ws, 256);
+  hipStream_t st = m3d::as_stream(stream);
+  if (p.tile_x == 8)
+    launch<3, 3>(d_in, d_grad_out, partial, batch, cin, cout, depth, height, width, p, st);
+  else
+    launch<2, 4>(d_in, d_grad_out, partial, batch, cin, cout, depth, height, width, p, st);
+  int lrc = m3d::check_launch("conv3d_wgrad_dilated");
+  if (lrc != M3D_OK) return lrc;
+  hipLaunchKernelGGL(wgrad_dilated_reduce_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, st, partial, p.S, p.n, d_grad_weight);
+  return m3d::check_launch("conv3d_wgrad_dilated_reduce");
+}
+
+M3D_API int m3d_conv3d_wgrad_dilated(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                     int depth, int height, int width, int k, int dilation, void* d_ws, size_t ws_bytes, void* stream) {
+  if (dilation == 1)
+    return m3d_conv3d_wgrad(d_in, d_grad_out, d_grad_weight, batch, cin, cout, depth, height, width, k, d_ws, ws_bytes, stream);
+  return m3d_conv3d_wgrad_dilated_tile(d_in, d_grad_out, d_grad_weight, batch, cin, cout, depth, height, width, k, dilation, 0, d_ws,
+                                       ws_bytes, stream);
+}

@@ -45,6 +45,7 @@ SYMBOLS = [
     "m3d_peak_stimulation3d_workspace_bytes", "m3d_peak_stimulation3d", "m3d_peak_stimulation3d_backward",
     "m3d_upconv3d_2x_forward", "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_dgrad", "m3d_upconv3d_2x_wgrad_workspace_bytes",
     "m3d_upconv3d_2x_wgrad", "m3d_upconv3d_2x_slices",
+    "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_dilated", "m3d_conv3d_wgrad_dilated_tile", "m3d_conv3d_wgrad_dilated_plan",
 ]
 
 
@@ -120,7 +121,8 @@ def _load(path):
               "m3d_paint_spheres_workspace_bytes", "m3d_rpn_targets_workspace_bytes", "m3d_box_head_targets_workspace_bytes",
               "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes",
               "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_peak_stimulation3d_workspace_bytes",
-              "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes"):
+              "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes",
+              "m3d_conv3d_wgrad_dilated_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -12,7 +12,8 @@ registers:
   otsu                     otsu_py_2d_fast                                               (tools/otsu.py:199-284)
 and install_conv3d() routes qualifying torch.nn.functional.conv3d calls (fp32, CUDA, NCDHW, stride 1,
 padding k//2, dilation 1, groups 1, k in {1,3} or the 5^3/Cin=1 stem) to the MFMA kernels, forward and
-backward-data, so lib/modeling/DSN.py and lib/prm/peak_backprop_3d.py run unchanged on them.
+backward-data, so lib/modeling/DSN.py and lib/prm/peak_backprop_3d.py run unchanged on them.  Under set_conv_dilated("m3d")
+(opt-in) the k = 3, dilation 2, padding 2 convs of the mask head go there too, forward and backward.
 """
 import importlib
 import sys
@@ -322,10 +323,73 @@ def _qualifies(x, weight, stride, padding, dilation, groups):
     return k == 5 and weight.shape[1] == 1 and weight.shape[0] <= 64
 
 
+CONV_DILATED_TORCH, CONV_DILATED_M3D = "torch", "m3d"
+_conv_dilated = CONV_DILATED_TORCH
+
+
+def set_conv_dilated(mode):
+    """The 3^3 convs with dilation 2 and padding 2 (the mask head at MRCNN.DILATION = 2, train.MaskHead): "torch" (the default;
+    install() does not change it) leaves them to torch's own conv3d, as every other dilation always is; "m3d" takes the library in
+    training: forward m3d_conv3d_forward_dilated, gx the same on the W_DGRAD pack, gw m3d_conv3d_wgrad_dilated, gb m3d_conv3d_bias_grad
+    (DESIGN, "Dilated conv backward").  All fp32: set_conv_train("f16x2") and set_conv_wgrad("f16x2") do not reach these layers.  The
+    backward of a call follows the mode its forward ran under.  Returns the previous mode."""
+    global _conv_dilated
+    if mode not in (CONV_DILATED_TORCH, CONV_DILATED_M3D):
+        raise ValueError("set_conv_dilated(%r): 'torch' or 'm3d'" % (mode,))
+    prev, _conv_dilated = _conv_dilated, mode
+    return prev
+
+
+def get_conv_dilated():
+    return _conv_dilated
+
+
+class _Conv3dDilated2Fn(torch.autograd.Function):
+    """k = 3, dilation 2, padding 2 on the library's fp32 kernels.  Reached only under set_conv_dilated("m3d"), so whatever a backward
+    of this Function runs is what its forward's mode asked for."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(weight, x if weight.requires_grad else None)
+        ctx.has_bias = bias is not None
+        return _packed(weight, ops.W_PLAIN)(x, shift=bias.detach().contiguous() if bias is not None else None, dilation=2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        weight, x = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = _packed(weight, ops.W_DGRAD)(gy, dilation=2)
+        if ctx.needs_input_grad[1]:
+            gw = ops.conv3d_wgrad(x, gy, 3, dilation=2)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = ops.conv3d_bias_grad(gy)
+        return gx, gw, gb
+
+
+def _qualifies_dilated2(x, weight, bias, stride, padding, dilation, groups):
+    def tup(v):
+        return (v,) * 3 if isinstance(v, int) else tuple(v)
+    if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda and x.dtype == torch.float32
+            and weight.dtype == torch.float32 and x.dim() == 5 and x.is_contiguous() and weight.dim() == 5):
+        return False
+    if tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[1] != x.shape[1] or groups != 1:
+        return False
+    if bias is not None and not (torch.is_tensor(bias) and bias.is_cuda and bias.dtype == torch.float32
+                                 and tuple(bias.shape) == (weight.shape[0],)):
+        return False
+    return tup(stride) == (1, 1, 1) and tup(dilation) == (2, 2, 2) and not isinstance(padding, str) and tup(padding) == (2, 2, 2)
+
+
 def conv3d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
     if _qualifies(input, weight, stride, padding, dilation, groups):
         return _Conv3dFn.apply(input.contiguous(), weight, bias)
-    return _orig_conv3d(input, weight, bias, stride, padding, dilation, groups)
+    if _conv_dilated == CONV_DILATED_M3D and _qualifies_dilated2(input, weight, bias, stride, padding, dilation, groups):
+        return _Conv3dDilated2Fn.apply(input, weight, bias)
+    # a direct call (train.MaskHead) before install_conv3d(): torch's own is still in its place
+    orig = _orig_conv3d if _orig_conv3d is not None else torch.nn.functional.conv3d
+    return orig(input, weight, bias, stride, padding, dilation, groups)
 
 
 # ----------------------------------------------------------------------------- F.linear interception (box head: fast_rcnn_heads.py:84-85,114-117,42-45)

@@ -1842,14 +1842,36 @@ class StemWinoConv3d(object):
 
 
 # ------------------------------------------------------------------ conv backward-weights / bias gradient
-def conv3d_wgrad(x, grad_out, k):
-    """dW [cout,cin,k,k,k] of a stride-1 pad-k/2 conv: x [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA)."""
+def conv3d_wgrad_dilated_plan(batch, cin, cout, D, H, W, tile_x=0):
+    """What conv3d_wgrad(..., 3, dilation=2) launches for this shape (m3d_conv3d_wgrad_dilated_plan, host only): dict(tile_x, tile_y, slots);
+    tile_x = 16 / 8 asks for that tile form instead of the library's choice."""
+    v = [C.c_int(0) for _ in range(3)]
+    check(lib().m3d_conv3d_wgrad_dilated_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), 3, 2, int(tile_x),
+                                              *[C.byref(a) for a in v]), "conv3d_wgrad_dilated_plan")
+    return dict(zip(("tile_x", "tile_y", "slots"), (a.value for a in v)))
+
+
+def conv3d_wgrad(x, grad_out, k, dilation=1, tile_x=0):
+    """dW [cout,cin,k,k,k] of a stride-1 conv with padding dilation * (k // 2): x [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA).
+    dilation 1 is m3d_conv3d_wgrad; k = 3 with dilation 2 is m3d_conv3d_wgrad_dilated (tile_x = 16 / 8: that voxel tile instead of the
+    library's choice, for A/B runs and tests); any other dilation is an error."""
     _need_gpu(x, grad_out)
     x, grad_out = _f32c(x), _f32c(grad_out)
     B, cin, D, H, W = x.shape
     cout = grad_out.shape[1]
     assert grad_out.shape == (B, cout, D, H, W)
     dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
+    if dilation != 1:
+        wsb = lib().m3d_conv3d_wgrad_dilated_workspace_bytes(B, cin, cout, D, H, W, k, int(dilation))
+        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+        if tile_x:
+            rc = lib().m3d_conv3d_wgrad_dilated_tile(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, k, int(dilation), int(tile_x),
+                                                     _ptr(ws), C.c_size_t(wsb), _stream())
+        else:
+            rc = lib().m3d_conv3d_wgrad_dilated(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, k, int(dilation), _ptr(ws),
+                                                C.c_size_t(wsb), _stream())
+        check(rc, "conv3d_wgrad_dilated")
+        return dw
     wsb = lib().m3d_conv3d_wgrad_workspace_bytes(B, cin, cout, D, H, W, k)
     ws = torch.empty((wsb,), dtype=torch.uint8, device=x.device)
     check(lib().m3d_conv3d_wgrad(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, k, _ptr(ws), C.c_size_t(wsb), _stream()),

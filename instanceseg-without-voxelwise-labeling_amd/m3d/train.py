@@ -389,12 +389,15 @@ class MaskTrainCfg:
         self.sampling_ratio = 2                             # MRCNN.ROI_XFORM_SAMPLING_RATIO
         self.dim_reduced = 256                              # MRCNN.DIM_REDUCED
         self.num_convs = 3                                  # MRCNN.ROI_MASK_HEAD: mask_rcnn_fcn_head_v1up3convs
+        self.dilation = 1                                   # MRCNN.DILATION: both shipped YAMLs set 1 (lib/core/config.py:767 defaults to 2)
         unknown = sorted(set(kw) - set(self.__dict__))
         if unknown:
             raise TypeError("MaskTrainCfg: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(sorted(self.__dict__))))
         self.__dict__.update(kw)
         if self.anno_type not in ("mask", "spot"):
             raise ValueError("MaskTrainCfg: anno_type is 'mask' or 'spot'")
+        if self.dilation not in (1, 2):
+            raise ValueError("MaskTrainCfg: dilation is 1 or 2 (the library's dilated 3^3 conv is dilation 2 only)")
 
     @staticmethod
     def nuclei(**kw):
@@ -546,20 +549,22 @@ def upconv3d_2x(x, weight, bias=None, relu=False):
 
 
 class MaskHead(torch.nn.Module):
-    """mask_rcnn_fcn_head_v1upXconvs followed by mask_rcnn_outputs (mask_rcnn_heads.py:132-193, 20-68; dilation 1, conv classifier, no
+    """mask_rcnn_fcn_head_v1upXconvs followed by mask_rcnn_outputs (mask_rcnn_heads.py:132-193, 20-68; conv classifier, no
     upsampling) as one module under the reference's parameter names conv_fcn.{0,2,..}, upconv, classify: its state_dict, prefixed
     Mask_Head. / Mask_Outs. by `detector_state`, is what MaskHeadM3D takes.  RoIAlign3D and the convolutions go through m3d.compat (the
     library's kernels, forward and backward).  The up-conv follows compat.set_upconv: "torch" (the default) is torch's ConvTranspose3d
     and a separate ReLU; "m3d" is upconv3d_2x with the bias and the ReLU in its epilogue and the library's dgrad / wgrad kernels behind
-    it - the same module, parameters and state_dict under both.  forward returns logits, as the reference does in training."""
+    it - the same module, parameters and state_dict under both.  cfg.dilation (MRCNN.DILATION) is the dilation and the padding of the 3^3
+    convs; no parameter name or shape depends on it.  At dilation 2 they follow compat.set_conv_dilated: "torch" (the default) is torch's
+    conv3d, "m3d" the library's dilated forward, dgrad and wgrad.  forward returns logits, as the reference does in training."""
 
     def __init__(self, dim_in, cfg, stride):
         super().__init__()
         self.cfg, self.spatial_scale = cfg, 1.0 / float(stride)
-        dim = int(cfg.dim_reduced)
+        dim, d = int(cfg.dim_reduced), int(cfg.dilation)
         layers, cin = [], int(dim_in)
         for _ in range(int(cfg.num_convs)):
-            layers += [torch.nn.Conv3d(cin, dim, 3, 1, 1), torch.nn.ReLU(inplace=True)]
+            layers += [torch.nn.Conv3d(cin, dim, 3, 1, padding=d, dilation=d), torch.nn.ReLU(inplace=True)]
             cin = dim
         self.conv_fcn = torch.nn.Sequential(*layers)
         self.upconv = torch.nn.ConvTranspose3d(dim, dim, 2, 2, 0)
@@ -587,7 +592,7 @@ class MaskHead(torch.nn.Module):
         r = int(self.cfg.roi_xform_resolution)
         x = compat.RoIAlignFunction_3d(r, r, r, self.spatial_scale, int(self.cfg.sampling_ratio))(feat, rois7)
         for m in self.conv_fcn:
-            x = compat.conv3d(x, m.weight, m.bias, 1, 1) if isinstance(m, torch.nn.Conv3d) else torch.relu(x)
+            x = compat.conv3d(x, m.weight, m.bias, 1, m.padding, m.dilation) if isinstance(m, torch.nn.Conv3d) else torch.relu(x)
         if compat.get_upconv() == compat.UPCONV_M3D:
             x = upconv3d_2x(x, self.upconv.weight, self.upconv.bias, relu=True)
         else:

@@ -9,7 +9,8 @@ layers and RoIAlign run on libm3d through m3d.compat; m3d.box_head_losses; torch
 Prints all four losses per step.  One fixed sample; this is not a training driver (no data loading, schedule or checkpoints).
 
 --mask spot (off by default; without it nothing changes) adds the mask branch: m3d.MaskHead on the same features, m3d.mask_targets from
-the spheres inscribed in the synthetic boxes, m3d.mask_losses; loss_mask joins the printed line and the sum."""
+the spheres inscribed in the synthetic boxes, m3d.mask_losses; loss_mask joins the printed line and the sum.  --mask-dilation 2 builds that head with MRCNN.DILATION = 2 (the reference's
+default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated convs on the library, forward and backward."""
 import argparse
 import os
 import sys
@@ -67,7 +68,14 @@ def main():
     ap.add_argument("--upconv", choices=("torch", "m3d"), default="torch",
                     help="with --mask: the mask head's ConvTranspose3d + ReLU (m3d.compat.set_upconv): m3d = csrc/upconv3d.hip, forward and "
                          "backward, bias and ReLU fused")
+    ap.add_argument("--mask-dilation", type=int, choices=(1, 2), default=1,
+                    help="with --mask: MRCNN.DILATION of the mask head's 3^3 convs (MaskTrainCfg.dilation)")
+    ap.add_argument("--conv-dilated", choices=("torch", "m3d"), default="torch",
+                    help="the dilation-2 convs (m3d.compat.set_conv_dilated): m3d = the library's dilated forward, dgrad and wgrad "
+                         "(csrc/conv3d_wgrad_dilated.hip)")
     a = ap.parse_args()
+    if a.mask_dilation != 1 and not a.mask:
+        ap.error("--mask-dilation needs --mask")
     import torch
     import m3d
     import m3d.compat
@@ -79,6 +87,7 @@ def main():
     m3d.compat.set_conv_train(a.conv)
     m3d.compat.set_roi_align_backward(a.roi_backward)
     m3d.compat.set_upconv(a.upconv)
+    m3d.compat.set_conv_dilated(a.conv_dilated)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
@@ -93,7 +102,7 @@ def main():
             m.eval()
     params = list(net.parameters()) + list(head.parameters())
     if a.mask:
-        mcfg = m3d.MaskTrainCfg.soma(in_size=tile, dim_reduced=4 * a.width, num_convs=2)
+        mcfg = m3d.MaskTrainCfg.soma(in_size=tile, dim_reduced=4 * a.width, num_convs=2, dilation=a.mask_dilation)
         mask_head = m3d.MaskHead(8 * a.width, mcfg, rcfg.stride).cuda()
         g = gt.cpu().numpy()                                                       # (x, y, z, r): centre and half the shortest edge
         spots = torch.from_numpy(np.concatenate([(g[:, :3] + g[:, 3:]) / 2, (g[:, 3:] - g[:, :3]).min(1, keepdims=True) / 2], 1)).cuda()
