@@ -324,6 +324,23 @@ int m3d_conv3d_wgrad_dilated_tile(const float* d_in, const float* d_grad_out, fl
                                   void* stream);
 int m3d_conv3d_wgrad_dilated_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int dilation, int tile_x,
                                   int* tile_x_out, int* tile_y_out, int* slots_out);
+/* The k = 3, dilation 1 weight gradient of m3d_conv3d_wgrad on maps at most 8 voxels wide (csrc/conv3d_wgrad_narrow.hip): the per-RoI
+ * convs on 7^3 grids of lib/modeling/fast_rcnn_heads.py:120-179 (roi_Xconv1fc_head) and of the mask head at MRCNN.DILATION = 1.  The
+ * scheme of the dilated kernel above (v_mfma_f32_32x32x2_f32, fp32 operands and accumulation, `slots` split-K partials in the
+ * workspace, a reduce launch that adds them in slot order; no atomics: bit-identical run to run) on a 2 x 8 x 8 voxel tile with a
+ * 1-voxel halo, where m3d_conv3d_wgrad has only 2 x 4 x 16.  Same sum as m3d_conv3d_wgrad in another order: equal within fp32
+ * rounding, not bit-equal.  Writes every element of d_grad_weight [cout,cin,3,3,3] and at most workspace_bytes of d_ws, nothing else.
+ * Refusals, all before a pointer is followed or anything is launched: M3D_EINVAL a NULL pointer or a non-positive extent;
+ * M3D_EUNSUPPORTED k != 3, width > 8, cin or cout * depth * height * width * 4 bytes >= 2^31 - 1, 2^31 voxel tiles or workgroups
+ * (workspace_bytes is then 0 and _supported 0); M3D_EWORKSPACE ws_bytes below workspace_bytes.
+ * _plan (host only; any output pointer may be NULL) reports the tile (8, 8) and the slot count, a function of the shape only, and
+ * returns what the launch would return for its shape. */
+int m3d_conv3d_wgrad_narrow_supported(int batch, int cin, int cout, int depth, int height, int width, int k);
+size_t m3d_conv3d_wgrad_narrow_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width, int k);
+int m3d_conv3d_wgrad_narrow_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int* tile_x_out,
+                                 int* tile_y_out, int* slots_out);
+int m3d_conv3d_wgrad_narrow(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout, int depth,
+                            int height, int width, int k, void* d_ws, size_t ws_bytes, void* stream);
 /* The k = 3 weight gradient above on the f16 matrix cores at fp32 accuracy (csrc/conv3d_wgrad_f16.hip): the f16x2 cut of
  * m3d_conv3d_zw_forward - each operand tensor scaled by ONE power of two (m3d::f16_scale_of of its bound) and cut into two fp16
  * numbers while it is staged, three v_mfma_f32_32x32x16_f16 products hh + hl + lh per fp32 product, fp32 accumulation, the sum

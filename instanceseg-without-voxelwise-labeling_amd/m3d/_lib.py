@@ -46,6 +46,7 @@ SYMBOLS = [
     "m3d_upconv3d_2x_forward", "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_dgrad", "m3d_upconv3d_2x_wgrad_workspace_bytes",
     "m3d_upconv3d_2x_wgrad", "m3d_upconv3d_2x_slices",
     "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_dilated", "m3d_conv3d_wgrad_dilated_tile", "m3d_conv3d_wgrad_dilated_plan",
+    "m3d_conv3d_wgrad_narrow_supported", "m3d_conv3d_wgrad_narrow_workspace_bytes", "m3d_conv3d_wgrad_narrow_plan", "m3d_conv3d_wgrad_narrow",
 ]
 
 
@@ -122,7 +123,7 @@ def _load(path):
               "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes",
               "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_peak_stimulation3d_workspace_bytes",
               "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes",
-              "m3d_conv3d_wgrad_dilated_workspace_bytes"):
+              "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_narrow_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

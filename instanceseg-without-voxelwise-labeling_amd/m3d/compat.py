@@ -13,7 +13,9 @@ registers:
 and install_conv3d() routes qualifying torch.nn.functional.conv3d calls (fp32, CUDA, NCDHW, stride 1,
 padding k//2, dilation 1, groups 1, k in {1,3} or the 5^3/Cin=1 stem) to the MFMA kernels, forward and
 backward-data, so lib/modeling/DSN.py and lib/prm/peak_backprop_3d.py run unchanged on them.  Under set_conv_dilated("m3d")
-(opt-in) the k = 3, dilation 2, padding 2 convs of the mask head go there too, forward and backward.
+(opt-in) the k = 3, dilation 2, padding 2 convs of the mask head go there too, forward and backward.  Under
+set_conv_wgrad_narrow(True) (opt-in) the weight gradient of the dilation-1 3^3 convs on maps at most 8 wide - the per-RoI convs of the
+conv box head and of the mask head - runs on the 2 x 8 x 8 tile kernel (m3d_conv3d_wgrad_narrow).
 """
 import importlib
 import sys
@@ -219,6 +221,24 @@ def get_conv_wgrad():
     return _conv_wgrad
 
 
+_conv_wgrad_narrow = False
+
+
+def set_conv_wgrad_narrow(on):
+    """The dilation-1 weight gradient of the intercepted 3^3 convs on maps at most 8 wide (the per-RoI convs of train.ConvBoxHead and of
+    train.MaskHead at dilation 1, on 7^3 grids): False (the default; install() does not change it) keeps m3d_conv3d_wgrad, whose
+    2 x 4 x 16 voxel tile such a map fills to a third; True takes m3d_conv3d_wgrad_narrow (2 x 8 x 8) for the layers
+    conv_plan.wgrad_kernel(narrow=True) routes to it.  A layer that set_conv_wgrad("f16x2") routes to the f16 kernel stays there; the
+    forward, dgrad and the bias gradient are the same under both settings.  Returns the previous setting."""
+    global _conv_wgrad_narrow
+    prev, _conv_wgrad_narrow = _conv_wgrad_narrow, bool(on)
+    return prev
+
+
+def get_conv_wgrad_narrow():
+    return _conv_wgrad_narrow
+
+
 _conv_train = conv_plan.TRAIN_FP32
 _conv_train_min_units = None          # None: conv_plan.ZW_MIN_UNITS
 
@@ -282,7 +302,8 @@ class _Conv3dFn(torch.autograd.Function):
         cout, cin = weight.shape[0], weight.shape[1]
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
         dgrad_zw = f16 and ctx.needs_input_grad[0] and _train_kernel("dgrad", ctx.train, gy.shape, weight.shape) == conv_plan.TRAIN_F16X2
-        wgrad_zw = ctx.needs_input_grad[1] and conv_plan.wgrad_kernel(B, cin, cout, D, H, W, _conv_wgrad, k=k) == conv_plan.WGRAD_F16X2
+        wgrad = conv_plan.wgrad_kernel(B, cin, cout, D, H, W, _conv_wgrad, k=k, narrow=_conv_wgrad_narrow) if ctx.needs_input_grad[1] else None
+        wgrad_zw = wgrad == conv_plan.WGRAD_F16X2
         gb = gy_max = None
         if f16 and (dgrad_zw or wgrad_zw or want_gb):
             # one pass over gy: the bias gradient and the bound both f16x2 kernels scale gy by.  In f16x2 mode gb ALWAYS comes from here, so
@@ -301,6 +322,8 @@ class _Conv3dFn(torch.autograd.Function):
             if wgrad_zw:
                 # mode "fp32": sweeps both operands for their bounds; "f16x2": x's bound from the forward (if it ran on f16x2), gy's shared
                 gw = ops.conv3d_wgrad_f16x2(x, gy, ctx.x_max, gy_max)
+            elif wgrad == conv_plan.WGRAD_NARROW:
+                gw = ops.conv3d_wgrad_narrow(x, gy)
             else:
                 gw = ops.conv3d_wgrad(x, gy, k)
         if want_gb and gb is None:

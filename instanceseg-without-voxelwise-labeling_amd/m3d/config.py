@@ -57,6 +57,9 @@ class Cfg:
         self.roi_res = 7                                    # FAST_RCNN.ROI_XFORM_RESOLUTION
         self.sampling_ratio = 2                             # FAST_RCNN.ROI_XFORM_SAMPLING_RATIO
         self.mlp_dim = 1024                                 # FAST_RCNN.MLP_HEAD_DIM
+        self.box_head = "roi_2mlp_head"                     # FAST_RCNN.ROI_BOX_HEAD ("roi_2mlp_head" / "roi_Xconv1fc_head")
+        self.conv_head_dim = 128                            # FAST_RCNN.CONV_HEAD_DIM (the nuclei YAML; config.py:637 has 256)
+        self.num_stacked_convs = 2                          # FAST_RCNN.NUM_STACKED_CONVS (the nuclei YAML; config.py:639 has 4)
         self.in_size = (64, 200, 200)                       # TEST.IN_SIZE
         self.crop_ovlp = 100                                # TEST.CROP_OVLP
         self.dataset = "nuclei"
@@ -79,9 +82,12 @@ class Cfg:
     @staticmethod
     def soma(**kw):
         d = dict(stride=4, sizes=(10, 12, 14, 16, 18, 20, 22, 24, 28, 30, 34, 36, 38, 40), aspect_ratios=[[1.0, 1.0]],
-                 rpn_nms_thresh=0.23, nms=0.23, score_thresh=0.0, in_size=(64, 160, 160), crop_ovlp=32, dataset="soma")
+                 rpn_nms_thresh=0.23, nms=0.23, score_thresh=0.0, in_size=(64, 160, 160), crop_ovlp=32, dataset="soma",
+                 conv_head_dim=256, num_stacked_convs=4)        # (the soma YAML sets neither: lib/core/config.py:637,639)
         d.update(kw)
         return Cfg(**d)
+
+    BOX_HEADS = ("roi_2mlp_head", "roi_Xconv1fc_head")      # lib/modeling/fast_rcnn_heads.py:74-117 / :120-179
 
     # reference YAML key -> attribute (the keys the hot path reads; every other key of the file is accepted and ignored, as
     # lib/core/config.py's merge would accept it)
@@ -93,7 +99,8 @@ class Cfg:
         ("TEST", "IN_SIZE"): "in_size", ("TEST", "CROP_OVLP"): "crop_ovlp",
         ("MODEL", "BBOX_REG_WEIGHTS"): "bbox_reg_weights", ("MODEL", "NUM_CLASSES"): "num_classes", ("MODEL", "MASK_ON"): "mask_on",
         ("FAST_RCNN", "ROI_XFORM_RESOLUTION"): "roi_res", ("FAST_RCNN", "ROI_XFORM_SAMPLING_RATIO"): "sampling_ratio",
-        ("FAST_RCNN", "MLP_HEAD_DIM"): "mlp_dim",
+        ("FAST_RCNN", "MLP_HEAD_DIM"): "mlp_dim", ("FAST_RCNN", "CONV_HEAD_DIM"): "conv_head_dim",
+        ("FAST_RCNN", "NUM_STACKED_CONVS"): "num_stacked_convs",
         ("MRCNN", "RESOLUTION"): "mask_resolution", ("MRCNN", "ROI_XFORM_RESOLUTION"): "mask_roi_res",
         ("MRCNN", "ROI_XFORM_SAMPLING_RATIO"): "mask_sampling_ratio", ("MRCNN", "DILATION"): "mask_dilation",
         ("MRCNN", "CLS_SPECIFIC_MASK"): "mask_cls_specific", ("MRCNN", "THRESH_BINARIZE"): "mask_thresh_binarize",
@@ -106,7 +113,8 @@ class Cfg:
         this path: YAML values are merged over the defaults of lib/core/config.py; tuples written as strings ('(64, 200, 200)')
         are decoded with literal_eval as `_merge_a_into_b` / `_decode_cfg_value` do (:1120-1160).  `dataset` ('nuclei' / 'soma':
         the reference's --dataset argument, which selects the tile grid and the binarisation rule) defaults to 'soma' for
-        stride-4 files.  Checks the model family: only the generalized_rcnn / DSN.dsn_body / roi_2mlp_head / RoIAlign path exists."""
+        stride-4 files.  Checks the model family: only the generalized_rcnn / DSN.dsn_body / RoIAlign path exists, with the box head
+        roi_2mlp_head or roi_Xconv1fc_head (FAST_RCNN.ROI_BOX_HEAD, with or without the reference's `fast_rcnn_heads.` prefix)."""
         import ast
         import os
         import yaml
@@ -120,12 +128,18 @@ class Cfg:
                 except (ValueError, SyntaxError):
                     return v
             return v
-        want = {("MODEL", "CONV_BODY"): "DSN.dsn_body", ("MODEL", "TYPE"): "generalized_rcnn",
-                ("FAST_RCNN", "ROI_BOX_HEAD"): "fast_rcnn_heads.roi_2mlp_head", ("FAST_RCNN", "ROI_XFORM_METHOD"): "RoIAlign"}
+        want = {("MODEL", "CONV_BODY"): "DSN.dsn_body", ("MODEL", "TYPE"): "generalized_rcnn", ("FAST_RCNN", "ROI_XFORM_METHOD"): "RoIAlign"}
         for (sec, key), val in want.items():
             got = (y.get(sec) or {}).get(key, val)
             if got != val:
                 raise NotImplementedError("%s.%s = %r: only %r is on the accelerated path" % (sec, key, got, val))
+        head = str((y.get("FAST_RCNN") or {}).get("ROI_BOX_HEAD", "fast_rcnn_heads.roi_2mlp_head"))
+        box_head = head[len("fast_rcnn_heads."):] if head.startswith("fast_rcnn_heads.") else head
+        if box_head == "roi_Xconv1fc_gn_head":
+            raise NotImplementedError("FAST_RCNN.ROI_BOX_HEAD = %r: this head is 2-D in the reference (nn.Conv2d + GroupNorm, "
+                                      "fast_rcnn_heads.py:182-243); the 3-D conv head is roi_Xconv1fc_head" % (head,))
+        if box_head not in Cfg.BOX_HEADS:
+            raise NotImplementedError("FAST_RCNN.ROI_BOX_HEAD = %r: only %s are on the accelerated path" % (head, " / ".join(Cfg.BOX_HEADS)))
         if (y.get("FPN") or {}).get("FPN_ON", False):
             raise NotImplementedError("FPN.FPN_ON: True is not on the accelerated path (both shipped configs have it off)")
         # lib/core/config.py's own defaults for these keys (:31-33,199-250,414-443,634-683), NOT the nuclei values of Cfg():
@@ -133,7 +147,7 @@ class Cfg:
         d = dict(stride=16, sizes=(64, 128, 256, 512), aspect_ratios=(0.5, 1, 2), pre_nms_topN=12000, post_nms_topN=2000,
                  rpn_nms_thresh=0.7, rpn_min_size=0, nms=0.3, score_thresh=0.05, detections_per_im=100, in_size=(64, 240, 240),
                  crop_ovlp=32, bbox_reg_weights=(10., 10., 5., 5.), num_classes=-1, mask_on=False, roi_res=14, sampling_ratio=0,
-                 mlp_dim=1024, prm_on=False, pp_method="norm1")
+                 mlp_dim=1024, prm_on=False, pp_method="norm1", box_head=box_head, conv_head_dim=256, num_stacked_convs=4)
         for keys, attr in Cfg.YAML_KEYS.items():
             node, ok = y, True
             for k in keys:

@@ -30,21 +30,29 @@ WGRAD_FP32, WGRAD_F16X2 = "fp32", "f16x2"            # wgrad kernels: m3d_conv3d
 WGRAD_F16X2_MIN_WORK = 1 << 27
 
 
-def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3):
-    """Which kernel computes the weight gradient of a stride-1 'same' conv layer with x [batch, cin, D, H, W]: WGRAD_F16X2 or WGRAD_FP32.
-    The one place that says so (m3d.compat asks it in backward).  mode: the caller's setting (compat.set_conv_wgrad): "fp32" keeps every
-    layer on m3d_conv3d_wgrad; "f16x2" moves the layers the f16x2 kernel takes (k = 3, cin and cout multiples of 32:
+# The dilation-1 fp32 kernel on the 2 x 8 x 8 voxel tile (m3d_conv3d_wgrad_narrow): maps at most 8 wide, i.e. the per-RoI convs on 7^3
+# grids of the conv box head and of the mask head at MRCNN.DILATION = 1.  Opt-in (compat.set_conv_wgrad_narrow).
+WGRAD_NARROW = "fp32 narrow"
+
+
+def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3, narrow=False):
+    """Which kernel computes the weight gradient of a stride-1 'same' conv layer with x [batch, cin, D, H, W]: WGRAD_F16X2, WGRAD_NARROW
+    or WGRAD_FP32.  The one place that says so (m3d.compat asks it in backward).  mode: the caller's setting (compat.set_conv_wgrad):
+    "fp32" keeps every layer on m3d_conv3d_wgrad; "f16x2" moves the layers the f16x2 kernel takes (k = 3, cin and cout multiples of 32:
     m3d_conv3d_wgrad_f16x2_supported) and was measured to win on by more than the spread of the measurement: layers of at least
-    WGRAD_F16X2_MIN_WORK products per tap.  A function of the shape only."""
+    WGRAD_F16X2_MIN_WORK products per tap.  narrow: the caller's switch (compat.set_conv_wgrad_narrow): a k = 3 layer that would end on
+    WGRAD_FP32 and that m3d_conv3d_wgrad_narrow takes (W <= 8) is WGRAD_NARROW instead; a layer the mode routes to f16x2 stays there.
+    A function of the shape only."""
     if mode not in (WGRAD_FP32, WGRAD_F16X2):
         raise ValueError("wgrad mode %r: 'fp32' or 'f16x2'" % (mode,))
-    if mode == WGRAD_FP32 or int(k) != 3:
+    if int(k) != 3:
         return WGRAD_FP32
-    if not ops.conv3d_wgrad_f16x2_supported(batch, cin, cout, D, H, W):
-        return WGRAD_FP32
-    if int(batch) * int(D) * int(H) * int(W) * int(cin) * int(cout) < WGRAD_F16X2_MIN_WORK:
-        return WGRAD_FP32
-    return WGRAD_F16X2
+    if (mode == WGRAD_F16X2 and ops.conv3d_wgrad_f16x2_supported(batch, cin, cout, D, H, W)
+            and int(batch) * int(D) * int(H) * int(W) * int(cin) * int(cout) >= WGRAD_F16X2_MIN_WORK):
+        return WGRAD_F16X2
+    if narrow and ops.conv3d_wgrad_narrow_supported(batch, cin, cout, D, H, W, 3):
+        return WGRAD_NARROW
+    return WGRAD_FP32
 
 
 TRAIN_FP32, TRAIN_F16X2 = "fp32", "f16x2"            # forward / dgrad kernels of a training conv: the direct fp32 MFMA kernel / conv3d_zw.hip

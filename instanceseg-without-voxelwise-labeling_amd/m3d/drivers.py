@@ -36,8 +36,8 @@ def _im_info_row(im_info):
 
 def _to_params(state, device):
     """Accept a checkpoint dict ({'model': state_dict}, infer_simple.py:142-150) or a bare state dict; tensors -> fp32 CUDA.
-    Keys keep the reference layout (Conv_Body.conv1a.weight ... Box_Outs.bbox_pred.bias; a DataParallel 'module.' prefix
-    is dropped)."""
+    Keys keep the reference layout (Conv_Body.conv1a.weight ... Box_Outs.bbox_pred.bias; the box head as Box_Head.fc1 / fc2 or, for
+    roi_Xconv1fc_head, Box_Head.convs.{0,2,..} / Box_Head.fc; a DataParallel 'module.' prefix is dropped)."""
     if "model" in state and isinstance(state["model"], dict):
         state = state["model"]
     out = {}

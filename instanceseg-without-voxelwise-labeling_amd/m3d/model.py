@@ -3,7 +3,7 @@
 Mirrors (reference paths): lib/modeling/DSN.py:57-68 (dsn_body), lib/modeling/rpn_heads.py:88-137
 (single_scale_rpn_outputs), lib/modeling/generate_proposals_3d.py (via m3d.generate_proposals3d),
 lib/modeling/model_builder.py:294-312 (roi_feature_transform, RoIAlign branch),
-lib/modeling/fast_rcnn_heads.py:104-117,39-47 (roi_2mlp_head, fast_rcnn_outputs),
+lib/modeling/fast_rcnn_heads.py:104-117,39-47 (roi_2mlp_head, fast_rcnn_outputs), :120-179 (roi_Xconv1fc_head),
 lib/core/test.py:194-263,806-883 (im_detect_bbox, box_results_with_nms_and_limit).
 The state-dict key layout is the reference's: Conv_Body.conv1a.weight ... Box_Outs.bbox_pred.bias.
 
@@ -84,6 +84,7 @@ class DetectorM3D:
         self.cfg = cfg
         self.P = params
         self.probe = None
+        n_head_convs = self._check_conv_head(params, cfg) if "Box_Head.convs.0.weight" in params else 0
         self.anchors = np.ascontiguousarray(cfg.anchors, dtype=np.float64)
         # M3D_WINO: the plain-forward 3x3x3 layers (and the 5^3 stem) also get Winograd weights - 2 (default): F(2x2,3x3) / F(2x4,3x3) on (y,x);
         # 1: F(2,3) along x; 0: direct kernels only.  Round 6, M3D_CONV_F16 (default 1; needs M3D_WINO != 0): the 3^3 layers with cin % 16 == 0
@@ -107,7 +108,9 @@ class DetectorM3D:
         w = torch.cat([params["RPN.RPN_cls_score.weight"], params["RPN.RPN_bbox_pred.weight"]], 0).contiguous()
         self.rpn_heads = ops.PackedConv3d(w)
         self.rpn_heads_bias = torch.cat([params["RPN.RPN_cls_score.bias"], params["RPN.RPN_bbox_pred.bias"]]).contiguous()
-        self.has_head = "Box_Head.fc1.weight" in params
+        # the box head: roi_2mlp_head (Box_Head.fc1 / fc2) or roi_Xconv1fc_head (Box_Head.convs.{0,2,..} + Box_Head.fc)
+        self.conv_head = "Box_Head.convs.0.weight" in params
+        self.has_head = self.conv_head or "Box_Head.fc1.weight" in params
         # RoIAlign3D's matrix-core form for sub-volumes of <= 128 voxels (round 6 A/B, M3D_ROI_GEMM=1).  NOT the product path: correct
         # (tests/test_gpu_ops.py) and slower - 0.49 instead of 0.23 ms at R = 1281: its two launches take 0.16 ms each (1 408 dword stores
         # per RoI from two waves per SIMD) and run AFTER the separable launch, whose time is set by its heavy RoIs either way
@@ -120,12 +123,43 @@ class DetectorM3D:
             # bf16 cut (six products), M3D_FC_SPLIT=0 the fp32-input MFMA kernel (A/B tooling).
             self.fc_split = {}
             mode = os.environ.get("M3D_FC_SPLIT", "f16x2")
+            if self.conv_head:
+                self.head_convs = self._conv_head_layers(params, n_head_convs)
             if mode != "0":
                 cls = ops.SplitLinear if mode in ("bf16x3", "1") else ops.SplitLinearF16
-                for name in ("fc1", "fc2"):
+                for name in (("fc",) if self.conv_head else ("fc1", "fc2")):
                     w = params["Box_Head.%s.weight" % name]
                     if cls.supported(w):
                         self.fc_split[name] = cls(w, params["Box_Head.%s.bias" % name])
+
+    @staticmethod
+    def _check_conv_head(params, cfg):
+        """A checkpoint with roi_Xconv1fc_head (fast_rcnn_heads.py:128-140) against cfg: the number of conv layers, their channel counts
+        and fc's shape.  Raises ValueError; called before anything is packed or launched.  Returns the number of conv layers."""
+        n = 0
+        while "Box_Head.convs.%d.weight" % (2 * n) in params:
+            n += 1
+        want_n, dim, res = int(cfg.num_stacked_convs), int(cfg.conv_head_dim), int(cfg.roi_res)
+        if n != want_n or any(k.startswith("Box_Head.convs.") and int(k.split(".")[2]) >= 2 * n for k in params):
+            raise ValueError("the checkpoint's Box_Head has %d conv layers (convs.0 .. convs.%d) but cfg.num_stacked_convs is %d"
+                             % (n, 2 * (n - 1), want_n))
+        if "Box_Head.fc.weight" not in params:
+            raise ValueError("the checkpoint has Box_Head.convs but no Box_Head.fc (roi_Xconv1fc_head, fast_rcnn_heads.py:140)")
+        cin = int(params["RPN.RPN_conv.weight"].shape[1])                 # dim_out of the conv body: what RoIAlign reads
+        for i in range(n):
+            shp = tuple(params["Box_Head.convs.%d.weight" % (2 * i)].shape)
+            if shp != (dim, cin, 3, 3, 3):
+                raise ValueError("Box_Head.convs.%d.weight is %r, cfg (conv_head_dim %d) needs %r" % (2 * i, shp, dim, (dim, cin, 3, 3, 3)))
+            cin = dim
+        shp = tuple(params["Box_Head.fc.weight"].shape)
+        if shp != (int(cfg.mlp_dim), cin * res ** 3):
+            raise ValueError("Box_Head.fc.weight is %r, cfg needs %r (mlp_dim x conv_head_dim * roi_res^3)" % (shp, (int(cfg.mlp_dim), cin * res ** 3)))
+        return n
+
+    def _conv_head_layers(self, params, n):
+        """The LayerConvs of roi_Xconv1fc_head's conv stack (conv + bias + ReLU, no BN, no pool)"""
+        return [LayerConv(params["Box_Head.convs.%d.weight" % (2 * i)], None, params["Box_Head.convs.%d.bias" % (2 * i)].contiguous(), False,
+                          self.wino_mode, self.conv_f16) for i in range(n)]
 
     # ---- lib/modeling/DSN.py:57-68
     def body_layer(self, li, x, bound_slot=None):
@@ -242,6 +276,8 @@ class DetectorM3D:
         """RoIAlign3D -> fc1 -> fc2 -> (cls_score | bbox_pred as one GEMM) -> softmax / deltas / decoded + clipped boxes in one launch:
         (cls [R,nc], bbox [R,6nc], pred_boxes [R,6nc]).  rois [R,7]."""
         c, P = self.cfg, self.P
+        if self.conv_head:
+            return self._conv_head_outputs(feat, rois, clip_to)
         if self.probe is None and self._one_call_ok(feat, rois, int(rois.shape[0])):
             return self._box_head_call(feat, rois, int(rois.shape[0]), clip_to)
         f16 = [isinstance(self.fc_split.get(n), ops.SplitLinearF16) for n in ("fc1", "fc2")]
@@ -273,6 +309,29 @@ class DetectorM3D:
                     x = ops.linear(x, P["Box_Head.%s.weight" % name], P["Box_Head.%s.bias" % name], relu=True)
         o = ops.linear(x, self.outs_w, self.outs_b)              # cls_score and bbox_pred share their input: one GEMM (:42,45)
         return ops.box_head_outputs(o, rois, c.num_classes, c.bbox_reg_weights, clip_to=clip_to)   # :43-44 (eval) + core/test.py:250-251
+
+    # ---- lib/modeling/fast_rcnn_heads.py:120-179,39-47
+    def _conv_head_outputs(self, feat, rois, clip_to=None):
+        """roi_Xconv1fc_head: RoIAlign3D -> num_stacked_convs x (3^3 conv + ReLU on the [R, C, 7, 7, 7] grids, each on the kernel
+        conv_plan.plan_conv picks) -> fc + ReLU -> (cls_score | bbox_pred as one GEMM) -> softmax / deltas / decoded + clipped boxes.
+        Not on the one-call path (m3d_box_head_forward): one library call per stage."""
+        c, P = self.cfg, self.P
+        with self.span("roi_align3d"):
+            x = ops.roi_align3d_forward(feat, rois, c.roi_res, c.roi_res, c.roi_res, 1.0 / c.stride, c.sampling_ratio)
+        if x.shape[0] == 0:                                           # no rows: nothing for the convs to launch
+            x = x.new_zeros((0, self.head_convs[-1].cout) + tuple(x.shape[2:]))
+        else:
+            for i, conv in enumerate(self.head_convs):                # :177
+                with self.span("head_conv%d" % (i + 1)):
+                    x = conv(x, self._bound, out_max=False)
+        x = x.flatten(1)
+        with self.span("fc"):                                         # :178
+            if "fc" in self.fc_split:
+                x = self.fc_split["fc"](x, relu=True)
+            else:
+                x = ops.linear(x, P["Box_Head.fc.weight"], P["Box_Head.fc.bias"], relu=True)
+        o = ops.linear(x, self.outs_w, self.outs_b)
+        return ops.box_head_outputs(o, rois, c.num_classes, c.bbox_reg_weights, clip_to=clip_to)
 
     # ---- the same chain as ONE library call (m3d_box_head_forward): the bare path of a detection step.  Between the host read of the
     # proposal counts and the first launch behind it the GPU is idle, so everything that does not need the counts is done before the

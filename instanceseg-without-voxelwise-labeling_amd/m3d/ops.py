@@ -1879,6 +1879,37 @@ def conv3d_wgrad(x, grad_out, k, dilation=1, tile_x=0):
     return dw
 
 
+def conv3d_wgrad_narrow_supported(batch, cin, cout, D, H, W, k=3):
+    """m3d_conv3d_wgrad_narrow_supported (host only): the dilation-1 weight gradient of this shape runs on the 2 x 8 x 8 tile kernel
+    (k = 3, W <= 8)"""
+    return bool(lib().m3d_conv3d_wgrad_narrow_supported(int(batch), int(cin), int(cout), int(D), int(H), int(W), int(k)))
+
+
+def conv3d_wgrad_narrow_plan(batch, cin, cout, D, H, W):
+    """What conv3d_wgrad_narrow launches for this shape (m3d_conv3d_wgrad_narrow_plan, host only): dict(tile_x, tile_y, slots)"""
+    v = [C.c_int(0) for _ in range(3)]
+    check(lib().m3d_conv3d_wgrad_narrow_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), 3, *[C.byref(a) for a in v]),
+          "conv3d_wgrad_narrow_plan")
+    return dict(zip(("tile_x", "tile_y", "slots"), (a.value for a in v)))
+
+
+def conv3d_wgrad_narrow(x, grad_out):
+    """dW [cout,cin,3,3,3] of a stride-1 pad-1 3^3 conv on a map at most 8 wide (m3d_conv3d_wgrad_narrow: fp32 MFMA on the 2 x 8 x 8
+    voxel tile): x [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA).  An unsupported shape is an error: ask
+    conv3d_wgrad_narrow_supported (or conv_plan.wgrad_kernel)."""
+    _need_gpu(x, grad_out)
+    x, grad_out = _f32c(x), _f32c(grad_out)
+    B, cin, D, H, W = x.shape
+    cout = grad_out.shape[1]
+    assert grad_out.shape == (B, cout, D, H, W)
+    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    wsb = lib().m3d_conv3d_wgrad_narrow_workspace_bytes(B, cin, cout, D, H, W, 3)
+    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+    check(lib().m3d_conv3d_wgrad_narrow(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, 3, _ptr(ws), C.c_size_t(wsb),
+                                        _stream()), "conv3d_wgrad_narrow")
+    return dw
+
+
 def conv3d_wgrad_f16x2_supported(batch, cin, cout, D, H, W):
     """m3d_conv3d_wgrad_f16x2_supported (host only): the k = 3 weight gradient of this shape runs on the f16 matrix cores"""
     return bool(lib().m3d_conv3d_wgrad_f16x2_supported(int(batch), int(cin), int(cout), int(D), int(H), int(W)))

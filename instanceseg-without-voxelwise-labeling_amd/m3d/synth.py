@@ -8,8 +8,13 @@ import torch
 from .model import dsn_layers
 
 
-def make_params(stride=8, num_anchors=35, mlp_dim=1024, roi_res=7, num_classes=2, seed=0, head=True):
-    """kaiming-normal conv/linear, biases N(0,0.1), BN gamma U[0.5,1.5], beta N(0,0.1), mean N(0,0.1), var U[0.5,1.5]."""
+def make_params(stride=8, num_anchors=35, mlp_dim=1024, roi_res=7, num_classes=2, seed=0, head=True, box_head="roi_2mlp_head",
+                conv_head_dim=128, num_stacked_convs=2):
+    """kaiming-normal conv/linear, biases N(0,0.1), BN gamma U[0.5,1.5], beta N(0,0.1), mean N(0,0.1), var U[0.5,1.5].
+    box_head = "roi_Xconv1fc_head": Box_Head.convs.{0,2,..} + Box_Head.fc (fast_rcnn_heads.py:120-179) instead of fc1 / fc2; the
+    default output does not depend on the two conv-head arguments."""
+    if box_head not in ("roi_2mlp_head", "roi_Xconv1fc_head"):
+        raise ValueError("make_params(box_head=%r): 'roi_2mlp_head' or 'roi_Xconv1fc_head'" % (box_head,))
     g = torch.Generator().manual_seed(seed)
     P = {}
     chans = {"conv1a": (1, 32, 5), "conv2a": (32, 64, 3), "conv2b": (64, 64, 3), "conv3a": (64, 128, 3),
@@ -34,9 +39,16 @@ def make_params(stride=8, num_anchors=35, mlp_dim=1024, roi_res=7, num_classes=2
     conv("RPN.RPN_conv", dim, dim, 3)
     conv("RPN.RPN_cls_score", dim, num_anchors, 1, scale=2.0)
     conv("RPN.RPN_bbox_pred", dim, num_anchors * 6, 1, scale=0.2)
-    if head:
+    if head and box_head == "roi_Xconv1fc_head":
+        cin = dim
+        for i in range(num_stacked_convs):
+            conv("Box_Head.convs.%d" % (2 * i), cin, conv_head_dim, 3)
+            cin = conv_head_dim
+        lin("Box_Head.fc", cin * roi_res ** 3, mlp_dim)
+    elif head:
         lin("Box_Head.fc1", dim * roi_res ** 3, mlp_dim)
         lin("Box_Head.fc2", mlp_dim, mlp_dim)
+    if head:
         lin("Box_Outs.cls_score", mlp_dim, num_classes)
         lin("Box_Outs.bbox_pred", mlp_dim, 6 * num_classes, scale=0.3)
     return P

@@ -598,3 +598,54 @@ class MaskHead(torch.nn.Module):
         else:
             x = torch.relu(self.upconv(x))
         return compat.conv3d(x, self.classify.weight, self.classify.bias, 1, 0)
+
+
+class ConvBoxHead(torch.nn.Module):
+    """roi_Xconv1fc_head followed by fast_rcnn_outputs (fast_rcnn_heads.py:120-179, 12-47) as one module under the reference's parameter
+    names convs.{0,2,..}, fc, cls_score, bbox_pred: its state_dict, prefixed Box_Head. / Box_Outs. by `detector_state`, is what
+    DetectorM3D takes.  Plain torch modules: under m3d.compat.install() RoIAlign3D, the convolutions and the linear layers run forward and
+    backward on the library's kernels (the convs' weight gradient on m3d_conv3d_wgrad, or on the 2 x 8 x 8 tile kernel under
+    compat.set_conv_wgrad_narrow(True)); on CPU tensors `trunk` is torch's own arithmetic.  Returns the class scores as logits, as the
+    reference does in training."""
+
+    def __init__(self, dim_in, stride, num_classes=2, conv_head_dim=128, num_stacked_convs=2, mlp_head_dim=1024, roi_res=7,
+                 sampling_ratio=2, cls_agnostic_bbox_reg=False):
+        super().__init__()
+        from . import compat
+        roi_res, dim = int(roi_res), int(conv_head_dim)
+        self.roi_align = compat.RoIAlign_3d(roi_res, roi_res, roi_res, 1.0 / float(stride), int(sampling_ratio))
+        layers, cin = [], int(dim_in)
+        for _ in range(int(num_stacked_convs)):
+            layers += [torch.nn.Conv3d(cin, dim, 3, 1, 1), torch.nn.ReLU(inplace=True)]
+            cin = dim
+        self.convs = torch.nn.Sequential(*layers)
+        self.fc = torch.nn.Linear(cin * roi_res ** 3, int(mlp_head_dim))
+        self.cls_score = torch.nn.Linear(int(mlp_head_dim), int(num_classes))
+        self.bbox_pred = torch.nn.Linear(int(mlp_head_dim), 6 * (2 if cls_agnostic_bbox_reg else int(num_classes)))
+        # The reference's roi_Xconv1fc_head._init_weights (fast_rcnn_heads.py:144-152) tests `isinstance(m, nn.Conv2d)`: its nn.Conv3d layers
+        # never match, so they keep torch's default initialisation (kaiming_uniform_(a = sqrt(5)), bias uniform) - MSRAFill is never
+        # applied to them.  What it effectively does is kept here: only fc gets XavierFill (uniform +- sqrt(3 / fan_in)) and a zero bias.
+        bound = math.sqrt(3.0 / self.fc.in_features)
+        torch.nn.init.uniform_(self.fc.weight, -bound, bound)
+        torch.nn.init.constant_(self.fc.bias, 0.0)
+        torch.nn.init.normal_(self.cls_score.weight, std=0.01)          # fast_rcnn_outputs._init_weights, :23-27
+        torch.nn.init.constant_(self.cls_score.bias, 0.0)
+        torch.nn.init.normal_(self.bbox_pred.weight, std=0.001)
+        torch.nn.init.constant_(self.bbox_pred.bias, 0.0)
+
+    def detector_state(self):
+        """the parameters under the keys of the reference's detector (and of DetectorM3D): Box_Head.convs.*, Box_Head.fc.*, Box_Outs.*"""
+        return {("Box_Outs." if k.startswith(("cls_score", "bbox_pred")) else "Box_Head.") + k: v for k, v in self.state_dict().items()}
+
+    def load_detector_state(self, params):
+        own = {k.split(".", 1)[1]: v for k, v in params.items() if k.startswith(("Box_Head.", "Box_Outs."))}
+        return self.load_state_dict(own)
+
+    def trunk(self, pooled):
+        """[R, dim_in, r, r, r] RoIAlign output -> (cls_score [R, num_classes] logits, bbox_pred [R, 6 num_classes])"""
+        x = self.convs(pooled)
+        x = torch.relu(self.fc(x.reshape(x.shape[0], -1)))
+        return self.cls_score(x), self.bbox_pred(x)
+
+    def forward(self, feat, rois7):
+        return self.trunk(self.roi_align(feat, rois7))

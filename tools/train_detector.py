@@ -10,7 +10,12 @@ Prints all four losses per step.  One fixed sample; this is not a training drive
 
 --mask spot (off by default; without it nothing changes) adds the mask branch: m3d.MaskHead on the same features, m3d.mask_targets from
 the spheres inscribed in the synthetic boxes, m3d.mask_losses; loss_mask joins the printed line and the sum.  --mask-dilation 2 builds that head with MRCNN.DILATION = 2 (the reference's
-default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated convs on the library, forward and backward."""
+default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated convs on the library, forward and backward.
+
+--box-head conv (default mlp, whose output stays as it is) trains m3d.ConvBoxHead (roi_Xconv1fc_head, fast_rcnn_heads.py:120-179:
+--conv-head-convs 3^3 convs of --conv-head-dim channels on the 7^3 grids, then one FC layer of --hidden) in place of the two-FC head;
+--wgrad-narrow moves the weight gradient of every intercepted dilation-1 conv on a map at most 8 wide (those head convs and, with
+--mask, the mask head's) to the 2 x 8 x 8 tile kernel (m3d.compat.set_conv_wgrad_narrow, csrc/conv3d_wgrad_narrow.hip)."""
 import argparse
 import os
 import sys
@@ -73,6 +78,13 @@ def main():
     ap.add_argument("--conv-dilated", choices=("torch", "m3d"), default="torch",
                     help="the dilation-2 convs (m3d.compat.set_conv_dilated): m3d = the library's dilated forward, dgrad and wgrad "
                          "(csrc/conv3d_wgrad_dilated.hip)")
+    ap.add_argument("--box-head", choices=("mlp", "conv"), default="mlp",
+                    help="mlp = RoIAlign -> two FC layers (roi_2mlp_head); conv = m3d.ConvBoxHead (roi_Xconv1fc_head)")
+    ap.add_argument("--conv-head-dim", type=int, default=128, help="with --box-head conv: FAST_RCNN.CONV_HEAD_DIM (the nuclei YAML has 128)")
+    ap.add_argument("--conv-head-convs", type=int, default=2, help="with --box-head conv: FAST_RCNN.NUM_STACKED_CONVS (the nuclei YAML has 2)")
+    ap.add_argument("--wgrad-narrow", action="store_true",
+                    help="dilation-1 conv weight gradients on maps at most 8 wide (the per-RoI convs) on the 2 x 8 x 8 tile kernel "
+                         "(m3d.compat.set_conv_wgrad_narrow)")
     a = ap.parse_args()
     if a.mask_dilation != 1 and not a.mask:
         ap.error("--mask-dilation needs --mask")
@@ -84,6 +96,7 @@ def main():
     assert torch.cuda.is_available(), "train_detector needs a GPU"
     m3d.compat.install()
     m3d.compat.set_conv_wgrad(a.wgrad)
+    m3d.compat.set_conv_wgrad_narrow(a.wgrad_narrow)
     m3d.compat.set_conv_train(a.conv)
     m3d.compat.set_roi_align_backward(a.roi_backward)
     m3d.compat.set_upconv(a.upconv)
@@ -95,7 +108,11 @@ def main():
     x = torch.from_numpy((vol - vol.mean()) / vol.std())[None, None].cuda()
     gt = torch.from_numpy(synth_volume_boxes(0, tile)).cuda()
     net = build_model(rcfg.num_anchors, a.width).cuda()
-    head = build_box_head(8 * a.width, a.hidden, bcfg.num_classes, rcfg.stride).cuda()
+    if a.box_head == "conv":
+        head = m3d.ConvBoxHead(8 * a.width, rcfg.stride, num_classes=bcfg.num_classes, conv_head_dim=a.conv_head_dim,
+                               num_stacked_convs=a.conv_head_convs, mlp_head_dim=a.hidden).cuda()
+    else:
+        head = build_box_head(8 * a.width, a.hidden, bcfg.num_classes, rcfg.stride).cuda()
     net.train()
     for m in net.modules():                       # running statistics; the reference trains on batch statistics (m3d.train.DsnBody does)
         if isinstance(m, torch.nn.BatchNorm3d):
