@@ -796,7 +796,25 @@ int m3d_conv3d_zw_bound_of(const float* d_x, long long n, float* d_slots, void* 
 int m3d_conv3d_zw_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
                           int width, const float* d_scale, const float* d_shift, int relu, int pool, const float* d_in_max,
                           float* d_out_max, void* stream);
-/* The same convolution on a PRM window strip [cin, depth, height, width] (peak_backprop_3d.py:8-34 batched over peaks: the windows of all
+/* The 3x3x3 convolution (stride 1, pad 1) [+ scale / shift + ReLU] on NARROW maps - width <= 8: the per-RoI convs on 7^3 RoI grids - on
+ * the f16 matrix cores at fp32 accuracy: the f16x2 split in the DIRECT form (27 taps, no Winograd; a zero product stays exact), csrc/conv3d_zn.hip.
+ * [batch, cin, depth, height, width] with cin % 16 == 0, width <= 8, any cout / depth / height / batch >= 1, cin * depth * height * width
+ * < 2^29 (m3d_conv3d_zn_supported).  One workgroup per unit of (64 output channels) x (8 x 8 x 4 voxels), the whole K inside it: no
+ * atomics on d_out, bit-identical run to run; every element of d_out is written.  d_in_max / d_out_max as m3d_conv3d_zw_forward's
+ * (m3d_conv3d_zw_slots() floats; d_out_max zeroed by the caller, or NULL); out = acc x (1 / (s_a s_b)) [x d_scale[c]] + d_shift[c], then
+ * ReLU.  m3d_conv3d_zn_pack_dgrad: the pack of the backward-data conv straight from the forward parameter [cout, cin, 3, 3, 3], equal to
+ * m3d_conv3d_zn_pack of w.flip(2, 3, 4).transpose(0, 1) byte for byte, m3d_conv3d_zn_packed_bytes(cout, cin) bytes (cout % 16 == 0).
+ * M3D_EINVAL (a NULL pointer, a non-positive count) and M3D_EUNSUPPORTED (a shape m3d_conv3d_zn_supported refuses) before any pointer is
+ * followed. */
+int m3d_conv3d_zn_supported(int cin, int cout, int depth, int height, int width);
+size_t m3d_conv3d_zn_packed_bytes(int cin, int cout);
+int m3d_conv3d_zn_pack(const float* d_weight, int cin, int cout, void* d_packed, void* stream);
+int m3d_conv3d_zn_pack_dgrad(const float* d_weight, int cin, int cout, void* d_packed, void* stream);
+long long m3d_conv3d_zn_launch_units(int batch, int cin, int cout, int depth, int height, int width);
+int m3d_conv3d_zn_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
+                          int width, const float* d_scale, const float* d_shift, int relu, const float* d_in_max, float* d_out_max,
+                          void* stream);
+/* The convolution of m3d_conv3d_zw_forward on a PRM window strip [cin, depth, height, width] (peak_backprop_3d.py:8-34 batched over peaks: the windows of all
  * peaks side by side along x, cell p = columns [pitch p, pitch (p + 1)), pitch a multiple of 4 - m3d_prm_strip_geometry mode 2) with ONE
  * OPERAND SCALE PER WINDOW: d_col_bound [num_peaks x 32], element 32 p = the largest |input| of window p (one cache line per window;
  * m3d_prm_strip_absmax: one sweep, rows = cin x depth x height; or the d_peak_max of m3d_prm_prepare_ex3).  The gradients of different peaks differ by orders of magnitude: each keeps its own 22 bits, and a window's

@@ -47,6 +47,8 @@ SYMBOLS = [
     "m3d_upconv3d_2x_wgrad", "m3d_upconv3d_2x_slices",
     "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_dilated", "m3d_conv3d_wgrad_dilated_tile", "m3d_conv3d_wgrad_dilated_plan",
     "m3d_conv3d_wgrad_narrow_supported", "m3d_conv3d_wgrad_narrow_workspace_bytes", "m3d_conv3d_wgrad_narrow_plan", "m3d_conv3d_wgrad_narrow",
+    "m3d_conv3d_zn_supported", "m3d_conv3d_zn_packed_bytes", "m3d_conv3d_zn_pack", "m3d_conv3d_zn_pack_dgrad", "m3d_conv3d_zn_launch_units",
+    "m3d_conv3d_zn_forward",
 ]
 
 
@@ -114,6 +116,7 @@ def _load(path):
     L.m3d_prm_strip_geometry.restype = C.c_int64
     L.m3d_conv3d_x3_launch_units.restype = C.c_longlong
     L.m3d_conv3d_zw_launch_units.restype = C.c_longlong
+    L.m3d_conv3d_zn_launch_units.restype = C.c_longlong
     for n in ("m3d_roi_align3d_workspace_bytes", "m3d_roi_align3d_backward_ordered_workspace_bytes","m3d_nms3d_workspace_bytes", "m3d_generate_proposals3d_workspace_bytes",
               "m3d_conv3d_packed_weight_bytes", "m3d_conv3d_x3_packed_bytes", "m3d_conv3d_x3f_packed_bytes", "m3d_conv3d_zw_packed_bytes", "m3d_reduce_minmax_multi_workspace_bytes", "m3d_conv3d_x3_workspace_bytes", "m3d_reduce_min_workspace_bytes", "m3d_reduce_min_multi_workspace_bytes", "m3d_norm1_workspace_bytes", "m3d_prm_small_dgrad_packed_bytes", "m3d_prm_small_dgrad_f16_packed_bytes", "m3d_prm_small_dgrad_f16_workspace_bytes", "m3d_linear_workspace_bytes", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_workspace_bytes", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_bf16x3_w32_workspace_bytes", "m3d_linear_bf16x3_roi_workspace_bytes", "m3d_mask_paste3d_workspace_bytes", "m3d_generate_proposals3d_batched_workspace_bytes",
               "m3d_box_results3d_batched_workspace_bytes", "m3d_nms3d_batched_workspace_bytes", "m3d_otsu2d_workspace_bytes",
@@ -123,7 +126,7 @@ def _load(path):
               "m3d_box_head_workspace_bytes", "m3d_linear_dgrad_workspace_bytes", "m3d_linear_wgrad_workspace_bytes",
               "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_peak_stimulation3d_workspace_bytes",
               "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes",
-              "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_narrow_workspace_bytes"):
+              "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_narrow_workspace_bytes", "m3d_conv3d_zn_packed_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

@@ -16,6 +16,8 @@ backward-data, so lib/modeling/DSN.py and lib/prm/peak_backprop_3d.py run unchan
 (opt-in) the k = 3, dilation 2, padding 2 convs of the mask head go there too, forward and backward.  Under
 set_conv_wgrad_narrow(True) (opt-in) the weight gradient of the dilation-1 3^3 convs on maps at most 8 wide - the per-RoI convs of the
 conv box head and of the mask head - runs on the 2 x 8 x 8 tile kernel (m3d_conv3d_wgrad_narrow).
+set_conv_train_narrow(True) (opt-in) runs the forward and the backward-data pass of those same convs on the narrow-map f16x2 kernel
+(m3d_conv3d_zn_forward, csrc/conv3d_zn.hip).
 """
 import importlib
 import sys
@@ -173,6 +175,7 @@ _orig_conv3d = None
 _pack_cache = {}          # (id(parameter), mode) -> (weakref to the parameter, _version, data_ptr, pack)
 STEM_DGRAD = "stem-dgrad"  # pseudo-mode: tap-flipped [C,125] weights of the 5^3 / Cin = 1 stem's backward-data
 ZW_PLAIN, ZW_DGRAD = "zw-plain", "zw-dgrad"     # pseudo-modes: the f16x2 kernel's packs of the forward / backward-data conv (set_conv_train)
+ZN_PLAIN, ZN_DGRAD = "zn-plain", "zn-dgrad"     # the narrow-map f16x2 kernel's packs (set_conv_train_narrow)
 
 
 def _make_pack(weight, mode):
@@ -181,6 +184,10 @@ def _make_pack(weight, mode):
         return ops.ZwConv3d(w)
     if mode == ZW_DGRAD:
         return ops.ZwConv3d.dgrad_of(w)
+    if mode == ZN_PLAIN:
+        return ops.ZnConv3d(w)
+    if mode == ZN_DGRAD:
+        return ops.ZnConv3d.dgrad_of(w)
     return ops.conv3d_stem5_dgrad_weights(w) if mode == STEM_DGRAD else ops.PackedConv3d(w, mode)
 
 
@@ -269,14 +276,41 @@ def get_conv_train():
     return _conv_train
 
 
+_conv_train_narrow = False           # False, or the routing threshold in launch units (set_conv_train_narrow)
+
+
+def set_conv_train_narrow(on, min_units=None):
+    """The forward and backward-data kernels of the intercepted 3^3 convs on maps at most 8 wide (the per-RoI convs of train.ConvBoxHead
+    and of train.MaskHead at dilation 1, on 7^3 grids): False (the default; install() does not change it) keeps what set_conv_train
+    gives them - the direct fp32 MFMA kernel, the zw kernel takes no map narrower than 12; True takes the narrow-map f16x2 kernel
+    (ops.ZnConv3d, csrc/conv3d_zn.hip; dgrad on its dgrad_of pack) for the layers and directions
+    conv_plan.train_conv_kernel(narrow=True) routes to it.  Such a forward sweeps x once; such a dgrad takes gy's bound from
+    m3d_conv3d_gy_reduce, which then also gives the bias gradient (as set_conv_train("f16x2") does).  Independent of set_conv_train; the
+    weight gradient's routing (set_conv_wgrad, set_conv_wgrad_narrow) is untouched.  min_units: the routing threshold in launch units
+    (None: conv_plan.ZN_MIN_UNITS; 0 routes every supported layer - tests and A/B runs; a call without it puts the default back).
+    Returns the previous setting (True / False)."""
+    global _conv_train_narrow
+    if min_units is not None and int(min_units) < 0:
+        raise ValueError("set_conv_train_narrow(min_units=%r): None or a count >= 0" % (min_units,))
+    prev = _conv_train_narrow is not False
+    _conv_train_narrow = (conv_plan.ZN_MIN_UNITS if min_units is None else int(min_units)) if on else False
+    return prev
+
+
+def get_conv_train_narrow():
+    return _conv_train_narrow is not False
+
+
 def _train_kernel(direction, setting, xshape, wshape):
-    """conv_plan.train_conv_kernel for a layer with weight `wshape` on a map `xshape` under setting = (mode, min_units)"""
-    mode, mu = setting
-    if mode == conv_plan.TRAIN_FP32:
+    """conv_plan.train_conv_kernel for a layer with weight `wshape` on a map `xshape` under setting = (mode, min_units[, narrow])"""
+    mode, mu = setting[:2]
+    narrow = setting[2] if len(setting) > 2 else False           # False, or the narrow kernel's threshold in units
+    if mode == conv_plan.TRAIN_FP32 and narrow is False:
         return conv_plan.TRAIN_FP32
     B, _, D, H, W = xshape
+    kw = dict(narrow=True, narrow_min_units=narrow) if narrow is not False else {}
     return conv_plan.train_conv_kernel(direction, B, wshape[1], wshape[0], D, H, W, mode,
-                                       min_units=conv_plan.ZW_MIN_UNITS if mu is None else mu, k=wshape[2])
+                                       min_units=conv_plan.ZW_MIN_UNITS if mu is None else mu, k=wshape[2], **kw)
 
 
 class _Conv3dFn(torch.autograd.Function):
@@ -284,12 +318,16 @@ class _Conv3dFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(weight, x if weight.requires_grad else None)
         ctx.has_bias = bias is not None
-        ctx.train = (_conv_train, _conv_train_min_units)      # the backward of this call follows the setting its forward ran under
+        ctx.train = (_conv_train, _conv_train_min_units, _conv_train_narrow)      # the backward of this call follows the setting its forward ran under
         ctx.x_max = None
         shift = bias.detach().contiguous() if bias is not None else None
-        if _train_kernel("forward", ctx.train, x.shape, weight.shape) == conv_plan.TRAIN_F16X2:
+        kern = _train_kernel("forward", ctx.train, x.shape, weight.shape)
+        if kern == conv_plan.TRAIN_F16X2:
             ctx.x_max = ops.ZwConv3d.bound_of(x)
             return _packed(weight, ZW_PLAIN)(x, ctx.x_max, shift=shift, out_max=False)[0]
+        if kern == conv_plan.TRAIN_F16X2_NARROW:
+            ctx.x_max = ops.ZnConv3d.bound_of(x)
+            return _packed(weight, ZN_PLAIN)(x, ctx.x_max, shift=shift, out_max=False)[0]
         return _packed(weight, ops.W_PLAIN)(x, shift=shift)
 
     @staticmethod
@@ -301,11 +339,13 @@ class _Conv3dFn(torch.autograd.Function):
         B, _, D, H, W = gy.shape
         cout, cin = weight.shape[0], weight.shape[1]
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
-        dgrad_zw = f16 and ctx.needs_input_grad[0] and _train_kernel("dgrad", ctx.train, gy.shape, weight.shape) == conv_plan.TRAIN_F16X2
+        dkern = _train_kernel("dgrad", ctx.train, gy.shape, weight.shape) if (ctx.needs_input_grad[0] and (f16 or ctx.train[2] is not False)) else None
+        dgrad_zw = f16 and dkern == conv_plan.TRAIN_F16X2
+        dgrad_zn = dkern == conv_plan.TRAIN_F16X2_NARROW
         wgrad = conv_plan.wgrad_kernel(B, cin, cout, D, H, W, _conv_wgrad, k=k, narrow=_conv_wgrad_narrow) if ctx.needs_input_grad[1] else None
         wgrad_zw = wgrad == conv_plan.WGRAD_F16X2
         gb = gy_max = None
-        if f16 and (dgrad_zw or wgrad_zw or want_gb):
+        if (f16 and (dgrad_zw or wgrad_zw or want_gb)) or dgrad_zn:
             # one pass over gy: the bias gradient and the bound both f16x2 kernels scale gy by.  In f16x2 mode gb ALWAYS comes from here, so
             # that a change of route (another batch size, min_units) never changes gb
             gb, gy_max = ops.conv3d_gy_reduce(gy, bias=want_gb)
@@ -315,6 +355,8 @@ class _Conv3dFn(torch.autograd.Function):
                 gx = ops.conv3d_stem5_dgrad(gy, _packed(weight, STEM_DGRAD))
             elif dgrad_zw:
                 gx = _packed(weight, ZW_DGRAD)(gy, gy_max, out_max=False)[0]
+            elif dgrad_zn:
+                gx = _packed(weight, ZN_DGRAD)(gy, gy_max, out_max=False)[0]
             else:
                 gx = _packed(weight, ops.W_DGRAD)(gy)
         gw = None

@@ -17,6 +17,12 @@ ITEM_LIMIT = 0x7FFFFFFF
 ZW_MIN_UNITS = 200
 
 DIRECT, STEM, ZW = "direct", "winograd F(2,5)x stem", "f16x2 F(2,3)z"         # kinds: keys of DetectorM3D.ISSUED_FRACTION
+ZN = "f16x2 narrow"                   # csrc/conv3d_zn.hip: maps at most 8 wide (the per-RoI convs), opt-in (narrow_f16)
+# The narrow f16x2 kernel runs one workgroup per (64 channels, 8 x 8 x 4 voxels); a 7^3 RoI grid is 2 units per RoI and 64 channels.
+# Every row of profiles/conv_narrow_f16.txt is faster than the direct fp32 kernel by more than the spreads, sweep / gy_reduce and the
+# per-step pack inside the window: 1.9 x .. 3.2 x from 512 units up, and the two smallest launches measured, 128 units (the mask head's
+# 256 -> 256 at R = 16, forward and dgrad), still 1.17 x and 1.13 x.  Nothing smaller was measured: it stays on fp32.
+ZN_MIN_UNITS = 128
 
 # kind: the kernel family; fused: the layer's max-pool runs in the conv launch (else ops.maxpool3d_2x follows); sweep: the kernel scales
 # its input by the input's operand bound (DetectorM3D._bound: left on the tensor by the launch that produced it, else one sweep)
@@ -56,6 +62,7 @@ def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3, narrow=False):
 
 
 TRAIN_FP32, TRAIN_F16X2 = "fp32", "f16x2"            # forward / dgrad kernels of a training conv: the direct fp32 MFMA kernel / conv3d_zw.hip
+TRAIN_F16X2_NARROW = "f16x2 narrow"                  # conv3d_zn.hip (ops.ZnConv3d): maps at most 8 wide, opt-in (compat.set_conv_train_narrow)
 # Output channels of the launched conv (forward: cout; dgrad: the forward cin) from which a direction routes to the f16x2 kernel.  Its
 # units are 64 channels wide: with 32 output channels half of every unit's matrix work is spent on channels that do not exist.  The PRM
 # engine keeps such a dgrad off the kernel (PRMEngine._dgrad_zw: >= 64, measured against the fp32 Winograd strips); against the DIRECT
@@ -66,24 +73,38 @@ TRAIN_FP32, TRAIN_F16X2 = "fp32", "f16x2"            # forward / dgrad kernels o
 TRAIN_F16X2_MIN_COUT = {"forward": 32, "dgrad": 32}
 
 
-def train_conv_kernel(direction, batch, cin, cout, D, H, W, mode, min_units=ZW_MIN_UNITS, k=3):
+def _narrow_takes(batch, ci, co, D, H, W, min_units):
+    """the narrow f16x2 kernel takes the launched conv [batch, ci, D, H, W] -> co and the launch reaches min_units units"""
+    L = ops.lib()
+    if batch < 1 or ci < 1 or co < 1 or not L.m3d_conv3d_zn_supported(ci, co, D, H, W):
+        return False
+    return L.m3d_conv3d_zn_launch_units(batch, ci, co, D, H, W) >= int(min_units)
+
+
+def train_conv_kernel(direction, batch, cin, cout, D, H, W, mode, min_units=ZW_MIN_UNITS, k=3, narrow=False, narrow_min_units=ZN_MIN_UNITS):
     """Which kernel runs the forward ("forward") or the backward-data ("dgrad") conv of a stride-1 'same' training layer with weight
     [cout, cin, k, k, k] on a map [batch, ., D, H, W]: TRAIN_F16X2 (m3d_conv3d_zw_forward; dgrad on an m3d_conv3d_zw_pack_dgrad pack) or
     TRAIN_FP32 (the direct fp32 MFMA kernel, ops.PackedConv3d).  The one place that says so (m3d.compat asks it, as it asks wgrad_kernel).
     mode: the caller's setting (compat.set_conv_train).  TRAIN_FP32 for mode "fp32", k != 3, channel counts or a map the zw kernel has no
     configuration for (m3d_conv3d_zw_supported on the launched conv: a dgrad swaps the channel roles), a batch item of ITEM_LIMIT bytes
-    or more, fewer launched output channels than TRAIN_F16X2_MIN_COUT[direction], fewer than min_units launch units.  A function of the
-    shape only."""
+    or more, fewer launched output channels than TRAIN_F16X2_MIN_COUT[direction], fewer than min_units launch units.
+    narrow: the caller's switch (compat.set_conv_train_narrow), independent of mode: a k = 3 layer the zw kernel does not take
+    (m3d_conv3d_zw_supported refuses maps narrower than 12), that m3d_conv3d_zn_supported takes for the launched conv (W <= 8, launched
+    input channels a multiple of 16) and whose launch has at least narrow_min_units units is TRAIN_F16X2_NARROW (ops.ZnConv3d; dgrad on its
+    dgrad_of pack).  With narrow left False the result is what it was without the argument.  A function of the shape only."""
     if direction not in TRAIN_F16X2_MIN_COUT:
         raise ValueError("direction %r: 'forward' or 'dgrad'" % (direction,))
     if mode not in (TRAIN_FP32, TRAIN_F16X2):
         raise ValueError("conv train mode %r: 'fp32' or 'f16x2'" % (mode,))
-    if mode == TRAIN_FP32 or int(k) != 3:
+    if int(k) != 3:
         return TRAIN_FP32
     batch, D, H, W = int(batch), int(D), int(H), int(W)
     ci, co = (int(cin), int(cout)) if direction == "forward" else (int(cout), int(cin))     # of the conv that is launched
     L = ops.lib()
-    if batch < 1 or ci < 1 or co < 1 or not L.m3d_conv3d_zw_supported(ci, co, D, H, W, 0):
+    zw_takes = batch >= 1 and ci >= 1 and co >= 1 and bool(L.m3d_conv3d_zw_supported(ci, co, D, H, W, 0))
+    if narrow and not zw_takes and _narrow_takes(batch, ci, co, D, H, W, narrow_min_units):
+        return TRAIN_F16X2_NARROW
+    if mode == TRAIN_FP32 or not zw_takes:
         return TRAIN_FP32
     # (m3d_conv3d_zw_forward itself refuses an item from 0x7FFFFF00 bytes: the 255 bytes below ITEM_LIMIT stay on fp32 too)
     if ci * D * H * W * 4 >= ITEM_LIMIT - 0xFF or co < TRAIN_F16X2_MIN_COUT[direction]:
@@ -93,15 +114,21 @@ def train_conv_kernel(direction, batch, cin, cout, D, H, W, mode, min_units=ZW_M
     return TRAIN_F16X2
 
 
-def plan_conv(layer, shape, argmax=False, f16=True, winograd=True):
+def plan_conv(layer, shape, argmax=False, f16=True, winograd=True, narrow_f16=False):
     """The kernel for `layer` (a LayerConv: cin, cout, k, pool and the packs the switches M3D_WINO / M3D_CONV_F16 gave it) on an input
     [B, cin, D, H, W], shape = (B, D, H, W).  Host queries of the library only.  The caller's needs:
     argmax    PRM mode: a pooled layer must deliver the pool's arg-max.  Only the direct kernels (fused, or ops.maxpool3d_2x behind the
               conv) and the 2-D Winograd family's fused pool do: such a layer never runs on f16x2, on un-fused Winograd or on the F(2,5) stem
     f16       the f16x2 kernel may run this layer (the PRM forward keeps the RPN conv off it)
-    winograd  False: direct kernels only (PRMEngine(wino_forward=False))"""
+    winograd  False: direct kernels only (PRMEngine(wino_forward=False))
+    narrow_f16  the narrow f16x2 kernel may run this layer (opt-in: the conv box head under M3D_HEAD_CONV_F16): a k = 3 layer without
+              pool whose map ZwConv3d does not take, that ZnConv3d (layer.zn) takes and whose launch has at least ZN_MIN_UNITS units is ZN"""
     B, D, H, W = (int(v) for v in shape)
     pool = layer.pool
+    zn = getattr(layer, "zn", None)
+    if (narrow_f16 and zn is not None and layer.k == 3 and not pool and not (layer.zw is not None and layer.zw.supports((D, H, W)))
+            and zn.supports((D, H, W)) and zn.units((B, layer.cin, D, H, W)) >= ZN_MIN_UNITS):
+        return Plan(ZN, False, True)
     if winograd and layer.cin * D * H * W * 4 < ITEM_LIMIT:
         if layer.stem is not None and not argmax and layer.stem.supports(W):
             return Plan(STEM, pool, False)
@@ -120,13 +147,16 @@ class LayerConv:
     input channel) and f16x2 F(2,3)z (cin % 16 == 0, conv_f16) where the switches allow them - and the execution of a plan.
     The only writer of the tensor attribute `_m3d_bound` (read by DetectorM3D._bound)."""
 
-    def __init__(self, weight, scale, shift, pool, wino_mode, conv_f16):
+    def __init__(self, weight, scale, shift, pool, wino_mode, conv_f16, narrow_f16=False):
         self.cout, self.cin, self.k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[-1])
         self.scale, self.shift, self.pool, self.conv_f16 = scale, shift, bool(pool), bool(conv_f16)
         self.conv = ops.PackedConv3d(weight)
         self.wino = ops.WinoConv3d(weight, two_d=(wino_mode == 2)) if (wino_mode and self.k == 3) else None
         self.stem = ops.StemWinoConv3d(weight) if (wino_mode and tuple(weight.shape[1:]) == (1, 5, 5, 5)) else None
         self.zw = ops.ZwConv3d(weight) if (conv_f16 and ops.ZwConv3d.supported(weight)) else None
+        # the narrow-map f16x2 pack (maps at most 8 wide: the per-RoI convs), only where the caller asked for it
+        self.narrow_f16 = bool(narrow_f16 and conv_f16)
+        self.zn = ops.ZnConv3d(weight) if (self.narrow_f16 and not pool and ops.ZnConv3d.supported(weight)) else None
         self.wino_kind = None if self.wino is None else "winograd F(2,3)x" if wino_mode != 2 else \
             "winograd F(2x4,3x3)" if ops.lib().m3d_conv3d_wino2_family() == 4 else "winograd F(2x2,3x3)"
         self._plans = {}
@@ -136,7 +166,7 @@ class LayerConv:
         key = (tuple(int(v) for v in shape), argmax, f16, winograd)
         p = self._plans.get(key)
         if p is None:
-            p = self._plans[key] = plan_conv(self, *key)
+            p = self._plans[key] = plan_conv(self, *key, narrow_f16=self.narrow_f16) if self.narrow_f16 else plan_conv(self, *key)
         return p
 
     def __call__(self, x, bound_of, out_max=None, argmax=False, **needs):
@@ -154,6 +184,8 @@ class LayerConv:
             y = (self.stem.pooled if p.fused else self.stem)(x, bound=bound if bound is not None else False, **kw)
         elif p.kind == ZW:
             y, bound = self.zw(x, in_max, pool=p.fused, out_max=out_max, **kw)
+        elif p.kind == ZN:
+            y, bound = self.zn(x, in_max, out_max=out_max, **kw)
         elif p.kind == DIRECT:
             y = self.conv.pooled(x, **kw, **want_am) if p.fused else self.conv(x, **kw)
         else:

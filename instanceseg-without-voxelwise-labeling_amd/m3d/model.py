@@ -94,6 +94,9 @@ class DetectorM3D:
         self.wino_mode = int(os.environ.get("M3D_WINO", "2"))
         self.use_wino = self.wino_mode != 0
         self.conv_f16 = self.use_wino and os.environ.get("M3D_CONV_F16", "1") == "1"
+        # M3D_HEAD_CONV_F16 (default 0; needs M3D_CONV_F16): the per-RoI convs of roi_Xconv1fc_head on the narrow-map f16x2 kernel
+        # (csrc/conv3d_zn.hip) where conv_plan.plan_conv(narrow_f16=True) routes them; unset, the head runs as it always did
+        self.head_conv_f16 = self.conv_f16 and os.environ.get("M3D_HEAD_CONV_F16", "0") == "1"
         self.body, self.convs = [], []                 # body[li] = (direct conv, scale, shift, pool); convs[li]: the layer's LayerConv
         for cname, bname, pool in dsn_layers(cfg.stride):
             c, b = "Conv_Body." + cname, "Conv_Body." + bname
@@ -158,8 +161,9 @@ class DetectorM3D:
 
     def _conv_head_layers(self, params, n):
         """The LayerConvs of roi_Xconv1fc_head's conv stack (conv + bias + ReLU, no BN, no pool)"""
+        kw = dict(narrow_f16=True) if self.head_conv_f16 else {}
         return [LayerConv(params["Box_Head.convs.%d.weight" % (2 * i)], None, params["Box_Head.convs.%d.bias" % (2 * i)].contiguous(), False,
-                          self.wino_mode, self.conv_f16) for i in range(n)]
+                          self.wino_mode, self.conv_f16, **kw) for i in range(n)]
 
     # ---- lib/modeling/DSN.py:57-68
     def body_layer(self, li, x, bound_slot=None):
@@ -320,6 +324,16 @@ class DetectorM3D:
             x = ops.roi_align3d_forward(feat, rois, c.roi_res, c.roi_res, c.roi_res, 1.0 / c.stride, c.sampling_ratio)
         if x.shape[0] == 0:                                           # no rows: nothing for the convs to launch
             x = x.new_zeros((0, self.head_convs[-1].cout) + tuple(x.shape[2:]))
+        elif self.head_conv_f16:
+            # the first conv's operand bound is the feature map's carried bound, not a sweep of the [R, C, 7, 7, 7] RoIAlign output: every
+            # RoIAlign value is a convex combination of feature-map values (the argument box_head_outputs uses for fc1); a map that
+            # carries none is swept.  Each conv's epilogue leaves the next conv's bound on its output (`_m3d_bound`): one chain, no sweep
+            fmax = self._carried_bound(feat)
+            first = (lambda t: fmax) if fmax is not None else self._bound
+            last = len(self.head_convs) - 1
+            for i, conv in enumerate(self.head_convs):                # :177
+                with self.span("head_conv%d" % (i + 1)):
+                    x = conv(x, first if i == 0 else self._bound, out_max=False if i == last else None)
         else:
             for i, conv in enumerate(self.head_convs):                # :177
                 with self.span("head_conv%d" % (i + 1)):

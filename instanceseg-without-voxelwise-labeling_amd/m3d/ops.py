@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "ZnConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1652,6 +1652,81 @@ class ZwConv3d(object):
                                           _ptr(scale) if scale is not None else None, _ptr(shift) if shift is not None else None,
                                           int(bool(relu)), int(bool(pool)), _ptr(in_max), _ptr(out_max) if out_max is not None else None,
                                           _stream()), "conv3d_zw_forward")
+        return out, out_max
+
+
+class ZnConv3d(object):
+    """3x3x3 conv (stride 1, pad 1) + scale/shift + ReLU on maps at most 8 wide - the per-RoI convs on 7^3 RoI grids - on the f16 matrix
+    cores at fp32 accuracy (csrc/conv3d_zn.hip: f16x2 split, direct 27 taps, one workgroup per 64 channels x 8 x 8 x 4 voxels, no atomics
+    on the output).  Operand bounds travel as ZwConv3d's: `in_max` is [SLOTS] device floats whose largest is the bound
+    (ZwConv3d.bound_of(x) sweeps a tensor), every call returns the same kind of array for its output.  __call__ -> (out, out_max)."""
+    SLOTS = ZwConv3d.SLOTS
+    bound_of = staticmethod(ZwConv3d.bound_of)
+
+    @staticmethod
+    def supported(weight, shape=None):
+        """weight [cout, cin, 3, 3, 3] with cin % 16 == 0; shape = (D, H, W) of the input (None: any supported map)."""
+        if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or int(weight.shape[1]) % 16 != 0:
+            return False
+        if shape is None:
+            return True
+        D, H, W = (int(v) for v in shape)
+        return bool(lib().m3d_conv3d_zn_supported(int(weight.shape[1]), int(weight.shape[0]), D, H, W))
+
+    def __init__(self, weight):
+        _need_gpu(weight)
+        w = _f32c(weight)
+        assert ZnConv3d.supported(w)
+        self.cout, self.cin = int(w.shape[0]), int(w.shape[1])
+        nbytes = lib().m3d_conv3d_zn_packed_bytes(self.cin, self.cout)
+        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        check(lib().m3d_conv3d_zn_pack(_ptr(w), self.cin, self.cout, _ptr(self.packed), _stream()), "conv3d_zn_pack")
+
+    @classmethod
+    def dgrad_of(cls, weight):
+        """The BACKWARD-DATA conv of a forward layer `weight` [cout, cin, 3, 3, 3] (cout % 16 == 0) as a ZnConv3d: cin = the layer's cout,
+        cout = the layer's cin.  The pack comes straight from the parameter's own layout (m3d_conv3d_zn_pack_dgrad): the bytes of
+        ZnConv3d(weight.flip(2, 3, 4).transpose(0, 1).contiguous()).packed without that copy."""
+        if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or int(weight.shape[0]) % 16 != 0:
+            raise ValueError("ZnConv3d.dgrad_of: weight [cout, cin, 3, 3, 3] with cout %% 16 == 0, got %s" % (tuple(weight.shape),))
+        _need_gpu(weight)
+        w = _f32c(weight)
+        self = cls.__new__(cls)
+        self.cout, self.cin = int(w.shape[1]), int(w.shape[0])
+        nbytes = lib().m3d_conv3d_zn_packed_bytes(self.cin, self.cout)
+        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        check(lib().m3d_conv3d_zn_pack_dgrad(_ptr(w), self.cout, self.cin, _ptr(self.packed), _stream()), "conv3d_zn_pack_dgrad")
+        return self
+
+    def supports(self, shape):
+        D, H, W = (int(v) for v in shape[-3:])
+        return bool(lib().m3d_conv3d_zn_supported(self.cin, self.cout, D, H, W))
+
+    def units(self, shape):
+        """workgroups of a launch on an input [B, cin, D, H, W] (or (D, H, W): one item): the library's own count"""
+        B = int(shape[0]) if len(shape) == 5 else 1
+        D, H, W = (int(v) for v in shape[-3:])
+        return int(lib().m3d_conv3d_zn_launch_units(B, self.cin, self.cout, D, H, W))
+
+    def __call__(self, x, in_max, scale=None, shift=None, relu=False, out=None, out_max=None):
+        """out_max: a ZEROED [SLOTS] float tensor to receive the output's bound (None: a fresh one; False: no bound output)."""
+        _need_gpu(x, in_max)
+        x = _f32c(x)
+        B, cin, D, H, W = x.shape
+        assert cin == self.cin and in_max.numel() == self.SLOTS and in_max.dtype == torch.float32
+        oshape = (B, self.cout, D, H, W)
+        _claim(out)
+        if out is None:
+            out = torch.empty(oshape, dtype=torch.float32, device=x.device)
+        assert tuple(out.shape) == oshape and out.is_contiguous()
+        if out_max is None:
+            out_max = torch.zeros((self.SLOTS,), dtype=torch.float32, device=x.device)
+        elif out_max is False:                             # nobody needs the output's bound (the last layer of a chain)
+            out_max = None
+        check(lib().m3d_conv3d_zn_forward(_ptr(x), _ptr(self.packed), _ptr(out), B, cin, self.cout, D, H, W,
+                                          _ptr(scale) if scale is not None else None, _ptr(shift) if shift is not None else None,
+                                          int(bool(relu)), _ptr(in_max), _ptr(out_max) if out_max is not None else None,
+                                          _stream()), "conv3d_zn_forward")
         return out, out_max
 
 

@@ -15,7 +15,9 @@ default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated conv
 --box-head conv (default mlp, whose output stays as it is) trains m3d.ConvBoxHead (roi_Xconv1fc_head, fast_rcnn_heads.py:120-179:
 --conv-head-convs 3^3 convs of --conv-head-dim channels on the 7^3 grids, then one FC layer of --hidden) in place of the two-FC head;
 --wgrad-narrow moves the weight gradient of every intercepted dilation-1 conv on a map at most 8 wide (those head convs and, with
---mask, the mask head's) to the 2 x 8 x 8 tile kernel (m3d.compat.set_conv_wgrad_narrow, csrc/conv3d_wgrad_narrow.hip)."""
+--mask, the mask head's) to the 2 x 8 x 8 tile kernel (m3d.compat.set_conv_wgrad_narrow, csrc/conv3d_wgrad_narrow.hip);
+--conv-narrow f16x2 runs the forward and the backward-data pass of those convs on the narrow-map f16x2 kernel
+(m3d.compat.set_conv_train_narrow, csrc/conv3d_zn.hip).  The two compose."""
 import argparse
 import os
 import sys
@@ -82,6 +84,9 @@ def main():
                     help="mlp = RoIAlign -> two FC layers (roi_2mlp_head); conv = m3d.ConvBoxHead (roi_Xconv1fc_head)")
     ap.add_argument("--conv-head-dim", type=int, default=128, help="with --box-head conv: FAST_RCNN.CONV_HEAD_DIM (the nuclei YAML has 128)")
     ap.add_argument("--conv-head-convs", type=int, default=2, help="with --box-head conv: FAST_RCNN.NUM_STACKED_CONVS (the nuclei YAML has 2)")
+    ap.add_argument("--conv-narrow", choices=("fp32", "f16x2"), default="fp32",
+                    help="forward and dgrad of the dilation-1 3^3 convs on maps at most 8 wide (the per-RoI convs): f16x2 = the narrow-map "
+                         "kernel on the f16 matrix cores at fp32 accuracy (m3d.compat.set_conv_train_narrow)")
     ap.add_argument("--wgrad-narrow", action="store_true",
                     help="dilation-1 conv weight gradients on maps at most 8 wide (the per-RoI convs) on the 2 x 8 x 8 tile kernel "
                          "(m3d.compat.set_conv_wgrad_narrow)")
@@ -97,6 +102,7 @@ def main():
     m3d.compat.install()
     m3d.compat.set_conv_wgrad(a.wgrad)
     m3d.compat.set_conv_wgrad_narrow(a.wgrad_narrow)
+    m3d.compat.set_conv_train_narrow(a.conv_narrow == "f16x2")
     m3d.compat.set_conv_train(a.conv)
     m3d.compat.set_roi_align_backward(a.roi_backward)
     m3d.compat.set_upconv(a.upconv)
