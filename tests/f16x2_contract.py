@@ -37,6 +37,8 @@ The constants of the kernels (derived from their code, not fitted):
   prm_small_f16.hip (SmallWindowDgrad)      G_N of peak p                relu(W)                3.01   81 cout_fwd / 16 + cout_fwd / 32 + 2
                                             (A = max|G_N[p]|, per peak)  (B = max relu(W))             (+ tot += acc every 2 chunks;
                                                                                                        x (X - off) rounds once more)
+                                            (f16_scale_of clamps s at 2^125: for A < 2^-111 the row holds with A_eff = max(A, 2^-111),
+                                            for which 1 / s = 2^-125 <= A_eff 2^-14 - tests/prm_small_cases.py, clamp edge)
   roi_align3d.hip roi_align3d_fwd_gemm_kernel  f, the feature map       M[k][bin] = Wz Wy Wx   6.51   3 K / 16, K <= 128 voxels
     (roi_align3d_forward(feat_absmax=))     (A = feat_absmax)            (scale 2^14: B = 1)           (the un-scaling is exact)
 The fc row assumes the planner's split-K (at most 64 slices); an OPT_TUNE_FC_SLICES override above 64 adds one step per slice.  The RoI
