@@ -18,6 +18,8 @@ set_conv_wgrad_narrow(True) (opt-in) the weight gradient of the dilation-1 3^3 c
 conv box head and of the mask head - runs on the 2 x 8 x 8 tile kernel (m3d_conv3d_wgrad_narrow).
 set_conv_train_narrow(True) (opt-in) runs the forward and the backward-data pass of those same convs on the narrow-map f16x2 kernel
 (m3d_conv3d_zn_forward, csrc/conv3d_zn.hip).
+What the setters say is one conv_plan.TrainSetting; what a routed conv launches under it, forward and backward, is decided by
+conv_plan.plan_train_conv alone, and the one conv Function (_Conv3dFn) runs that plan.
 """
 import importlib
 import sys
@@ -172,23 +174,14 @@ class _Legacy2D(object):
 
 # ----------------------------------------------------------------------------- F.conv3d interception
 _orig_conv3d = None
-_pack_cache = {}          # (id(parameter), mode) -> (weakref to the parameter, _version, data_ptr, pack)
-STEM_DGRAD = "stem-dgrad"  # pseudo-mode: tap-flipped [C,125] weights of the 5^3 / Cin = 1 stem's backward-data
-ZW_PLAIN, ZW_DGRAD = "zw-plain", "zw-dgrad"     # pseudo-modes: the f16x2 kernel's packs of the forward / backward-data conv (set_conv_train)
-ZN_PLAIN, ZN_DGRAD = "zn-plain", "zn-dgrad"     # the narrow-map f16x2 kernel's packs (set_conv_train_narrow)
-
-
-def _make_pack(weight, mode):
-    w = weight.detach()
-    if mode == ZW_PLAIN:
-        return ops.ZwConv3d(w)
-    if mode == ZW_DGRAD:
-        return ops.ZwConv3d.dgrad_of(w)
-    if mode == ZN_PLAIN:
-        return ops.ZnConv3d(w)
-    if mode == ZN_DGRAD:
-        return ops.ZnConv3d.dgrad_of(w)
-    return ops.conv3d_stem5_dgrad_weights(w) if mode == STEM_DGRAD else ops.PackedConv3d(w, mode)
+_pack_cache = {}          # (id(parameter), pack kind) -> (weakref to the parameter, _version, data_ptr, pack)
+_PACKS = {                # pack kind -> constructor from the detached weight
+    "plain": lambda w: ops.PackedConv3d(w, ops.W_PLAIN),     # the direct fp32 kernel, forward (dilation 1 and 2)
+    "dgrad": lambda w: ops.PackedConv3d(w, ops.W_DGRAD),     # ... its backward-data
+    "stem-dgrad": ops.conv3d_stem5_dgrad_weights,            # tap-flipped [C,125] weights of the 5^3 / Cin = 1 stem's backward-data
+    "zw-plain": ops.ZwConv3d, "zw-dgrad": ops.ZwConv3d.dgrad_of,       # the f16x2 kernel (set_conv_train)
+    "zn-plain": ops.ZnConv3d, "zn-dgrad": ops.ZnConv3d.dgrad_of,       # the narrow-map f16x2 kernel (set_conv_train_narrow)
+}
 
 
 def _packed(weight, mode):
@@ -197,19 +190,19 @@ def _packed(weight, mode):
     every call (peak_backprop_3d.py:41) whose address the allocator may later hand to another layer's temporary of the
     same shape - temporaries are therefore re-packed on every call (7-25 us, small next to the conv)."""
     if not isinstance(weight, torch.nn.Parameter):
-        return _make_pack(weight, mode)
+        return _PACKS[mode](weight.detach())
     key = (id(weight), mode)
     ent = _pack_cache.get(key)
     if ent is not None:
         ref, ver, ptr, pack = ent
         if ref() is weight and ver == weight._version and ptr == weight.data_ptr():
             return pack
-    pack = _make_pack(weight, mode)
+    pack = _PACKS[mode](weight.detach())
     _pack_cache[key] = (weakref.ref(weight, lambda _r, k=key: _pack_cache.pop(k, None)), weight._version, weight.data_ptr(), pack)
     return pack
 
 
-_conv_wgrad = conv_plan.WGRAD_FP32
+_setting = conv_plan.TrainSetting()          # what the setters below say; WHEN each field is read: the TrainSetting docstring
 
 
 def set_conv_wgrad(mode):
@@ -217,18 +210,15 @@ def set_conv_wgrad(mode):
     "f16x2" takes m3d_conv3d_wgrad_f16x2 (the f16 matrix cores at fp32 accuracy, two operand sweeps included) for the layers
     conv_plan.wgrad_kernel routes to it - every other layer (the 5^3 stem, k = 1, channel counts that are no multiple of 32) stays on the
     fp32 kernel.  Forward, dgrad and the bias gradient are the same under both settings.  Returns the previous setting."""
-    global _conv_wgrad
+    global _setting
     if mode not in (conv_plan.WGRAD_FP32, conv_plan.WGRAD_F16X2):
         raise ValueError("set_conv_wgrad(%r): 'fp32' or 'f16x2'" % (mode,))
-    prev, _conv_wgrad = _conv_wgrad, mode
+    prev, _setting = _setting.wgrad, _setting._replace(wgrad=mode)
     return prev
 
 
 def get_conv_wgrad():
-    return _conv_wgrad
-
-
-_conv_wgrad_narrow = False
+    return _setting.wgrad
 
 
 def set_conv_wgrad_narrow(on):
@@ -237,17 +227,13 @@ def set_conv_wgrad_narrow(on):
     2 x 4 x 16 voxel tile such a map fills to a third; True takes m3d_conv3d_wgrad_narrow (2 x 8 x 8) for the layers
     conv_plan.wgrad_kernel(narrow=True) routes to it.  A layer that set_conv_wgrad("f16x2") routes to the f16 kernel stays there; the
     forward, dgrad and the bias gradient are the same under both settings.  Returns the previous setting."""
-    global _conv_wgrad_narrow
-    prev, _conv_wgrad_narrow = _conv_wgrad_narrow, bool(on)
+    global _setting
+    prev, _setting = _setting.wgrad_narrow, _setting._replace(wgrad_narrow=bool(on))
     return prev
 
 
 def get_conv_wgrad_narrow():
-    return _conv_wgrad_narrow
-
-
-_conv_train = conv_plan.TRAIN_FP32
-_conv_train_min_units = None          # None: conv_plan.ZW_MIN_UNITS
+    return _setting.wgrad_narrow
 
 
 def set_conv_train(mode, min_units=None):
@@ -262,21 +248,17 @@ def set_conv_train(mode, min_units=None):
     As set_conv_wgrad("f16x2") already implies for its kernel: with a non-finite value in an operand the operand's bound is non-finite and
     the WHOLE result is, not only the elements the fp32 kernel's element-wise propagation would reach; Solver(stats=True).nonfinite is
     the guard."""
-    global _conv_train, _conv_train_min_units
+    global _setting
     if mode not in (conv_plan.TRAIN_FP32, conv_plan.TRAIN_F16X2):
         raise ValueError("set_conv_train(%r): 'fp32' or 'f16x2'" % (mode,))
     if min_units is not None and int(min_units) < 0:
         raise ValueError("set_conv_train(min_units=%r): None or a count >= 0" % (min_units,))
-    prev = _conv_train
-    _conv_train, _conv_train_min_units = mode, (None if min_units is None else int(min_units))
+    prev, _setting = _setting.train, _setting._replace(train=mode, min_units=None if min_units is None else int(min_units))
     return prev
 
 
 def get_conv_train():
-    return _conv_train
-
-
-_conv_train_narrow = False           # False, or the routing threshold in launch units (set_conv_train_narrow)
+    return _setting.train
 
 
 def set_conv_train_narrow(on, min_units=None):
@@ -289,107 +271,19 @@ def set_conv_train_narrow(on, min_units=None):
     weight gradient's routing (set_conv_wgrad, set_conv_wgrad_narrow) is untouched.  min_units: the routing threshold in launch units
     (None: conv_plan.ZN_MIN_UNITS; 0 routes every supported layer - tests and A/B runs; a call without it puts the default back).
     Returns the previous setting (True / False)."""
-    global _conv_train_narrow
+    global _setting
     if min_units is not None and int(min_units) < 0:
         raise ValueError("set_conv_train_narrow(min_units=%r): None or a count >= 0" % (min_units,))
-    prev = _conv_train_narrow is not False
-    _conv_train_narrow = (conv_plan.ZN_MIN_UNITS if min_units is None else int(min_units)) if on else False
+    prev = _setting.narrow is not None
+    _setting = _setting._replace(narrow=(conv_plan.ZN_MIN_UNITS if min_units is None else int(min_units)) if on else None)
     return prev
 
 
 def get_conv_train_narrow():
-    return _conv_train_narrow is not False
+    return _setting.narrow is not None
 
 
-def _train_kernel(direction, setting, xshape, wshape):
-    """conv_plan.train_conv_kernel for a layer with weight `wshape` on a map `xshape` under setting = (mode, min_units[, narrow])"""
-    mode, mu = setting[:2]
-    narrow = setting[2] if len(setting) > 2 else False           # False, or the narrow kernel's threshold in units
-    if mode == conv_plan.TRAIN_FP32 and narrow is False:
-        return conv_plan.TRAIN_FP32
-    B, _, D, H, W = xshape
-    kw = dict(narrow=True, narrow_min_units=narrow) if narrow is not False else {}
-    return conv_plan.train_conv_kernel(direction, B, wshape[1], wshape[0], D, H, W, mode,
-                                       min_units=conv_plan.ZW_MIN_UNITS if mu is None else mu, k=wshape[2], **kw)
-
-
-class _Conv3dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(weight, x if weight.requires_grad else None)
-        ctx.has_bias = bias is not None
-        ctx.train = (_conv_train, _conv_train_min_units, _conv_train_narrow)      # the backward of this call follows the setting its forward ran under
-        ctx.x_max = None
-        shift = bias.detach().contiguous() if bias is not None else None
-        kern = _train_kernel("forward", ctx.train, x.shape, weight.shape)
-        if kern == conv_plan.TRAIN_F16X2:
-            ctx.x_max = ops.ZwConv3d.bound_of(x)
-            return _packed(weight, ZW_PLAIN)(x, ctx.x_max, shift=shift, out_max=False)[0]
-        if kern == conv_plan.TRAIN_F16X2_NARROW:
-            ctx.x_max = ops.ZnConv3d.bound_of(x)
-            return _packed(weight, ZN_PLAIN)(x, ctx.x_max, shift=shift, out_max=False)[0]
-        return _packed(weight, ops.W_PLAIN)(x, shift=shift)
-
-    @staticmethod
-    def backward(ctx, gy):
-        weight, x = ctx.saved_tensors
-        gy = gy.contiguous()
-        f16 = ctx.train[0] == conv_plan.TRAIN_F16X2
-        k = weight.shape[2]
-        B, _, D, H, W = gy.shape
-        cout, cin = weight.shape[0], weight.shape[1]
-        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
-        dkern = _train_kernel("dgrad", ctx.train, gy.shape, weight.shape) if (ctx.needs_input_grad[0] and (f16 or ctx.train[2] is not False)) else None
-        dgrad_zw = f16 and dkern == conv_plan.TRAIN_F16X2
-        dgrad_zn = dkern == conv_plan.TRAIN_F16X2_NARROW
-        wgrad = conv_plan.wgrad_kernel(B, cin, cout, D, H, W, _conv_wgrad, k=k, narrow=_conv_wgrad_narrow) if ctx.needs_input_grad[1] else None
-        wgrad_zw = wgrad == conv_plan.WGRAD_F16X2
-        gb = gy_max = None
-        if (f16 and (dgrad_zw or wgrad_zw or want_gb)) or dgrad_zn:
-            # one pass over gy: the bias gradient and the bound both f16x2 kernels scale gy by.  In f16x2 mode gb ALWAYS comes from here, so
-            # that a change of route (another batch size, min_units) never changes gb
-            gb, gy_max = ops.conv3d_gy_reduce(gy, bias=want_gb)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            if k == 5:          # conv1a: one input channel -> VALU dgrad kernel (csrc/prm.hip)
-                gx = ops.conv3d_stem5_dgrad(gy, _packed(weight, STEM_DGRAD))
-            elif dgrad_zw:
-                gx = _packed(weight, ZW_DGRAD)(gy, gy_max, out_max=False)[0]
-            elif dgrad_zn:
-                gx = _packed(weight, ZN_DGRAD)(gy, gy_max, out_max=False)[0]
-            else:
-                gx = _packed(weight, ops.W_DGRAD)(gy)
-        gw = None
-        if ctx.needs_input_grad[1]:
-            if wgrad_zw:
-                # mode "fp32": sweeps both operands for their bounds; "f16x2": x's bound from the forward (if it ran on f16x2), gy's shared
-                gw = ops.conv3d_wgrad_f16x2(x, gy, ctx.x_max, gy_max)
-            elif wgrad == conv_plan.WGRAD_NARROW:
-                gw = ops.conv3d_wgrad_narrow(x, gy)
-            else:
-                gw = ops.conv3d_wgrad(x, gy, k)
-        if want_gb and gb is None:
-            gb = ops.conv3d_bias_grad(gy)
-        return gx, gw, gb
-
-
-def _qualifies(x, weight, stride, padding, dilation, groups):
-    def tup(v):
-        return (v,) * 3 if isinstance(v, int) else tuple(v)
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 5):
-        return False
-    k = weight.shape[2]
-    if weight.shape[3] != k or weight.shape[4] != k or groups != 1:
-        return False
-    if tup(stride) != (1, 1, 1) or tup(dilation) != (1, 1, 1) or isinstance(padding, str) or tup(padding) != (k // 2,) * 3:
-        return False
-    if k in (1, 3):
-        return True
-    return k == 5 and weight.shape[1] == 1 and weight.shape[0] <= 64
-
-
-CONV_DILATED_TORCH, CONV_DILATED_M3D = "torch", "m3d"
-_conv_dilated = CONV_DILATED_TORCH
+CONV_DILATED_TORCH, CONV_DILATED_M3D = conv_plan.DILATED_TORCH, conv_plan.DILATED_M3D
 
 
 def set_conv_dilated(mode):
@@ -398,60 +292,103 @@ def set_conv_dilated(mode):
     training: forward m3d_conv3d_forward_dilated, gx the same on the W_DGRAD pack, gw m3d_conv3d_wgrad_dilated, gb m3d_conv3d_bias_grad
     (DESIGN, "Dilated conv backward").  All fp32: set_conv_train("f16x2") and set_conv_wgrad("f16x2") do not reach these layers.  The
     backward of a call follows the mode its forward ran under.  Returns the previous mode."""
-    global _conv_dilated
+    global _setting
     if mode not in (CONV_DILATED_TORCH, CONV_DILATED_M3D):
         raise ValueError("set_conv_dilated(%r): 'torch' or 'm3d'" % (mode,))
-    prev, _conv_dilated = _conv_dilated, mode
+    prev, _setting = _setting.dilated, _setting._replace(dilated=mode)
     return prev
 
 
 def get_conv_dilated():
-    return _conv_dilated
+    return _setting.dilated
 
 
-class _Conv3dDilated2Fn(torch.autograd.Function):
-    """k = 3, dilation 2, padding 2 on the library's fp32 kernels.  Reached only under set_conv_dilated("m3d"), so whatever a backward
-    of this Function runs is what its forward's mode asked for."""
+class _Conv3dFn(torch.autograd.Function):
+    """A conv that conv3d() routes to the library (dilation 1 or 2): runs conv_plan.plan_train_conv's plan, the forward half in
+    forward, the backward half in backward.  Nothing is decided here."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, dilation):
         ctx.save_for_backward(weight, x if weight.requires_grad else None)
         ctx.has_bias = bias is not None
-        return _packed(weight, ops.W_PLAIN)(x, shift=bias.detach().contiguous() if bias is not None else None, dilation=2)
+        ctx.setting, ctx.xshape, ctx.dilation = _setting, tuple(x.shape), dilation      # (when each switch is read: TrainSetting)
+        shift = bias.detach().contiguous() if bias is not None else None
+        kind, sweep = conv_plan.plan_train_forward(_setting, ctx.xshape, weight.shape, dilation)
+        ctx.x_max = ops.ZwConv3d.bound_of(x) if sweep else None        # kept for the f16x2 wgrad
+        if kind == conv_plan.TRAIN_F16X2:
+            return _packed(weight, "zw-plain")(x, ctx.x_max, shift=shift, out_max=False)[0]
+        if kind == conv_plan.TRAIN_F16X2_NARROW:
+            return _packed(weight, "zn-plain")(x, ctx.x_max, shift=shift, out_max=False)[0]
+        if kind == conv_plan.TRAIN_DILATED:
+            return _packed(weight, "plain")(x, shift=shift, dilation=2)
+        return _packed(weight, "plain")(x, shift=shift)
 
     @staticmethod
     def backward(ctx, gy):
         weight, x = ctx.saved_tensors
         gy = gy.contiguous()
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = _packed(weight, ops.W_DGRAD)(gy, dilation=2)
-        if ctx.needs_input_grad[1]:
+        setting = ctx.setting._replace(wgrad=_setting.wgrad, wgrad_narrow=_setting.wgrad_narrow)
+        needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
+        dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs)
+        gx = gw = gb = gy_max = None
+        if gy_reduce:
+            gb, gy_max = ops.conv3d_gy_reduce(gy, bias=gb_from == conv_plan.GB_REDUCE)
+
+        if dgrad == conv_plan.DGRAD_STEM:
+            gx = ops.conv3d_stem5_dgrad(gy, _packed(weight, "stem-dgrad"))
+        elif dgrad == conv_plan.TRAIN_F16X2:
+            gx = _packed(weight, "zw-dgrad")(gy, gy_max, out_max=False)[0]
+        elif dgrad == conv_plan.TRAIN_F16X2_NARROW:
+            gx = _packed(weight, "zn-dgrad")(gy, gy_max, out_max=False)[0]
+        elif dgrad == conv_plan.TRAIN_DILATED:
+            gx = _packed(weight, "dgrad")(gy, dilation=2)
+        elif dgrad == conv_plan.TRAIN_FP32:
+            gx = _packed(weight, "dgrad")(gy)
+
+        if wgrad == conv_plan.WGRAD_F16X2:
+            # x's bound from the forward where that ran on an f16x2 kernel, gy's from the reduce where that ran; a missing one is swept
+            gw = ops.conv3d_wgrad_f16x2(x, gy, ctx.x_max, gy_max)
+        elif wgrad == conv_plan.WGRAD_NARROW:
+            gw = ops.conv3d_wgrad_narrow(x, gy)
+        elif wgrad == conv_plan.WGRAD_DILATED:
             gw = ops.conv3d_wgrad(x, gy, 3, dilation=2)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
+        elif wgrad == conv_plan.WGRAD_FP32:
+            gw = ops.conv3d_wgrad(x, gy, weight.shape[2])
+
+        if gb_from == conv_plan.GB_BIAS_GRAD:
             gb = ops.conv3d_bias_grad(gy)
-        return gx, gw, gb
+        return gx, gw, gb, None
 
 
-def _qualifies_dilated2(x, weight, bias, stride, padding, dilation, groups):
+def _routed_dilation(x, weight, bias, stride, padding, dilation, groups):
+    """The dilation of the library conv this call runs as, or None for torch's own.  1: fp32, CUDA, NCDHW, stride 1, padding k // 2,
+    groups 1, k in {1, 3} or the 5^3 / Cin = 1 stem (any strides of x: the caller makes it contiguous; nothing is asked of the bias).
+    2, only under set_conv_dilated("m3d"): k = 3, padding 2, and a contiguous x, matching channels and a well-formed bias."""
     def tup(v):
         return (v,) * 3 if isinstance(v, int) else tuple(v)
-    if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda and x.dtype == torch.float32
-            and weight.dtype == torch.float32 and x.dim() == 5 and x.is_contiguous() and weight.dim() == 5):
-        return False
-    if tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[1] != x.shape[1] or groups != 1:
-        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 5):
+        return None
+    k = weight.shape[2]
+    if weight.shape[3] != k or weight.shape[4] != k or groups != 1 or tup(stride) != (1, 1, 1):
+        return None
+    if tup(dilation) == (1, 1, 1):
+        if isinstance(padding, str) or tup(padding) != (k // 2,) * 3:
+            return None
+        return 1 if (k in (1, 3) or (k == 5 and weight.shape[1] == 1 and weight.shape[0] <= 64)) else None
+    if _setting.dilated != CONV_DILATED_M3D or tup(dilation) != (2, 2, 2) or isinstance(padding, str) or tup(padding) != (2, 2, 2):
+        return None
+    if not (k == 3 and weight.is_cuda and weight.dim() == 5 and x.is_contiguous() and weight.shape[1] == x.shape[1]):
+        return None
     if bias is not None and not (torch.is_tensor(bias) and bias.is_cuda and bias.dtype == torch.float32
                                  and tuple(bias.shape) == (weight.shape[0],)):
-        return False
-    return tup(stride) == (1, 1, 1) and tup(dilation) == (2, 2, 2) and not isinstance(padding, str) and tup(padding) == (2, 2, 2)
+        return None
+    return 2
 
 
 def conv3d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
-    if _qualifies(input, weight, stride, padding, dilation, groups):
-        return _Conv3dFn.apply(input.contiguous(), weight, bias)
-    if _conv_dilated == CONV_DILATED_M3D and _qualifies_dilated2(input, weight, bias, stride, padding, dilation, groups):
-        return _Conv3dDilated2Fn.apply(input, weight, bias)
+    routed = _routed_dilation(input, weight, bias, stride, padding, dilation, groups)
+    if routed is not None:
+        return _Conv3dFn.apply(input.contiguous(), weight, bias, routed)        # (.contiguous(): dilation 1 only, a dilation-2 input already is)
     # a direct call (train.MaskHead) before install_conv3d(): torch's own is still in its place
     orig = _orig_conv3d if _orig_conv3d is not None else torch.nn.functional.conv3d
     return orig(input, weight, bias, stride, padding, dilation, groups)

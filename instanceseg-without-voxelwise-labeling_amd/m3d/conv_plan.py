@@ -2,7 +2,11 @@
 
 `plan_conv` is the only place the order of the kernel families lives (DESIGN.md "Conv dispatch"): the detection path
 (DetectorM3D.body_layer / rpn), bench.py's roofline bookkeeping (DetectorM3D.conv_work) and the PRM forward
-(PRMEngine.forward_response) all ask it, each with its own needs, and run what it says by calling the layer's `LayerConv`."""
+(PRMEngine.forward_response) all ask it, each with its own needs, and run what it says by calling the layer's `LayerConv`.
+
+`plan_train_conv` is the same for the training path (m3d.compat.conv3d and its backward): what the switches of m3d.compat say travels
+as a `TrainSetting`, the rules `train_conv_kernel` and `wgrad_kernel` are its rows, and `compat._Conv3dFn` runs the plan (DESIGN.md
+"Training conv dispatch")."""
 import collections
 
 import torch
@@ -43,7 +47,7 @@ WGRAD_NARROW = "fp32 narrow"
 
 def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3, narrow=False):
     """Which kernel computes the weight gradient of a stride-1 'same' conv layer with x [batch, cin, D, H, W]: WGRAD_F16X2, WGRAD_NARROW
-    or WGRAD_FP32.  The one place that says so (m3d.compat asks it in backward).  mode: the caller's setting (compat.set_conv_wgrad):
+    or WGRAD_FP32.  The one place that says so (a row of plan_train_conv).  mode: the caller's setting (compat.set_conv_wgrad):
     "fp32" keeps every layer on m3d_conv3d_wgrad; "f16x2" moves the layers the f16x2 kernel takes (k = 3, cin and cout multiples of 32:
     m3d_conv3d_wgrad_f16x2_supported) and was measured to win on by more than the spread of the measurement: layers of at least
     WGRAD_F16X2_MIN_WORK products per tap.  narrow: the caller's switch (compat.set_conv_wgrad_narrow): a k = 3 layer that would end on
@@ -84,7 +88,7 @@ def _narrow_takes(batch, ci, co, D, H, W, min_units):
 def train_conv_kernel(direction, batch, cin, cout, D, H, W, mode, min_units=ZW_MIN_UNITS, k=3, narrow=False, narrow_min_units=ZN_MIN_UNITS):
     """Which kernel runs the forward ("forward") or the backward-data ("dgrad") conv of a stride-1 'same' training layer with weight
     [cout, cin, k, k, k] on a map [batch, ., D, H, W]: TRAIN_F16X2 (m3d_conv3d_zw_forward; dgrad on an m3d_conv3d_zw_pack_dgrad pack) or
-    TRAIN_FP32 (the direct fp32 MFMA kernel, ops.PackedConv3d).  The one place that says so (m3d.compat asks it, as it asks wgrad_kernel).
+    TRAIN_FP32 (the direct fp32 MFMA kernel, ops.PackedConv3d).  The one place that says so (a row of plan_train_conv, as wgrad_kernel is).
     mode: the caller's setting (compat.set_conv_train).  TRAIN_FP32 for mode "fp32", k != 3, channel counts or a map the zw kernel has no
     configuration for (m3d_conv3d_zw_supported on the launched conv: a dgrad swaps the channel roles), a batch item of ITEM_LIMIT bytes
     or more, fewer launched output channels than TRAIN_F16X2_MIN_COUT[direction], fewer than min_units launch units.
@@ -112,6 +116,98 @@ def train_conv_kernel(direction, batch, cin, cout, D, H, W, mode, min_units=ZW_M
     if L.m3d_conv3d_zw_launch_units(batch, ci, co, D, H, W) < int(min_units):
         return TRAIN_FP32
     return TRAIN_F16X2
+
+
+# ----------------------------------------------------------------------------- the training plan (m3d.compat._Conv3dFn runs it)
+DILATED_TORCH, DILATED_M3D = "torch", "m3d"          # who runs the k = 3, dilation 2, padding 2 convs (compat.set_conv_dilated)
+TRAIN_DILATED = "dilated"                            # forward / dgrad kind: m3d_conv3d_forward_dilated (fp32, on the W_PLAIN / W_DGRAD pack)
+DGRAD_STEM = "stem"                                  # dgrad kind: the VALU kernel of the 5^3 / Cin = 1 stem (m3d_conv3d_stem5_dgrad)
+WGRAD_DILATED = "dilated"                            # wgrad kind: m3d_conv3d_wgrad_dilated
+GB_REDUCE, GB_BIAS_GRAD = "gy_reduce", "bias_grad"   # where the bias gradient comes from
+
+
+class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narrow wgrad wgrad_narrow dilated",
+                                          defaults=(TRAIN_FP32, None, None, WGRAD_FP32, False, DILATED_TORCH))):
+    """Everything the switches of m3d.compat say about a training conv, immutable; the defaults are install()'s.
+    train         TRAIN_FP32 / TRAIN_F16X2 (set_conv_train)
+    min_units     its routing threshold in launch units; None: ZW_MIN_UNITS
+    narrow        None: the narrow f16x2 kernel is off; else its routing threshold in launch units (set_conv_train_narrow)
+    wgrad         WGRAD_FP32 / WGRAD_F16X2 (set_conv_wgrad)
+    wgrad_narrow  bool (set_conv_wgrad_narrow)
+    dilated       DILATED_TORCH / DILATED_M3D (set_conv_dilated)
+    WHEN each is read: train, min_units, narrow and dilated are those of the FORWARD call - the conv Function keeps the forward's
+    setting and its backward follows it, whatever the setters were told in between; wgrad and wgrad_narrow are read when the BACKWARD
+    runs (the Function puts the current two into the kept setting before it asks plan_train_backward)."""
+    __slots__ = ()
+
+
+# forward: TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED; sweep: the forward sweeps x for its operand bound and keeps it
+# (for the f16x2 wgrad); dgrad: None (gx not needed) / DGRAD_STEM / TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED;
+# wgrad: None (gw not needed) / WGRAD_FP32 / WGRAD_F16X2 / WGRAD_NARROW / WGRAD_DILATED; gy_reduce: m3d_conv3d_gy_reduce runs first (one
+# pass over gy: its operand bound, and the bias gradient where needed); gb: None / GB_REDUCE / GB_BIAS_GRAD
+TrainConvPlan = collections.namedtuple("TrainConvPlan", "forward sweep dgrad wgrad gy_reduce gb")
+
+
+def _train_rule(direction, setting, xshape, wshape):
+    """train_conv_kernel's row for a dilation-1 layer with weight `wshape` on a map `xshape` under `setting`"""
+    if setting.train == TRAIN_FP32 and setting.narrow is None:
+        return TRAIN_FP32
+    B, _, D, H, W = xshape
+    kw = {} if setting.narrow is None else dict(narrow=True, narrow_min_units=setting.narrow)
+    return train_conv_kernel(direction, B, wshape[1], wshape[0], D, H, W, setting.train,
+                             min_units=ZW_MIN_UNITS if setting.min_units is None else setting.min_units, k=wshape[2], **kw)
+
+
+def plan_train_forward(setting, xshape, wshape, dilation):
+    """(forward, sweep) of plan_train_conv: what the forward of the call needs, and no library query beyond that"""
+    if dilation == 2:
+        return TRAIN_DILATED, False
+    forward = _train_rule("forward", setting, xshape, wshape)
+    return forward, forward != TRAIN_FP32
+
+
+def plan_train_backward(setting, xshape, wshape, dilation, needs):
+    """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs"""
+    gx, gw, gb = (bool(v) for v in needs)
+    if dilation == 2:                                  # all fp32: train and wgrad do not reach these layers
+        return (TRAIN_DILATED if gx else None), (WGRAD_DILATED if gw else None), False, (GB_BIAS_GRAD if gb else None)
+    B, _, D, H, W = xshape
+    cout, cin, k = wshape[:3]
+    dgrad = None if not gx else DGRAD_STEM if k == 5 else _train_rule("dgrad", setting, xshape, wshape)
+    wgrad = wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow) if gw else None
+    # one pass over gy gives the bound both f16x2 kernels scale gy by, and the bias gradient.  In train mode f16x2 gb ALWAYS comes from
+    # it, so that a change of route (another batch size, min_units) never changes gb; in mode fp32 only the narrow f16x2 dgrad asks for
+    # it (the f16x2 wgrad then sweeps both operands itself)
+    gy_reduce = (setting.train == TRAIN_F16X2 and (dgrad == TRAIN_F16X2 or wgrad == WGRAD_F16X2 or gb)) or dgrad == TRAIN_F16X2_NARROW
+    return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
+
+
+def plan_train_conv(setting, xshape, wshape, dilation, needs):
+    """What a training conv that m3d.compat.conv3d routes to the library launches, forward and backward: a TrainConvPlan.  The only place
+    that combines the rules (train_conv_kernel and wgrad_kernel are its rows); host queries of the library only, a function of its
+    arguments only.  setting: a TrainSetting; xshape [B, cin, D, H, W]; wshape [cout, cin, k, k, k]; dilation: 1 (stride 1, padding
+    k // 2, k in {1, 3} or the 5^3 / Cin = 1 stem) or 2 (k = 3, padding 2, only routed under DILATED_M3D); needs = (gx, gw, gb) of
+    needs_input_grad, gb already False for a layer without bias.
+
+    | field     | value              | condition                                                                                      |
+    | forward   | TRAIN_DILATED      | dilation 2                                                                                     |
+    |           | else               | train_conv_kernel("forward", ...) under setting.train / min_units / narrow                     |
+    | sweep     | True               | forward is TRAIN_F16X2 or TRAIN_F16X2_NARROW                                                   |
+    | dgrad     | None               | gx not needed                                                                                  |
+    |           | TRAIN_DILATED      | dilation 2                                                                                     |
+    |           | DGRAD_STEM         | k = 5                                                                                          |
+    |           | else               | train_conv_kernel("dgrad", ...)                                                                |
+    | wgrad     | None               | gw not needed                                                                                  |
+    |           | WGRAD_DILATED      | dilation 2                                                                                     |
+    |           | else               | wgrad_kernel(...) under setting.wgrad / wgrad_narrow                                           |
+    | gy_reduce | True               | dilation 1 and: train is f16x2 and (dgrad or wgrad is f16x2, or gb needed); or dgrad is narrow |
+    | gb        | None               | gb not needed                                                                                  |
+    |           | GB_REDUCE          | gy_reduce                                                                                      |
+    |           | GB_BIAS_GRAD       | else                                                                                           |
+
+    compat asks the two halves when it needs them (plan_train_forward in forward, plan_train_backward in backward): a call makes the
+    library queries of the directions it runs and no others."""
+    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation) + plan_train_backward(setting, xshape, wshape, dilation, needs)))
 
 
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True, narrow_f16=False):

@@ -1512,51 +1512,107 @@ def roi_normalize(image_u16, prm_u8, boxes, mode, boxes_host=None, map_index=Non
 
 
 # ------------------------------------------------------------------ Winograd-x 3x3x3 forward
-class ZwConv3d(object):
-    """3x3x3 forward conv (stride 1, pad 1) + scale/shift + ReLU [+ MaxPool3d(2,2)] on the f16 matrix cores at fp32 accuracy
-    (csrc/conv3d_zw.hip: f16x2 split, Winograd F(2,3) along z).  The operand scale comes from a BOUND of the input's largest magnitude
-    that travels with the activations: `in_max` is a device array of SLOTS floats (its largest entry is the bound; `bound_of(x)` sweeps a
-    tensor), and every call returns the same kind of array for its OUTPUT (filled by the kernel's epilogue), so a chain of layers sweeps
-    only its first input.  __call__ -> (out, out_max)."""
+class _F16x2Conv3d(object):
+    """What the two f16x2 3x3x3 conv wrappers share, over the entry-point family m3d_conv3d_<FAMILY>_* (ZwConv3d: "zw", ZnConv3d: "zn"):
+    the weight packs (forward, and backward-data straight from the parameter's layout), the host queries, and how operand bounds
+    travel.  The operand scale comes from a BOUND of the input's largest magnitude that travels with the activations: `in_max` is a
+    device array of SLOTS floats (its largest entry is the bound; `bound_of(x)` sweeps a tensor), and every call returns the same kind of
+    array for its OUTPUT (filled by the kernel's epilogue), so a chain of layers sweeps only its first input."""
     SLOTS = 32
+    FAMILY = None
 
-    @staticmethod
-    def supported(weight, shape=None, pool=False):
+    @classmethod
+    def _entry(cls, name):
+        return getattr(lib(), "m3d_conv3d_%s_%s" % (cls.FAMILY, name))
+
+    @classmethod
+    def _takes(cls, cin, cout, D, H, W, pool):
+        """m3d_conv3d_<FAMILY>_supported; only zw has a fused pool, and only its query takes the argument"""
+        if cls.FAMILY == "zw":
+            return bool(cls._entry("supported")(cin, cout, D, H, W, int(bool(pool))))
+        return not pool and bool(cls._entry("supported")(cin, cout, D, H, W))
+
+    @classmethod
+    def supported(cls, weight, shape=None, pool=False):
         """weight [cout, cin, 3, 3, 3] with cin % 16 == 0; shape = (D, H, W) of the input (None: any supported map)."""
         if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or int(weight.shape[1]) % 16 != 0:
             return False
         if shape is None:
             return True
         D, H, W = (int(v) for v in shape)
-        return bool(lib().m3d_conv3d_zw_supported(int(weight.shape[1]), int(weight.shape[0]), D, H, W, int(bool(pool))))
+        return cls._takes(int(weight.shape[1]), int(weight.shape[0]), D, H, W, pool)
+
+    def _pack(self, w, cin, cout, entry):
+        """the logical conv cin -> cout from the weight w [., ., 3, 3, 3], packed by m3d_conv3d_<FAMILY>_<entry>(w, w's cin, w's cout, ..)"""
+        self.cout, self.cin = cout, cin
+        nbytes = self._entry("packed_bytes")(cin, cout)
+        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        check(self._entry(entry)(_ptr(w), int(w.shape[1]), int(w.shape[0]), _ptr(self.packed), _stream()), "conv3d_%s_%s" % (self.FAMILY, entry))
 
     def __init__(self, weight):
         _need_gpu(weight)
         w = _f32c(weight)
-        assert ZwConv3d.supported(w)
-        self.cout, self.cin = int(w.shape[0]), int(w.shape[1])
-        nbytes = lib().m3d_conv3d_zw_packed_bytes(self.cin, self.cout)
-        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-        check(lib().m3d_conv3d_zw_pack(_ptr(w), self.cin, self.cout, _ptr(self.packed), _stream()), "conv3d_zw_pack")
+        assert self.supported(w)
+        self._pack(w, int(w.shape[1]), int(w.shape[0]), "pack")
 
     @classmethod
     def dgrad_of(cls, weight):
-        """The BACKWARD-DATA conv of a forward layer `weight` [cout, cin, 3, 3, 3] (cout % 16 == 0) as a ZwConv3d: cin = the layer's cout,
-        cout = the layer's cin.  The pack comes straight from the parameter's own layout (m3d_conv3d_zw_pack_dgrad): the bytes of
-        ZwConv3d(weight.flip(2, 3, 4).transpose(0, 1).contiguous()).packed without that copy."""
+        """The BACKWARD-DATA conv of a forward layer `weight` [cout, cin, 3, 3, 3] (cout % 16 == 0) as a conv of this class: cin = the
+        layer's cout, cout = the layer's cin.  The pack comes straight from the parameter's own layout (m3d_conv3d_<FAMILY>_pack_dgrad):
+        the bytes of cls(weight.flip(2, 3, 4).transpose(0, 1).contiguous()).packed without that copy."""
+        cls._check_dgrad_weight(weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3) and int(weight.shape[0]) % 16 == 0, weight)
         _need_gpu(weight)
         w = _f32c(weight)
-        assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and int(w.shape[0]) % 16 == 0
         self = cls.__new__(cls)
-        self.cout, self.cin = int(w.shape[1]), int(w.shape[0])
-        nbytes = lib().m3d_conv3d_zw_packed_bytes(self.cin, self.cout)
-        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-        check(lib().m3d_conv3d_zw_pack_dgrad(_ptr(w), self.cout, self.cin, _ptr(self.packed), _stream()), "conv3d_zw_pack_dgrad")
+        self._pack(w, int(w.shape[0]), int(w.shape[1]), "pack_dgrad")
         return self
 
     def supports(self, shape, pool=False):
         D, H, W = (int(v) for v in shape[-3:])
-        return bool(lib().m3d_conv3d_zw_supported(self.cin, self.cout, D, H, W, int(bool(pool))))
+        return self._takes(self.cin, self.cout, D, H, W, pool)
+
+    def units(self, shape):
+        """workgroups of a launch on an input [B, cin, D, H, W] (or (D, H, W): one item): the library's own count, (64 channels) x (its tile)"""
+        B = int(shape[0]) if len(shape) == 5 else 1
+        D, H, W = (int(v) for v in shape[-3:])
+        return int(self._entry("launch_units")(B, self.cin, self.cout, D, H, W))
+
+    @staticmethod
+    def bound_of(x):
+        """[SLOTS] device floats, slot 0 = max |x| (one sweep of x)."""
+        _need_gpu(x)
+        x = _f32c(x)
+        out = torch.empty((_F16x2Conv3d.SLOTS,), dtype=torch.float32, device=x.device)
+        check(lib().m3d_conv3d_zw_bound_of(_ptr(x), C.c_longlong(x.numel()), _ptr(out), _stream()), "conv3d_zw_bound_of")
+        return out
+
+    def _operands(self, x, in_max, out, out_max, pool=False):
+        """-> (x, out, out_max) of a launch: x contiguous fp32 [B, cin, D, H, W]; `out` claimed, or fresh; out_max: a ZEROED [SLOTS] float
+        tensor to receive the output's bound (None: a fresh one; False: no bound output - the last layer of a chain - returned as None)"""
+        _need_gpu(x, in_max)
+        x = _f32c(x)
+        B, cin, D, H, W = x.shape
+        assert cin == self.cin and in_max.numel() == self.SLOTS and in_max.dtype == torch.float32
+        oshape = (B, self.cout, D // 2, H // 2, W // 2) if pool else (B, self.cout, D, H, W)
+        _claim(out)
+        if out is None:
+            out = torch.empty(oshape, dtype=torch.float32, device=x.device)
+        assert tuple(out.shape) == oshape and out.is_contiguous()
+        if out_max is None:
+            out_max = torch.zeros((self.SLOTS,), dtype=torch.float32, device=x.device)
+        elif out_max is False:
+            out_max = None
+        return x, out, out_max
+
+
+class ZwConv3d(_F16x2Conv3d):
+    """3x3x3 forward conv (stride 1, pad 1) + scale/shift + ReLU [+ MaxPool3d(2,2)] on the f16 matrix cores at fp32 accuracy
+    (csrc/conv3d_zw.hip: f16x2 split, Winograd F(2,3) along z); operand bounds as _F16x2Conv3d says.  __call__ -> (out, out_max)."""
+    FAMILY = "zw"
+
+    @staticmethod
+    def _check_dgrad_weight(ok, weight):
+        assert ok
 
     def strip(self, gn, pitch, P, out=None, bounds=None):
         """PRM window strip gn [cin, planes, U, L] (windows side by side along x, cell p = columns [pitch p, pitch (p + 1)): strip_geometry
@@ -1617,37 +1673,11 @@ class ZwConv3d(object):
         check(rc, "prm_strip_dgrad_prepare_zw")
         return out, oo
 
-    def units(self, shape):
-        """workgroups of a launch on an input [B, cin, D, H, W] (or (D, H, W): one item): the library's own count, (64 channels) x (its tile)"""
-        B = int(shape[0]) if len(shape) == 5 else 1
-        D, H, W = (int(v) for v in shape[-3:])
-        return int(lib().m3d_conv3d_zw_launch_units(B, self.cin, self.cout, D, H, W))
-
-    @staticmethod
-    def bound_of(x):
-        """[SLOTS] device floats, slot 0 = max |x| (one sweep of x)."""
-        _need_gpu(x)
-        x = _f32c(x)
-        out = torch.empty((ZwConv3d.SLOTS,), dtype=torch.float32, device=x.device)
-        check(lib().m3d_conv3d_zw_bound_of(_ptr(x), C.c_longlong(x.numel()), _ptr(out), _stream()), "conv3d_zw_bound_of")
-        return out
-
     def __call__(self, x, in_max, scale=None, shift=None, relu=False, pool=False, out=None, out_max=None):
         """out_max: a ZEROED [SLOTS] float tensor to receive the output's bound (None: a fresh one; False: no bound output)."""
-        _need_gpu(x, in_max)
-        x = _f32c(x)
-        B, cin, D, H, W = x.shape
-        assert cin == self.cin and in_max.numel() == self.SLOTS and in_max.dtype == torch.float32
+        x, out, out_max = self._operands(x, in_max, out, out_max, pool=pool)
         assert x[0].numel() * 4 < 0x7FFFFFFF                  # one batch item is addressed with 32-bit buffer offsets
-        oshape = (B, self.cout, D // 2, H // 2, W // 2) if pool else (B, self.cout, D, H, W)
-        _claim(out)
-        if out is None:
-            out = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        assert tuple(out.shape) == oshape and out.is_contiguous()
-        if out_max is None:
-            out_max = torch.zeros((self.SLOTS,), dtype=torch.float32, device=x.device)
-        elif out_max is False:                             # nobody needs the output's bound (the last layer of a chain)
-            out_max = None
+        B, cin, D, H, W = x.shape
         check(lib().m3d_conv3d_zw_forward(_ptr(x), _ptr(self.packed), _ptr(out), B, cin, self.cout, D, H, W,
                                           _ptr(scale) if scale is not None else None, _ptr(shift) if shift is not None else None,
                                           int(bool(relu)), int(bool(pool)), _ptr(in_max), _ptr(out_max) if out_max is not None else None,
@@ -1655,74 +1685,21 @@ class ZwConv3d(object):
         return out, out_max
 
 
-class ZnConv3d(object):
+class ZnConv3d(_F16x2Conv3d):
     """3x3x3 conv (stride 1, pad 1) + scale/shift + ReLU on maps at most 8 wide - the per-RoI convs on 7^3 RoI grids - on the f16 matrix
     cores at fp32 accuracy (csrc/conv3d_zn.hip: f16x2 split, direct 27 taps, one workgroup per 64 channels x 8 x 8 x 4 voxels, no atomics
-    on the output).  Operand bounds travel as ZwConv3d's: `in_max` is [SLOTS] device floats whose largest is the bound
-    (ZwConv3d.bound_of(x) sweeps a tensor), every call returns the same kind of array for its output.  __call__ -> (out, out_max)."""
-    SLOTS = ZwConv3d.SLOTS
-    bound_of = staticmethod(ZwConv3d.bound_of)
+    on the output); operand bounds as _F16x2Conv3d says (bound_of is ZwConv3d's sweep).  No fused pool.  __call__ -> (out, out_max)."""
+    FAMILY = "zn"
 
     @staticmethod
-    def supported(weight, shape=None):
-        """weight [cout, cin, 3, 3, 3] with cin % 16 == 0; shape = (D, H, W) of the input (None: any supported map)."""
-        if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or int(weight.shape[1]) % 16 != 0:
-            return False
-        if shape is None:
-            return True
-        D, H, W = (int(v) for v in shape)
-        return bool(lib().m3d_conv3d_zn_supported(int(weight.shape[1]), int(weight.shape[0]), D, H, W))
-
-    def __init__(self, weight):
-        _need_gpu(weight)
-        w = _f32c(weight)
-        assert ZnConv3d.supported(w)
-        self.cout, self.cin = int(w.shape[0]), int(w.shape[1])
-        nbytes = lib().m3d_conv3d_zn_packed_bytes(self.cin, self.cout)
-        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-        check(lib().m3d_conv3d_zn_pack(_ptr(w), self.cin, self.cout, _ptr(self.packed), _stream()), "conv3d_zn_pack")
-
-    @classmethod
-    def dgrad_of(cls, weight):
-        """The BACKWARD-DATA conv of a forward layer `weight` [cout, cin, 3, 3, 3] (cout % 16 == 0) as a ZnConv3d: cin = the layer's cout,
-        cout = the layer's cin.  The pack comes straight from the parameter's own layout (m3d_conv3d_zn_pack_dgrad): the bytes of
-        ZnConv3d(weight.flip(2, 3, 4).transpose(0, 1).contiguous()).packed without that copy."""
-        if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or int(weight.shape[0]) % 16 != 0:
+    def _check_dgrad_weight(ok, weight):
+        if not ok:
             raise ValueError("ZnConv3d.dgrad_of: weight [cout, cin, 3, 3, 3] with cout %% 16 == 0, got %s" % (tuple(weight.shape),))
-        _need_gpu(weight)
-        w = _f32c(weight)
-        self = cls.__new__(cls)
-        self.cout, self.cin = int(w.shape[1]), int(w.shape[0])
-        nbytes = lib().m3d_conv3d_zn_packed_bytes(self.cin, self.cout)
-        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-        check(lib().m3d_conv3d_zn_pack_dgrad(_ptr(w), self.cout, self.cin, _ptr(self.packed), _stream()), "conv3d_zn_pack_dgrad")
-        return self
-
-    def supports(self, shape):
-        D, H, W = (int(v) for v in shape[-3:])
-        return bool(lib().m3d_conv3d_zn_supported(self.cin, self.cout, D, H, W))
-
-    def units(self, shape):
-        """workgroups of a launch on an input [B, cin, D, H, W] (or (D, H, W): one item): the library's own count"""
-        B = int(shape[0]) if len(shape) == 5 else 1
-        D, H, W = (int(v) for v in shape[-3:])
-        return int(lib().m3d_conv3d_zn_launch_units(B, self.cin, self.cout, D, H, W))
 
     def __call__(self, x, in_max, scale=None, shift=None, relu=False, out=None, out_max=None):
         """out_max: a ZEROED [SLOTS] float tensor to receive the output's bound (None: a fresh one; False: no bound output)."""
-        _need_gpu(x, in_max)
-        x = _f32c(x)
+        x, out, out_max = self._operands(x, in_max, out, out_max)
         B, cin, D, H, W = x.shape
-        assert cin == self.cin and in_max.numel() == self.SLOTS and in_max.dtype == torch.float32
-        oshape = (B, self.cout, D, H, W)
-        _claim(out)
-        if out is None:
-            out = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        assert tuple(out.shape) == oshape and out.is_contiguous()
-        if out_max is None:
-            out_max = torch.zeros((self.SLOTS,), dtype=torch.float32, device=x.device)
-        elif out_max is False:                             # nobody needs the output's bound (the last layer of a chain)
-            out_max = None
         check(lib().m3d_conv3d_zn_forward(_ptr(x), _ptr(self.packed), _ptr(out), B, cin, self.cout, D, H, W,
                                           _ptr(scale) if scale is not None else None, _ptr(shift) if shift is not None else None,
                                           int(bool(relu)), _ptr(in_max), _ptr(out_max) if out_max is not None else None,

@@ -15,15 +15,15 @@ import gzip
 import itertools
 import json
 import os
-import types
 
 import pytest
 import torch
 
+from conv_record import CudaMeta, install
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "conv_dispatch.json.gz")
 
-PURE = ("_supported", "_score", "_bytes", "_family", "_units", "_plan", "_geometry", "_max_boxes", "_version", "_tuning_build")
 NETS = {"stride8": dict(stride=8, num_anchors=35), "stride4": dict(stride=4, num_anchors=14)}
 BATCHES = (1, 4)
 ENVS = ({}, {"M3D_WINO": "1"}, {"M3D_WINO": "0"}, {"M3D_CONV_F16": "0"})
@@ -50,59 +50,6 @@ DETECTION_ENTRIES = ("m3d_conv3d_forward", "m3d_conv3d_forward_pool2", "m3d_conv
 PRM_ENTRIES = ("m3d_conv3d_forward", "m3d_conv3d_forward_pool2", "m3d_conv3d_wino_forward", "m3d_conv3d_wino2_forward_ws",
                "m3d_conv3d_wino2_forward_pool2_argmax", "m3d_conv3d_zw_forward pool=0", "m3d_maxpool3d_2x_forward",
                "m3d_conv3d_zw_bound_of", "m3d_conv3d_forward_split_sigmoid")
-
-
-class CudaMeta(torch.Tensor):
-    """a meta tensor that says it is on the GPU (PackedConv3d.__call__ asserts it of scale and shift)"""
-    is_cuda = property(lambda self: True)
-
-
-def _arg(v):
-    if v is None:
-        return "null"
-    if isinstance(v, C.c_void_p):
-        return "ptr" if v.value else "null"
-    return int(getattr(v, "value", v))
-
-
-class Recorder:
-    """stands in for the ctypes library object: pure queries reach the real one and are counted, launches are written down"""
-
-    def __init__(self, real):
-        self.real, self.launches, self.queries = real, [], 0
-
-    def __getattr__(self, name):
-        if name.endswith(PURE):
-            fn = getattr(self.real, name)
-
-            def query(*a):
-                self.queries += 1
-                return fn(*a)
-            return query
-
-        def launch(*a):
-            self.launches.append([name] + [_arg(v) for v in a])
-            return 0
-        return launch
-
-    def take(self):
-        out = (self.launches, self.queries)
-        self.launches, self.queries = [], 0
-        return out
-
-
-def install(mp):
-    """the doubles at the ops / library boundary, through the MonkeyPatch `mp`"""
-    import __graft_entry__ as g
-    g.build()
-    from m3d import ops, _lib
-    rec = Recorder(_lib.lib())
-    mp.setattr(ops, "lib", lambda: rec)
-    mp.setattr(ops, "_need_gpu", lambda *ts: None)
-    mp.setattr(ops, "_stream", lambda: C.c_void_p(0))
-    mp.setattr(ops, "_ptr", lambda t: C.c_void_p(0 if t is None else 1))
-    mp.setattr(torch.cuda, "current_stream", lambda *a, **k: types.SimpleNamespace(cuda_stream=0))
-    return rec
 
 
 def params(net):
