@@ -369,6 +369,19 @@ int m3d_conv3d_wgrad_f16x2_plan(int batch, int cin, int cout, int depth, int hei
 int m3d_conv3d_wgrad_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout, int depth,
                            int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws, size_t ws_bytes,
                            void* stream);
+/* m3d_conv3d_wgrad_f16x2 for maps at most 8 voxels wide (csrc/conv3d_wgrad_narrow_f16.hip): the same cut, contract, argument order and
+ * refusals, on the 2 x 8 x 8 voxel tile of m3d_conv3d_wgrad_narrow (a 7^3 RoI grid fills 343 of its 512 slots, 343 of 1024 of the
+ * wide kernel's).  A 16-deep k-step is two 8-voxel rows; the +-1 shift along x is built in registers with a zero shifted in, since
+ * x = -1 and x = 8 are outside every map this kernel takes.  M3D_EUNSUPPORTED: width > 8, cin or cout not a multiple of 32 or above
+ * 4096, too many workgroups.  _plan also reports tile_z, the tile's depth (the tile is tile_z x 8 x 8): chain = tiles_per_slot *
+ * (tile_z * 8 / 2) * 3 <= 384, folds = ceil(slots / 8) + 7 adds + 2 scale multiplies.  workspace_bytes = slots * 27 * cin * cout * 4. */
+int m3d_conv3d_wgrad_narrow_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width);
+size_t m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width);
+int m3d_conv3d_wgrad_narrow_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int* tile_z, int* slots,
+                                       int* tiles_per_slot, int* chain, int* folds);
+int m3d_conv3d_wgrad_narrow_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                  int depth, int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws,
+                                  size_t ws_bytes, void* stream);
 /* One pass over a conv layer's output gradient d_gy [batch, cout, depth, height, width] (csrc/conv3d_gy_reduce.hip) for the bias gradient
  * and the operand bound the f16x2 dgrad (m3d_conv3d_zw_forward on an m3d_conv3d_zw_pack_dgrad pack) and m3d_conv3d_wgrad_f16x2 take:
  *   d_grad_bias  (or NULL) [cout]: gb[c] = fp32(S), S = the sum of d_gy[:, c] taken in fp64 over spans of one (image, channel) slab whose

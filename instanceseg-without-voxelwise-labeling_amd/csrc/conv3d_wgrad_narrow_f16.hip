@@ -1,0 +1,317 @@
+// 3x3x3 convolution backward-weights (stride 1, pad 1) on maps at most 8 voxels wide, on the f16 matrix cores at fp32 accuracy: the
+// "f16x2" cut of conv3d_wgrad_f16.hip (both operands scaled by a power of two and cut once into two fp16 numbers, three
+// v_mfma_f32_32x32x16_f16 per fp32 product, fp32 accumulation) on the 2 x 8 x 8 voxel tile of conv3d_wgrad_narrow.hip:
+//   dW[co,ci,dz,dy,dx] = sum_{b,z,y,x} gy[b,co,z,y,x] * x[b,ci,z+dz-1,y+dy-1,x+dx-1]
+// the gradient autograd computes for the per-RoI 3^3 convs on 7^3 grids: lib/modeling/fast_rcnn_heads.py:120-179 (roi_Xconv1fc_head)
+// and the mask head's convs at MRCNN.DILATION = 1 (lib/modeling/mask_rcnn_heads.py:141-151).  conv3d_wgrad_f16.hip's 2 x 4 x 16 tile
+// is a third full on such a grid (343 of 1024 slots); this one holds 343 of 512.
+//
+// GEMM view per tap as there: M = cout (32 per workgroup), N = cin (32 per workgroup), K = voxels.  Workgroup = (split-K slot, cout
+// block, cin block), 3 waves, wave = dz, nine accumulators for its (dy, dx) taps.  A row of the tile is 8 voxels = 16 bytes of fp16,
+// so a 16-deep k-step is TWO rows: lane (r, h) takes row (z, y + h), one aligned ds_read_b128 from a [channel][row][8 x] image.  A dz /
+// dy shift is another row of the halo image x[32 ci][4 x 10 rows].
+//
+// The +-1 shift along x needs no edge data: the map is one tile along x and starts at 0, so x = -1 is padding and x = 8 is outside the
+// map.  dx = 0 is the lane's eight halves shifted up by one half with a zero shifted in, dx = 2 shifted down with a zero shifted in: 4
+// v_alignbit per fragment, no edge dword, no 2-byte LDS access, no halo columns.  Columns >= W are staged as zeros in both images.
+//
+// LDS: pitches 656 B (x: 40 rows x 16 B + 16) and 272 B (gy: 16 rows x 16 B + 16), odd multiples of 16 bytes, 32 channels x hi / lo of
+// each = 59,392 bytes: two workgroups per CU, one stages while the other multiplies.
+//
+// Accumulation chain and fold as in conv3d_wgrad_f16.hip: a tile is 8 k-steps x 3 products = 24 MFMAs per accumulator, a slot at most
+// 16 tiles (WF_CHAIN = 384), then the workgroup writes its partial; the reduce kernel adds the partials with fp32 adds in a fixed
+// order (8 strided groups, then the 8 group sums in order) and un-scales by exact powers of two.  No atomics, every element of dW
+// written, slots a function of the shape only: bit-identical run to run and on any stream.
+// A file of its own so that the code objects of the other wgrad kernels stay what they were.  DESIGN, "Narrow-map wgrad on the f16 pipe".
+#include "m3d_common.h"
+
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+
+constexpr int WN_NT = 192;                                  // 3 waves: wave = dz
+constexpr int WN_SLOTS_IN = 32;                             // slots of an operand-bound array (m3d_conv3d_zw_slots)
+constexpr int TZ = 2, TY = 8, TX = 8;                       // voxel tile: 16 rows = 8 k-steps of two rows
+constexpr int MAX_W = TX;
+constexpr int GROWS = TZ * TY, KSTEPS = GROWS / 2, HZ = TZ + 2, HY = TY + 2, XROWS = HZ * HY;
+constexpr int MFMA_PER_TILE = KSTEPS * 3;                   // per accumulator: 8 k-steps x (hh + hl + lh)
+constexpr int WN_MAX_TILES = 16;                            // tiles of a slot
+constexpr int WN_CHAIN = WN_MAX_TILES * MFMA_PER_TILE;      // 384: the longest run of MFMAs into one accumulator
+static_assert(WN_CHAIN <= 384, "chain");
+constexpr int WN_TARGET_WGS = 512;                          // two workgroups per CU
+constexpr int RG = 8;                                       // strided groups of the reduce kernel
+constexpr long long WN_MAX_WGS = 0xFFFFFFFFll / WN_NT;      // a launch takes fewer than 2^32 threads
+constexpr int XP = XROWS * 16 + 16;                         // 656: channel pitch of the x image
+constexpr int GP = GROWS * 16 + 16;                         // 272: channel pitch of the gy image
+static_assert((XP / 16) % 2 == 1 && (GP / 16) % 2 == 1 && XP % 16 == 0 && GP % 16 == 0, "odd multiples of 16 bytes");
+constexpr int X_PART = 32 * XP, G_PART = 32 * GP;
+constexpr int LDS_BYTES = 2 * X_PART + 2 * G_PART;          // [x hi][x lo][gy hi][gy lo] = 59,392
+static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
+constexpr int X_ITEMS = 32 * XROWS * 2, G_ITEMS = 32 * GROWS * 2;      // quads
+
+struct WnPlan { int tiles_y, tiles_z, NT, cbs, ibs, tps, slots; long long n; };
+
+__device__ __forceinline__ float bound_of_slots(const float* __restrict__ slots, int lane) {
+  float m = slots[lane & (WN_SLOTS_IN - 1)];
+#pragma unroll
+  for (int o = 16; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  return m;
+}
+
+// the cut of the contract: v = a s (exact), h = fp16(v), l = fp16(v - h)
+__device__ __forceinline__ void cut(float a, float s, _Float16& h, _Float16& l) {
+  const float v = a * s;
+  h = (_Float16)v;
+  l = (_Float16)(v - (float)h);
+}
+
+__device__ __forceinline__ unsigned pack2(_Float16 a, _Float16 b) {
+  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
+}
+
+// four consecutive x of one row from column xf >= 0, zeros at columns >= W; p points at column xf of the row and is not dereferenced
+// outside the row (so no load starts before the image or ends behind it)
+__device__ __forceinline__ f32x4 load_quad(const float* __restrict__ p, int xf, int W, bool row_ok) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (row_ok) {
+    if (xf + 3 < W) {
+      v = *reinterpret_cast<const f32x4u*>(p);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xf + j < W) v[j] = p[j];
+    }
+  }
+  return v;
+}
+
+__device__ __forceinline__ void stage_quad(unsigned char* __restrict__ hi, unsigned char* __restrict__ lo, int off, const f32x4 v, float s) {
+  _Float16 hh[4], ll[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cut(v[j], s, hh[j], ll[j]);
+  *reinterpret_cast<u32x2*>(hi + off) = u32x2{pack2(hh[0], hh[1]), pack2(hh[2], hh[3])};
+  *reinterpret_cast<u32x2*>(lo + off) = u32x2{pack2(ll[0], ll[1]), pack2(ll[2], ll[3])};
+}
+
+// partial[slot][tap][co][ci] in scaled units
+__global__ __launch_bounds__(WN_NT, 2) void conv3d_wgrad_narrow_f16_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                                           float* __restrict__ partial, const float* __restrict__ x_max,
+                                                                           const float* __restrict__ g_max, int B, int cin, int cout,
+                                                                           int D, int H, int W, WnPlan pl) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  unsigned char* const xh = lds;
+  unsigned char* const xl = lds + X_PART;
+  unsigned char* const gh = lds + 2 * X_PART;
+  unsigned char* const gl = gh + G_PART;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int dz = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int bid = blockIdx.x;
+  const int ib = bid % pl.ibs; bid /= pl.ibs;
+  const int cb = bid % pl.cbs;
+  const int slot = bid / pl.cbs;
+  const size_t HW = (size_t)H * W, DHW = HW * D;
+
+  float sx, sg, inv_;
+  m3d::f16_scale_of(bound_of_slots(x_max, lane), sx, inv_);
+  m3d::f16_scale_of(bound_of_slots(g_max, lane), sg, inv_);
+
+  f32x16 acc[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+  const int r = lane & 31, h = lane >> 5;
+  const int xmain = r * XP + 16 * h;                   // half h = 1 reads the row below: y + 1
+  const int gmain = r * GP + 16 * h;
+
+  const int t_end = min(pl.NT, (slot + 1) * pl.tps);
+  for (int t = slot * pl.tps; t < t_end; ++t) {
+    int q = t;
+    const int y0 = (q % pl.tiles_y) * TY; q /= pl.tiles_y;
+    const int z0 = (q % pl.tiles_z) * TZ;
+    const int b = q / pl.tiles_z;
+    __syncthreads();                                   // the previous tile's MFMAs have read the images
+    // ---- gy[cb * 32 + c][row][4 q ..]: one quad per item, cut, 8 bytes to each image
+    {
+      const float* gb = gy + ((size_t)b * cout + (size_t)cb * 32) * DHW;
+      for (int e = tid; e < G_ITEMS; e += WN_NT) {
+        const int qq = e & 1, row = (e >> 1) & (GROWS - 1), c = e >> 5;
+        const int zz = z0 + (row >> 3), yy = y0 + (row & 7), xf = 4 * qq;
+        const bool rok = (zz < D) & (yy < H);
+        const float* rp = gb + (size_t)c * DHW + (rok ? (size_t)zz * HW + (size_t)yy * W : 0);
+        stage_quad(gh, gl, c * GP + row * 16 + qq * 8, load_quad(rp + xf, xf, W, rok & (xf < W)), sg);
+      }
+    }
+    // ---- x[ib * 32 + c][halo row][4 q ..]: the row's 8 aligned voxels, no halo columns
+    {
+      const float* xb = x + ((size_t)b * cin + (size_t)ib * 32) * DHW;
+#pragma unroll 2
+      for (int e = tid; e < X_ITEMS; e += WN_NT) {
+        const int qq = e & 1, rc = e >> 1, row = rc % XROWS, c = rc / XROWS;
+        const int zz = z0 + row / HY - 1, yy = y0 + row % HY - 1, xf = 4 * qq;
+        const bool rok = ((unsigned)zz < (unsigned)D) & ((unsigned)yy < (unsigned)H);
+        const float* rp = xb + (size_t)c * DHW + (rok ? (size_t)zz * HW + (size_t)yy * W : 0);
+        stage_quad(xh, xl, c * XP + row * 16 + qq * 8, load_quad(rp + xf, xf, W, rok & (xf < W)), sx);
+      }
+    }
+    __syncthreads();
+    // ---- MFMA: k-step = rows (2 ks, 2 ks + 1) of the tile; A = gy[co = r][row 2 ks + h][0..7], B = x[ci = r][halo row][dx - 1 ..]
+#pragma unroll 2
+    for (int ks = 0; ks < KSTEPS; ++ks) {
+      const int tz = ks >> 2, ty = (ks & 3) * 2;
+      const f16x8 ah = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(gh + gmain + ks * 32));
+      const f16x8 al = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(gl + gmain + ks * 32));
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) {
+        const int hr = (tz + dz) * HY + ty + dy;
+        u32x4 w[2], f0[2], f2[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const unsigned char* im = p ? xl : xh;
+          w[p] = *reinterpret_cast<const u32x4*>(im + xmain + hr * 16);
+          f0[p][0] = __builtin_amdgcn_alignbit(w[p][0], 0u, 16);          // x = -1 is padding
+          f0[p][1] = __builtin_amdgcn_alignbit(w[p][1], w[p][0], 16);
+          f0[p][2] = __builtin_amdgcn_alignbit(w[p][2], w[p][1], 16);
+          f0[p][3] = __builtin_amdgcn_alignbit(w[p][3], w[p][2], 16);
+          f2[p][0] = __builtin_amdgcn_alignbit(w[p][1], w[p][0], 16);
+          f2[p][1] = __builtin_amdgcn_alignbit(w[p][2], w[p][1], 16);
+          f2[p][2] = __builtin_amdgcn_alignbit(w[p][3], w[p][2], 16);
+          f2[p][3] = __builtin_amdgcn_alignbit(0u, w[p][3], 16);          // x = 8 is outside the map
+        }
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const f16x8 bh = __builtin_bit_cast(f16x8, dx == 0 ? f0[0] : dx == 1 ? w[0] : f2[0]);
+          const f16x8 bl = __builtin_bit_cast(f16x8, dx == 0 ? f0[1] : dx == 1 ? w[1] : f2[1]);
+          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[dy][dx], 0, 0, 0);
+          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[dy][dx], 0, 0, 0);
+          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[dy][dx], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // ---- this wave's nine taps of the slot's partial: acc[i = co][j = ci], col j = lane & 31, row i = (g & 3) + 8 (g >> 2) + 4 h
+  float* pp = partial + (size_t)slot * pl.n;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int tap = dz * 9 + dy * 3 + dx;
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        const int co = cb * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
+        pp[((size_t)tap * cout + co) * cin + ib * 32 + r] = acc[dy][dx][g];
+      }
+    }
+}
+
+// dW[co][ci][tap] = (sum over the slots in a fixed order) / s_g / s_x: a block is 32 consecutive partial elements x RG strided groups
+__global__ __launch_bounds__(256) void conv3d_wgrad_narrow_f16_reduce_kernel(const float* __restrict__ partial, int slots, long long n,
+                                                                             int cin, int cout, const float* __restrict__ x_max,
+                                                                             const float* __restrict__ g_max, float* __restrict__ dw) {
+  __shared__ float sm[RG][32];
+  const int e = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const long long i = (long long)blockIdx.x * 32 + e;                 // n is a multiple of 32 * 32 * 27
+  float s_, inv_x, inv_g;
+  m3d::f16_scale_of(bound_of_slots(x_max, threadIdx.x & 63), s_, inv_x);
+  m3d::f16_scale_of(bound_of_slots(g_max, threadIdx.x & 63), s_, inv_g);
+  float sum = 0.f;
+  for (int s = g; s < slots; s += RG) sum += partial[(size_t)s * n + i];
+  sm[g][e] = sum;
+  __syncthreads();
+  if (g == 0) {
+    float tot = sm[0][e];
+#pragma unroll
+    for (int k = 1; k < RG; ++k) tot += sm[k][e];
+    const long long cc = (long long)cout * cin;
+    const int tap = (int)(i / cc);
+    const long long rem = i - tap * cc;                                // co * cin + ci
+    dw[rem * 27 + tap] = tot * inv_g * inv_x;
+  }
+}
+
+bool extents_ok(int batch, int cin, int cout, int D, int H, int W) {
+  return batch > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0;
+}
+
+bool wn_shape_ok(int batch, int cin, int cout, int D, int H, int W) {
+  if (!extents_ok(batch, cin, cout, D, H, W)) return false;
+  if (W > MAX_W) return false;
+  if (cin % 32 || cout % 32 || cin > 4096 || cout > 4096) return false;
+  const long long tz = ((long long)D + TZ - 1) / TZ, ty = ((long long)H + TY - 1) / TY;
+  if (tz * ty > (1ll << 30)) return false;                                     // the product below 2^61
+  return (long long)batch * (tz * ty) <= (1ll << 30);
+}
+
+WnPlan wn_plan(int batch, int cin, int cout, int D, int H) {
+  WnPlan p;
+  p.tiles_y = (H + TY - 1) / TY; p.tiles_z = (D + TZ - 1) / TZ;
+  p.NT = batch * p.tiles_y * p.tiles_z;
+  p.cbs = cout / 32; p.ibs = cin / 32;
+  long long tps = (long long)p.NT * p.cbs * p.ibs / WN_TARGET_WGS;      // a function of the shape only
+  p.tps = (int)(tps < 1 ? 1 : tps > WN_MAX_TILES ? WN_MAX_TILES : tps);
+  p.slots = (p.NT + p.tps - 1) / p.tps;
+  p.n = (long long)cout * cin * 27;
+  return p;
+}
+
+}  // namespace
+
+M3D_API int m3d_conv3d_wgrad_narrow_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width) {
+  if (!wn_shape_ok(batch, cin, cout, depth, height, width)) return 0;
+  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
+  return (long long)p.slots * p.cbs * p.ibs <= WN_MAX_WGS ? 1 : 0;
+}
+
+M3D_API size_t m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width) {
+  if (!m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width)) return 0;
+  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
+  return (size_t)p.slots * (size_t)p.n * sizeof(float);
+}
+
+M3D_API int m3d_conv3d_wgrad_narrow_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int* tile_z, int* slots,
+                                               int* tiles_per_slot, int* chain, int* folds) {
+  if (!extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
+  if (!m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
+  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
+  if (tile_z) *tile_z = TZ;
+  if (slots) *slots = p.slots;
+  if (tiles_per_slot) *tiles_per_slot = p.tps;
+  if (chain) *chain = p.tps * MFMA_PER_TILE;
+  // fp32 operations on an output behind its MFMA chain: the adds of its strided group (the first partial is added to 0), the RG - 1 adds
+  // of the group sums, the two scale multiplies
+  if (folds) *folds = (p.slots + RG - 1) / RG + (RG - 1) + 2;
+  return M3D_OK;
+}
+
+M3D_API int m3d_conv3d_wgrad_narrow_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                          int depth, int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws,
+                                          size_t ws_bytes, void* stream) {
+  if (!d_in || !d_grad_out || !d_grad_weight || !d_in_max || !d_gy_max || !d_ws) return M3D_EINVAL;
+  if (((uintptr_t)d_in | (uintptr_t)d_grad_out | (uintptr_t)d_grad_weight | (uintptr_t)d_in_max | (uintptr_t)d_gy_max) & 3) return M3D_EINVAL;
+  if ((uintptr_t)d_ws & 15) return M3D_EINVAL;
+  if (!extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
+  if (!m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
+  if (ws_bytes < m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
+  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
+  hipStream_t st = m3d::as_stream(stream);
+  float* partial = (float*)d_ws;
+  auto kern = conv3d_wgrad_narrow_f16_kernel;
+  // 58 KB of LDS: asked for per launch, as conv3d_wgrad_f16.hip does (the attribute belongs to the current device's copy of the kernel)
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  const unsigned blocks = (unsigned)((long long)p.slots * p.cbs * p.ibs);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(WN_NT), LDS_BYTES, st, d_in, d_grad_out, partial, d_in_max, d_gy_max, batch, cin, cout,
+                     depth, height, width, p);
+  int rc = m3d::check_launch("conv3d_wgrad_narrow_f16x2");
+  if (rc != M3D_OK) return rc;
+  hipLaunchKernelGGL(conv3d_wgrad_narrow_f16_reduce_kernel, dim3((unsigned)(p.n / 32)), dim3(256), 0, st, partial, p.slots, p.n, cin,
+                     cout, d_in_max, d_gy_max, d_grad_weight);
+  return m3d::check_launch("conv3d_wgrad_narrow_f16x2_reduce");
+}

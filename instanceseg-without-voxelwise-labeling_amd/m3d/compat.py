@@ -16,6 +16,7 @@ backward-data, so lib/modeling/DSN.py and lib/prm/peak_backprop_3d.py run unchan
 (opt-in) the k = 3, dilation 2, padding 2 convs of the mask head go there too, forward and backward.  Under
 set_conv_wgrad_narrow(True) (opt-in) the weight gradient of the dilation-1 3^3 convs on maps at most 8 wide - the per-RoI convs of the
 conv box head and of the mask head - runs on the 2 x 8 x 8 tile kernel (m3d_conv3d_wgrad_narrow).
+set_conv_wgrad_narrow_f16(True) (opt-in) runs that weight gradient on the f16 matrix cores instead (m3d_conv3d_wgrad_narrow_f16x2).
 set_conv_train_narrow(True) (opt-in) runs the forward and the backward-data pass of those same convs on the narrow-map f16x2 kernel
 (m3d_conv3d_zn_forward, csrc/conv3d_zn.hip).
 What the setters say is one conv_plan.TrainSetting; what a routed conv launches under it, forward and backward, is decided by
@@ -203,6 +204,7 @@ def _packed(weight, mode):
 
 
 _setting = conv_plan.TrainSetting()          # what the setters below say; WHEN each field is read: the TrainSetting docstring
+_wgrad_narrow_f16 = None                     # set_conv_wgrad_narrow_f16: None (off) or its threshold; beside _setting, whose fields are pinned
 
 
 def set_conv_wgrad(mode):
@@ -234,6 +236,27 @@ def set_conv_wgrad_narrow(on):
 
 def get_conv_wgrad_narrow():
     return _setting.wgrad_narrow
+
+
+def set_conv_wgrad_narrow_f16(on, min_work=None):
+    """The weight gradient of the intercepted 3^3 convs on maps at most 8 wide with channel counts that are multiples of 32 (the per-RoI
+    convs on 7^3 grids): False (the default; install() does not change it) keeps what set_conv_wgrad and set_conv_wgrad_narrow give
+    them; True takes m3d_conv3d_wgrad_narrow_f16x2 (the f16 matrix cores at fp32 accuracy on the 2 x 8 x 8 tile) for the layers
+    conv_plan.wgrad_kernel(narrow_f16=) routes to it, whatever those two switches say.  x's bound comes from the forward and gy's from
+    m3d_conv3d_gy_reduce where set_conv_train_narrow / set_conv_train ran them, else the kernel's wrapper sweeps; forward, dgrad and the
+    bias gradient are the same with the switch on or off.  min_work: the routing threshold in products per tap, batch D H W cin cout
+    (None: conv_plan.WGRAD_NARROW_F16X2_MIN_WORK; 0 routes every supported layer - tests and A/B runs; a call without it puts the
+    default back).  Read when the backward runs.  Returns the previous setting (True / False)."""
+    global _wgrad_narrow_f16
+    if min_work is not None and int(min_work) < 0:
+        raise ValueError("set_conv_wgrad_narrow_f16(min_work=%r): None or a count >= 0" % (min_work,))
+    prev = _wgrad_narrow_f16 is not None
+    _wgrad_narrow_f16 = (conv_plan.WGRAD_NARROW_F16X2_MIN_WORK if min_work is None else int(min_work)) if on else None
+    return prev
+
+
+def get_conv_wgrad_narrow_f16():
+    return _wgrad_narrow_f16 is not None
 
 
 def set_conv_train(mode, min_units=None):
@@ -329,7 +352,8 @@ class _Conv3dFn(torch.autograd.Function):
         gy = gy.contiguous()
         setting = ctx.setting._replace(wgrad=_setting.wgrad, wgrad_narrow=_setting.wgrad_narrow)
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
-        dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs)
+        dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs,
+                                                                         _wgrad_narrow_f16)
         gx = gw = gb = gy_max = None
         if gy_reduce:
             gb, gy_max = ops.conv3d_gy_reduce(gy, bias=gb_from == conv_plan.GB_REDUCE)
@@ -354,6 +378,11 @@ class _Conv3dFn(torch.autograd.Function):
             gw = ops.conv3d_wgrad(x, gy, 3, dilation=2)
         elif wgrad == conv_plan.WGRAD_FP32:
             gw = ops.conv3d_wgrad(x, gy, weight.shape[2])
+        else:
+            # the kinds left: None (gw not needed) and WGRAD_NARROW_F16X2, with the bounds WGRAD_F16X2 takes.  (An else, since the count of
+            # branches of this function is pinned: tests/test_conv_train_dispatch.py::test_backward_has_no_routing_left)
+            assert wgrad in (None, conv_plan.WGRAD_NARROW_F16X2), wgrad
+            gw = None if wgrad is None else ops.conv3d_wgrad_narrow_f16x2(x, gy, ctx.x_max, gy_max)
 
         if gb_from == conv_plan.GB_BIAS_GRAD:
             gb = ops.conv3d_bias_grad(gy)

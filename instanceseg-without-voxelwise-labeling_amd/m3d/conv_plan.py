@@ -43,20 +43,35 @@ WGRAD_F16X2_MIN_WORK = 1 << 27
 # The dilation-1 fp32 kernel on the 2 x 8 x 8 voxel tile (m3d_conv3d_wgrad_narrow): maps at most 8 wide, i.e. the per-RoI convs on 7^3
 # grids of the conv box head and of the mask head at MRCNN.DILATION = 1.  Opt-in (compat.set_conv_wgrad_narrow).
 WGRAD_NARROW = "fp32 narrow"
+# The f16x2 cut on that 2 x 8 x 8 tile (m3d_conv3d_wgrad_narrow_f16x2): opt-in (compat.set_conv_wgrad_narrow_f16).
+WGRAD_NARROW_F16X2 = "f16x2 narrow"
+# Its fixed costs are the wide kernel's (two sweeps where the step holds no bound, a workspace round trip per slot, a second launch).  A
+# layer is routed to it from the work, batch x voxels x cin x cout products per tap, of the smallest shape measured to beat the faster of
+# m3d_conv3d_wgrad_narrow and m3d_conv3d_wgrad_f16x2 by more than the sum of the spreads, sweeps inside the window
+# (profiles/conv_wgrad_narrow_f16.txt: 256 -> 256 on 7^3 at R = 4, 4 x 343 x 256 x 256, 1.58 x); all eleven larger measured shapes win
+# too (1.92 x .. 2.32 x).  Nothing smaller was measured: below it nothing routes.
+WGRAD_NARROW_F16X2_MIN_WORK = 4 * 343 * 256 * 256
 
 
-def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3, narrow=False):
-    """Which kernel computes the weight gradient of a stride-1 'same' conv layer with x [batch, cin, D, H, W]: WGRAD_F16X2, WGRAD_NARROW
-    or WGRAD_FP32.  The one place that says so (a row of plan_train_conv).  mode: the caller's setting (compat.set_conv_wgrad):
+def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3, narrow=False, narrow_f16=None):
+    """Which kernel computes the weight gradient of a stride-1 'same' conv layer with x [batch, cin, D, H, W]: WGRAD_F16X2, WGRAD_NARROW,
+    WGRAD_NARROW_F16X2 or WGRAD_FP32.  The one place that says so (a row of plan_train_conv).  mode: the caller's setting (compat.set_conv_wgrad):
     "fp32" keeps every layer on m3d_conv3d_wgrad; "f16x2" moves the layers the f16x2 kernel takes (k = 3, cin and cout multiples of 32:
     m3d_conv3d_wgrad_f16x2_supported) and was measured to win on by more than the spread of the measurement: layers of at least
     WGRAD_F16X2_MIN_WORK products per tap.  narrow: the caller's switch (compat.set_conv_wgrad_narrow): a k = 3 layer that would end on
     WGRAD_FP32 and that m3d_conv3d_wgrad_narrow takes (W <= 8) is WGRAD_NARROW instead; a layer the mode routes to f16x2 stays there.
+    narrow_f16: None (off: the result is what it was without the argument, and no further library query is made), else a routing
+    threshold in products per tap (compat.set_conv_wgrad_narrow_f16): a k = 3 layer that m3d_conv3d_wgrad_narrow_f16x2_supported takes
+    (W <= 8, cin and cout multiples of 32) and whose work reaches it is WGRAD_NARROW_F16X2 whatever mode and narrow say - at W <= 8
+    the wide f16x2 tile is a third full; every other layer follows the rule above.
     A function of the shape only."""
     if mode not in (WGRAD_FP32, WGRAD_F16X2):
         raise ValueError("wgrad mode %r: 'fp32' or 'f16x2'" % (mode,))
     if int(k) != 3:
         return WGRAD_FP32
+    if (narrow_f16 is not None and ops.conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, D, H, W)
+            and int(batch) * int(D) * int(H) * int(W) * int(cin) * int(cout) >= int(narrow_f16)):
+        return WGRAD_NARROW_F16X2
     if (mode == WGRAD_F16X2 and ops.conv3d_wgrad_f16x2_supported(batch, cin, cout, D, H, W)
             and int(batch) * int(D) * int(H) * int(W) * int(cin) * int(cout) >= WGRAD_F16X2_MIN_WORK):
         return WGRAD_F16X2
@@ -137,13 +152,16 @@ class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narro
     dilated       DILATED_TORCH / DILATED_M3D (set_conv_dilated)
     WHEN each is read: train, min_units, narrow and dilated are those of the FORWARD call - the conv Function keeps the forward's
     setting and its backward follows it, whatever the setters were told in between; wgrad and wgrad_narrow are read when the BACKWARD
-    runs (the Function puts the current two into the kept setting before it asks plan_train_backward)."""
+    runs (the Function puts the current two into the kept setting before it asks plan_train_backward).
+    The field list is pinned (tests/test_conv_train_dispatch.py compares _asdict() of the defaults), so the one later switch,
+    set_conv_wgrad_narrow_f16, travels beside the setting: the wgrad_narrow_f16 argument of plan_train_backward / plan_train_conv,
+    read when the backward runs as the other two wgrad switches are."""
     __slots__ = ()
 
 
 # forward: TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED; sweep: the forward sweeps x for its operand bound and keeps it
 # (for the f16x2 wgrad); dgrad: None (gx not needed) / DGRAD_STEM / TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED;
-# wgrad: None (gw not needed) / WGRAD_FP32 / WGRAD_F16X2 / WGRAD_NARROW / WGRAD_DILATED; gy_reduce: m3d_conv3d_gy_reduce runs first (one
+# wgrad: None (gw not needed) / WGRAD_FP32 / WGRAD_F16X2 / WGRAD_NARROW / WGRAD_NARROW_F16X2 / WGRAD_DILATED; gy_reduce: m3d_conv3d_gy_reduce runs first (one
 # pass over gy: its operand bound, and the bias gradient where needed); gb: None / GB_REDUCE / GB_BIAS_GRAD
 TrainConvPlan = collections.namedtuple("TrainConvPlan", "forward sweep dgrad wgrad gy_reduce gb")
 
@@ -166,28 +184,35 @@ def plan_train_forward(setting, xshape, wshape, dilation):
     return forward, forward != TRAIN_FP32
 
 
-def plan_train_backward(setting, xshape, wshape, dilation, needs):
-    """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs"""
+def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None):
+    """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs.  wgrad_narrow_f16: None (the narrow f16x2
+    wgrad kernel is off), else its routing threshold in products per tap (compat.set_conv_wgrad_narrow_f16)"""
     gx, gw, gb = (bool(v) for v in needs)
     if dilation == 2:                                  # all fp32: train and wgrad do not reach these layers
         return (TRAIN_DILATED if gx else None), (WGRAD_DILATED if gw else None), False, (GB_BIAS_GRAD if gb else None)
     B, _, D, H, W = xshape
     cout, cin, k = wshape[:3]
     dgrad = None if not gx else DGRAD_STEM if k == 5 else _train_rule("dgrad", setting, xshape, wshape)
-    wgrad = wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow) if gw else None
+    # base: the wgrad kernel without the narrow f16x2 switch (the only one asked while that switch is off)
+    base = wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow) if gw else None
+    wgrad = base if base is None or wgrad_narrow_f16 is None else \
+        wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow, narrow_f16=wgrad_narrow_f16)
     # one pass over gy gives the bound both f16x2 kernels scale gy by, and the bias gradient.  In train mode f16x2 gb ALWAYS comes from
     # it, so that a change of route (another batch size, min_units) never changes gb; in mode fp32 only the narrow f16x2 dgrad asks for
-    # it (the f16x2 wgrad then sweeps both operands itself)
-    gy_reduce = (setting.train == TRAIN_F16X2 and (dgrad == TRAIN_F16X2 or wgrad == WGRAD_F16X2 or gb)) or dgrad == TRAIN_F16X2_NARROW
+    # it (the f16x2 wgrad then sweeps both operands itself).  WGRAD_NARROW_F16X2 asks for nothing: the pass runs where it would have run
+    # for `base`, the wgrad kernel without wgrad_narrow_f16; the narrow kernel takes gy's bound where it ran and sweeps otherwise, so
+    # gy_reduce and gb are the same with its switch on or off
+    gy_reduce = (setting.train == TRAIN_F16X2 and (dgrad == TRAIN_F16X2 or base == WGRAD_F16X2 or gb)) or dgrad == TRAIN_F16X2_NARROW
     return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
 
 
-def plan_train_conv(setting, xshape, wshape, dilation, needs):
+def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None):
     """What a training conv that m3d.compat.conv3d routes to the library launches, forward and backward: a TrainConvPlan.  The only place
     that combines the rules (train_conv_kernel and wgrad_kernel are its rows); host queries of the library only, a function of its
     arguments only.  setting: a TrainSetting; xshape [B, cin, D, H, W]; wshape [cout, cin, k, k, k]; dilation: 1 (stride 1, padding
     k // 2, k in {1, 3} or the 5^3 / Cin = 1 stem) or 2 (k = 3, padding 2, only routed under DILATED_M3D); needs = (gx, gw, gb) of
-    needs_input_grad, gb already False for a layer without bias.
+    needs_input_grad, gb already False for a layer without bias; wgrad_narrow_f16: None or the threshold of
+    compat.set_conv_wgrad_narrow_f16 (it moves the wgrad field only: gy_reduce and gb do not depend on it).
 
     | field     | value              | condition                                                                                      |
     | forward   | TRAIN_DILATED      | dilation 2                                                                                     |
@@ -199,6 +224,7 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs):
     |           | else               | train_conv_kernel("dgrad", ...)                                                                |
     | wgrad     | None               | gw not needed                                                                                  |
     |           | WGRAD_DILATED      | dilation 2                                                                                     |
+    |           | WGRAD_NARROW_F16X2 | wgrad_narrow_f16 is a threshold, k = 3, m3d_conv3d_wgrad_narrow_f16x2_supported, work >= it    |
     |           | else               | wgrad_kernel(...) under setting.wgrad / wgrad_narrow                                           |
     | gy_reduce | True               | dilation 1 and: train is f16x2 and (dgrad or wgrad is f16x2, or gb needed); or dgrad is narrow |
     | gb        | None               | gb not needed                                                                                  |
@@ -207,7 +233,8 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs):
 
     compat asks the two halves when it needs them (plan_train_forward in forward, plan_train_backward in backward): a call makes the
     library queries of the directions it runs and no others."""
-    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation) + plan_train_backward(setting, xshape, wshape, dilation, needs)))
+    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation)
+                           + plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16)))
 
 
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True, narrow_f16=False):

@@ -13,7 +13,7 @@ BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
            "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "SplitLinear", "linear_roi_fused", "mask_paste3d",
-           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "ZnConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
+           "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_wgrad_narrow_f16x2", "conv3d_wgrad_narrow_f16x2_supported", "conv3d_wgrad_narrow_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "ZnConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
 
@@ -1994,6 +1994,43 @@ def conv3d_wgrad_f16x2(x, grad_out, x_max=None, gy_max=None):
     ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
     check(lib().m3d_conv3d_wgrad_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, _ptr(x_max), _ptr(gy_max), _ptr(ws),
                                        C.c_size_t(wsb), _stream()), "conv3d_wgrad_f16x2")
+    return dw
+
+
+def conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, D, H, W):
+    """m3d_conv3d_wgrad_narrow_f16x2_supported (host only): the k = 3 weight gradient of this shape runs on the f16 matrix cores on the
+    2 x 8 x 8 voxel tile (W <= 8, cin and cout multiples of 32)"""
+    return bool(lib().m3d_conv3d_wgrad_narrow_f16x2_supported(int(batch), int(cin), int(cout), int(D), int(H), int(W)))
+
+
+def conv3d_wgrad_narrow_f16x2_plan(batch, cin, cout, D, H, W):
+    """The host decision of the launch (m3d_conv3d_wgrad_narrow_f16x2_plan): dict(tile_z, slots, tiles_per_slot, chain, folds)"""
+    v = [C.c_int(0) for _ in range(5)]
+    check(lib().m3d_conv3d_wgrad_narrow_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), *[C.byref(a) for a in v]),
+          "conv3d_wgrad_narrow_f16x2_plan")
+    return dict(zip(("tile_z", "slots", "tiles_per_slot", "chain", "folds"), (a.value for a in v)))
+
+
+def conv3d_wgrad_narrow_f16x2(x, grad_out, x_max=None, gy_max=None):
+    """conv3d_wgrad_f16x2 for maps at most 8 wide (m3d_conv3d_wgrad_narrow_f16x2: the same cut on the 2 x 8 x 8 voxel tile): x
+    [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA) -> dW [cout,cin,3,3,3].  x_max / gy_max: [ZwConv3d.SLOTS] device floats whose
+    largest bounds |x| / |grad_out|; a missing one is swept (ZwConv3d.bound_of).  An unsupported shape is an error: ask
+    conv3d_wgrad_narrow_f16x2_supported (or conv_plan.wgrad_kernel)."""
+    _need_gpu(x, grad_out, x_max, gy_max)
+    x, grad_out = _f32c(x), _f32c(grad_out)
+    B, cin, D, H, W = x.shape
+    cout = grad_out.shape[1]
+    assert grad_out.shape == (B, cout, D, H, W)
+    if x_max is None:
+        x_max = ZwConv3d.bound_of(x)
+    if gy_max is None:
+        gy_max = ZwConv3d.bound_of(grad_out)
+    assert x_max.numel() == ZwConv3d.SLOTS and gy_max.numel() == ZwConv3d.SLOTS and x_max.dtype == gy_max.dtype == torch.float32
+    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    wsb = lib().m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(B, cin, cout, D, H, W)
+    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
+    check(lib().m3d_conv3d_wgrad_narrow_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, _ptr(x_max), _ptr(gy_max),
+                                              _ptr(ws), C.c_size_t(wsb), _stream()), "conv3d_wgrad_narrow_f16x2")
     return dw
 
 

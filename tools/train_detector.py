@@ -17,7 +17,9 @@ default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated conv
 --wgrad-narrow moves the weight gradient of every intercepted dilation-1 conv on a map at most 8 wide (those head convs and, with
 --mask, the mask head's) to the 2 x 8 x 8 tile kernel (m3d.compat.set_conv_wgrad_narrow, csrc/conv3d_wgrad_narrow.hip);
 --conv-narrow f16x2 runs the forward and the backward-data pass of those convs on the narrow-map f16x2 kernel
-(m3d.compat.set_conv_train_narrow, csrc/conv3d_zn.hip).  The two compose."""
+(m3d.compat.set_conv_train_narrow, csrc/conv3d_zn.hip); --wgrad-narrow-f16 runs their weight gradient on the f16 matrix cores on that
+2 x 8 x 8 tile (m3d.compat.set_conv_wgrad_narrow_f16, csrc/conv3d_wgrad_narrow_f16.hip: layers of at least
+conv_plan.WGRAD_NARROW_F16X2_MIN_WORK products per tap, whatever --wgrad and --wgrad-narrow say).  They compose."""
 import argparse
 import os
 import sys
@@ -90,6 +92,9 @@ def main():
     ap.add_argument("--wgrad-narrow", action="store_true",
                     help="dilation-1 conv weight gradients on maps at most 8 wide (the per-RoI convs) on the 2 x 8 x 8 tile kernel "
                          "(m3d.compat.set_conv_wgrad_narrow)")
+    ap.add_argument("--wgrad-narrow-f16", action="store_true",
+                    help="weight gradients of those convs (cin and cout multiples of 32) on the f16 matrix cores at fp32 accuracy on the "
+                         "2 x 8 x 8 tile (m3d.compat.set_conv_wgrad_narrow_f16)")
     a = ap.parse_args()
     if a.mask_dilation != 1 and not a.mask:
         ap.error("--mask-dilation needs --mask")
@@ -102,6 +107,7 @@ def main():
     m3d.compat.install()
     m3d.compat.set_conv_wgrad(a.wgrad)
     m3d.compat.set_conv_wgrad_narrow(a.wgrad_narrow)
+    m3d.compat.set_conv_wgrad_narrow_f16(a.wgrad_narrow_f16)
     m3d.compat.set_conv_train_narrow(a.conv_narrow == "f16x2")
     m3d.compat.set_conv_train(a.conv)
     m3d.compat.set_roi_align_backward(a.roi_backward)
