@@ -827,6 +827,25 @@ long long m3d_conv3d_zn_launch_units(int batch, int cin, int cout, int depth, in
 int m3d_conv3d_zn_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
                           int width, const float* d_scale, const float* d_shift, int relu, const float* d_in_max, float* d_out_max,
                           void* stream);
+/* m3d_conv3d_zn_forward at dilation 1 or 2 with padding = dilation: dilation 2 / padding 2 is the 3x3x3 "same" convolution of the mask
+ * head at MRCNN.DILATION = 2 (lib/modeling/mask_rcnn_heads.py:141-151, lib/core/config.py:767) on the per-RoI 7^3 grids.  The same
+ * kernel instantiated for a 2-voxel halo (csrc/conv3d_zn.hip): the same unit of (64 output channels) x (8 x 8 x 4 voxels), the same
+ * f16x2 cut, three MFMAs per product, fp32 accumulation, exact un-scale, epilogue and d_out_max; no atomics on d_out, bit-identical run
+ * to run, every element of d_out written, a zero product exact.  The weight packs do not depend on the dilation: d_packed is an
+ * m3d_conv3d_zn_pack pack for a forward conv.  With the m3d_conv3d_zn_pack_dgrad pack of a layer's weights, that layer's output
+ * gradient as d_in, cin and cout exchanged, d_scale = d_shift = NULL and relu = 0 it is the layer's backward-data at the same dilation
+ * (padding = dilation makes the transposed conv the same dilated conv of the flipped, transposed weights, as for
+ * m3d_conv3d_forward_dilated).
+ * m3d_conv3d_zn_dilated_supported: dilation 1 what m3d_conv3d_zn_supported says, dilation 2 the same limits, any other dilation 0.
+ * m3d_conv3d_zn_dilated_launch_units: host only, the workgroups of such a launch (0 for a dilation that is not supported).
+ * m3d_conv3d_zn_dilated_forward: dilation 1 IS m3d_conv3d_zn_forward (the same launch, the same bits).  Refusals, all before a pointer
+ * is followed or anything is launched: M3D_EINVAL a NULL d_in / d_packed / d_out / d_in_max or batch <= 0; M3D_EUNSUPPORTED another
+ * dilation, a shape m3d_conv3d_zn_dilated_supported refuses, 2^31 units or more. */
+int m3d_conv3d_zn_dilated_supported(int cin, int cout, int depth, int height, int width, int dilation);
+long long m3d_conv3d_zn_dilated_launch_units(int batch, int cin, int cout, int depth, int height, int width, int dilation);
+int m3d_conv3d_zn_dilated_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth,
+                                  int height, int width, int dilation, const float* d_scale, const float* d_shift, int relu,
+                                  const float* d_in_max, float* d_out_max, void* stream);
 /* The convolution of m3d_conv3d_zw_forward on a PRM window strip [cin, depth, height, width] (peak_backprop_3d.py:8-34 batched over peaks: the windows of all
  * peaks side by side along x, cell p = columns [pitch p, pitch (p + 1)), pitch a multiple of 4 - m3d_prm_strip_geometry mode 2) with ONE
  * OPERAND SCALE PER WINDOW: d_col_bound [num_peaks x 32], element 32 p = the largest |input| of window p (one cache line per window;

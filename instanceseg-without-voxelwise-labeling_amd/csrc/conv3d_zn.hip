@@ -15,6 +15,14 @@
 // A column block is 8 x of the rows (y, z), (y, z + 1), (y + 1, z), (y + 1, z + 1), laid on the lanes so that each 16-lane group
 // ds_read_b128 is served in ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31}) reads the two rows (y, z), (y, z + 1): with a halo row pitch of
 // 10 units and a plane pitch of 104 (= 8 mod 16) those are 16 different 16-byte slots of the 256-byte bank row - no bank conflicts.
+//
+// DILATION 2 (padding 2: the mask head at MRCNN.DILATION = 2) is the second instantiation of the same kernel, conv3d_zn_kernel<2>: the
+// same unit, waves, weight packs (a pack does not depend on the dilation), cut, MFMA order and epilogue; a tap reads at 2 (d - 1), so the
+// halo is 2 voxels per side: 12 x 12 x 8 voxels, row pitch 12, plane pitch 144 -> 152 (= 8 mod 16: the same two-rows-one-plane-apart
+// reads, the same argument), four images of 8 planes = 77 824 bytes of LDS, asked for dynamically.  The map is at most 8 wide, so the
+// halo columns x < 0 and x >= 8 are padding in every chunk: they are written as zero units ONCE, before the first chunk, and staging
+// covers the 8 columns that can hold data - 12 x 8 x 8 voxels x 2 channel halves = 1536 items, exactly 6 per thread (48 raw registers
+// against the 40 of dilation 1), which keeps the kernel at two workgroups per CU without scratch.
 #include "m3d_common.h"
 
 namespace {
@@ -28,13 +36,24 @@ constexpr int ZN_NT = 256;
 constexpr int ZN_SLOTS = 32;                       // slots of an absmax array (m3d_conv3d_zw_slots)
 constexpr int ZN_STEP_UNITS = 2 * 2 * 2 * 32;      // packed weights of one (chunk, tap): [block 2][hi / lo][k half][row 32] 16-byte units
 constexpr int ZN_TY = 8, ZN_TZ = 4;                // tile: 8 x 8 x 4 voxels (x: the whole row)
-constexpr int ZN_HX = 10, ZN_HY = 10, ZN_HZ = 6;   // halo tile
-constexpr int ZN_ROW = 10, ZN_PLANE = 104;         // pitches in 16-byte units (plane: 100 -> 104 = 8 mod 16, see above)
-constexpr int ZN_IMG = ZN_HZ * ZN_PLANE;           // one (piece, k half) image
-constexpr int ZN_ITEMS = 2 * ZN_HZ * ZN_HY * ZN_HX;            // staging items of a chunk: (8-channel half, halo voxel)
-constexpr int ZN_PER = (ZN_ITEMS + ZN_NT - 1) / ZN_NT;         // items per thread
-constexpr int ZN_LDS_BYTES = 4 * ZN_IMG * 16;
-static_assert(ZN_LDS_BYTES <= 160 * 1024, "LDS");
+// the geometry of the halo tile at dilation DIL (1 or 2)
+template <int DIL>
+struct ZnGeom {
+  static constexpr int HX = 8 + 2 * DIL, HY = ZN_TY + 2 * DIL, HZ = ZN_TZ + 2 * DIL;      // halo tile: 10 x 10 x 6 / 12 x 12 x 8
+  // pitches in 16-byte units; plane: the smallest count >= HY * HX that is 8 mod 16 (100 -> 104, 144 -> 152), see above
+  static constexpr int ROW = HX, PLANE = HY * HX + (24 - HY * HX % 16) % 16;
+  static constexpr int IMG = HZ * PLANE;                       // one (piece, k half) image
+  // staged columns of a halo row: all 10 at dilation 1; at dilation 2 the 8 that can lie inside the map (the other 4 are zeroed once)
+  static constexpr int SX0 = DIL == 1 ? 0 : DIL, SXN = DIL == 1 ? HX : 8;
+  static constexpr int ITEMS = 2 * HZ * HY * SXN;              // staging items of a chunk: (8-channel half, halo voxel)
+  static constexpr int PER = (ITEMS + ZN_NT - 1) / ZN_NT;      // items per thread
+  static constexpr int LDS_BYTES = 4 * IMG * 16;
+  static constexpr bool DYNAMIC = LDS_BYTES > 64 * 1024 - 64;  // above the static limit: asked for at the launch
+  static_assert(PLANE % 16 == 8 && PLANE >= HY * HX, "plane pitch");
+  static_assert(LDS_BYTES <= 160 * 1024 / 2, "two workgroups per CU");
+};
+static_assert(ZnGeom<1>::PLANE == 104 && ZnGeom<1>::ITEMS == 1200 && ZnGeom<1>::PER == 5 && !ZnGeom<1>::DYNAMIC, "dilation 1 as it was");
+static_assert(ZnGeom<2>::PLANE == 152 && ZnGeom<2>::ITEMS == 1536 && ZnGeom<2>::PER == 6 && ZnGeom<2>::LDS_BYTES == 77824, "dilation 2");
 constexpr int acc_row(int g) { return (g & 3) + 8 * (g >> 2); }
 
 // column (lane % 32) of a column block -> (x, row y, row z) inside the block's 8 x 2 x 2 voxels
@@ -92,8 +111,19 @@ struct ZnArgs {
   int tiles_y, tiles_z, ncg;
 };
 
-__global__ __launch_bounds__(ZN_NT) void conv3d_zn_kernel(ZnArgs a) {
-  __shared__ u32x4 lds[4 * ZN_IMG];
+// (launch bounds: DIL waves per SIMD at least.  1 is what a kernel of 256 threads has anyway - dilation 1 is built as before; dilation 2
+// stages 48 raw registers per chunk against 40 and, left alone, the register allocator takes 264 registers and with them the whole SIMD
+// for one wave: asked for two - its 76 KB of LDS allow two workgroups per CU - it stays inside 256 without scratch)
+template <int DIL>
+__global__ __launch_bounds__(ZN_NT, DIL) void conv3d_zn_kernel(ZnArgs a) {
+  typedef ZnGeom<DIL> G;
+  constexpr int ZN_HX = G::HX, ZN_HY = G::HY, ZN_ROW = G::ROW, ZN_PLANE = G::PLANE, ZN_IMG = G::IMG, ZN_ITEMS = G::ITEMS, ZN_PER = G::PER;
+  // the four LDS images: static at dilation 1; at dilation 2 above the 64 KB static limit, so dynamic (the static array is then one
+  // unit that nothing touches).  ZN_LDS names the array itself under a constant condition: through a reference or a pointer the
+  // dilation-1 instantiation comes out with two registers renamed, named directly it is the code it was before the template
+  __shared__ u32x4 zn_lds_static[G::DYNAMIC ? 1 : 4 * G::IMG];
+  extern __shared__ u32x4 zn_lds_dynamic[];
+#define ZN_LDS(i) (G::DYNAMIC ? zn_lds_dynamic[i] : zn_lds_static[i])
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cb = wave & 1, yh = wave >> 1;
@@ -128,8 +158,8 @@ __global__ __launch_bounds__(ZN_NT) void conv3d_zn_kernel(ZnArgs a) {
     const int i = tid + q * ZN_NT;
     const bool has = i < ZN_ITEMS;
     const int g = has ? i / (ZN_ITEMS / 2) : 0, r = has ? i % (ZN_ITEMS / 2) : 0;
-    const int hz = r / (ZN_HY * ZN_HX), hy = (r / ZN_HX) % ZN_HY, hx = r % ZN_HX;
-    const int z = z0 - 1 + hz, y = y0 - 1 + hy, x = hx - 1;
+    const int hz = r / (ZN_HY * G::SXN), hy = (r / G::SXN) % ZN_HY, hx = G::SX0 + r % G::SXN;
+    const int z = z0 - DIL + hz, y = y0 - DIL + hy, x = hx - DIL;
     sok[q] = has & (z >= 0) & (z < a.D) & (y >= 0) & (y < a.H) & (x >= 0) & (x < a.W);
     soff[q] = sok[q] ? (int)((size_t)8 * g * DHW + (size_t)z * HW + (size_t)y * a.W + x) : 0;
     sdst[q] = has ? g * ZN_IMG + hz * ZN_PLANE + hy * ZN_ROW + hx : -1;
@@ -157,7 +187,7 @@ __global__ __launch_bounds__(ZN_NT) void conv3d_zn_kernel(ZnArgs a) {
         }
         ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
       }
-      if (sdst[q] >= 0) { lds[sdst[q]] = ph; lds[sdst[q] + 2 * ZN_IMG] = pl; }
+      if (sdst[q] >= 0) { ZN_LDS(sdst[q]) = ph; ZN_LDS(sdst[q] + 2 * ZN_IMG) = pl; }
     }
   };
 
@@ -182,6 +212,16 @@ __global__ __launch_bounds__(ZN_NT) void conv3d_zn_kernel(ZnArgs a) {
 
   fetch_in(0);
   fetch_a(A0, 0);
+  if constexpr (G::SXN < ZN_HX) {
+    // the halo columns staging never writes (x < 0, x >= 8: outside every map): zero units, once
+    constexpr int NP = ZN_HX - G::SXN, PADS = 4 * G::HZ * ZN_HY * NP;
+    for (int i = tid; i < PADS; i += ZN_NT) {
+      const int img = i / (PADS / 4), r = i % (PADS / 4);
+      const int row = r / NP, k = r % NP;
+      const int hx = k < G::SX0 ? k : G::SXN + k;
+      ZN_LDS(img * ZN_IMG + (row / ZN_HY) * ZN_PLANE + (row % ZN_HY) * ZN_ROW + hx) = u32x4{0u, 0u, 0u, 0u};
+    }
+  }
   commit_in();
   __syncthreads();
 
@@ -200,7 +240,7 @@ __global__ __launch_bounds__(ZN_NT) void conv3d_zn_kernel(ZnArgs a) {
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-          Bf[j][p] = __builtin_bit_cast(f16x8, lds[bB + (2 * (j & 1) + dz) * ZN_PLANE + (2 * (j >> 1) + dy) * ZN_ROW + dx + p * 2 * ZN_IMG]);
+          Bf[j][p] = __builtin_bit_cast(f16x8, ZN_LDS(bB + (2 * (j & 1) + DIL * dz) * ZN_PLANE + (2 * (j >> 1) + DIL * dy) * ZN_ROW + DIL * dx + p * 2 * ZN_IMG));
       constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};                     // small products first: (lo, hi) (hi, lo) (hi, hi)
 #pragma unroll
       for (int q = 0; q < 3; ++q)
@@ -252,6 +292,8 @@ __global__ __launch_bounds__(ZN_NT) void conv3d_zn_kernel(ZnArgs a) {
   }
 }
 
+#undef ZN_LDS
+
 inline size_t zn_plane_bytes(int cin, int cout) { return (size_t)((cout + 63) / 64) * (cin / 16) * 27 * ZN_STEP_UNITS * 16; }
 
 inline long long zn_units(int batch, int cout, int depth, int height) {
@@ -296,9 +338,12 @@ M3D_API long long m3d_conv3d_zn_launch_units(int batch, int cin, int cout, int d
   return zn_units(batch, cout, depth, height);
 }
 
-M3D_API int m3d_conv3d_zn_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
-                                  int width, const float* d_scale, const float* d_shift, int relu, const float* d_in_max, float* d_out_max,
-                                  void* stream) {
+namespace {
+
+// every refusal of a forward launch, before a pointer is followed; then the launch of instantiation DIL
+template <int DIL>
+int zn_launch(const char* what, const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
+              int width, const float* d_scale, const float* d_shift, int relu, const float* d_in_max, float* d_out_max, void* stream) {
   if (!d_in || !d_packed || !d_out || !d_in_max || batch <= 0) return M3D_EINVAL;
   if (!m3d_conv3d_zn_supported(cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
   ZnArgs a{};
@@ -309,6 +354,45 @@ M3D_API int m3d_conv3d_zn_forward(const float* d_in, const void* d_packed, float
   a.tiles_y = (height + ZN_TY - 1) / ZN_TY; a.tiles_z = (depth + ZN_TZ - 1) / ZN_TZ; a.ncg = (cout + 63) / 64;
   const long long units = zn_units(batch, cout, depth, height);
   if (units > 0x7FFFFFFFll) return M3D_EUNSUPPORTED;
-  hipLaunchKernelGGL(conv3d_zn_kernel, dim3((unsigned)units), dim3(ZN_NT), 0, m3d::as_stream(stream), a);
-  return m3d::check_launch("conv3d_zn_forward");
+  auto kern = conv3d_zn_kernel<DIL>;
+  unsigned dyn = 0;
+  if (ZnGeom<DIL>::DYNAMIC) {
+    // 76 KB of LDS: asked for per launch, as conv3d_wgrad_narrow_f16.hip does (the attribute belongs to the current device's copy of the kernel)
+    dyn = ZnGeom<DIL>::LDS_BYTES;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)units), dim3(ZN_NT), dyn, m3d::as_stream(stream), a);
+  return m3d::check_launch(what);
+}
+
+}  // namespace
+
+M3D_API int m3d_conv3d_zn_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth, int height,
+                                  int width, const float* d_scale, const float* d_shift, int relu, const float* d_in_max, float* d_out_max,
+                                  void* stream) {
+  return zn_launch<1>("conv3d_zn_forward", d_in, d_packed, d_out, batch, cin, cout, depth, height, width, d_scale, d_shift, relu, d_in_max,
+                      d_out_max, stream);
+}
+
+/* ---- dilation 1 or 2 (padding = dilation) ---- */
+M3D_API int m3d_conv3d_zn_dilated_supported(int cin, int cout, int depth, int height, int width, int dilation) {
+  if (dilation != 1 && dilation != 2) return 0;
+  return m3d_conv3d_zn_supported(cin, cout, depth, height, width);           // the tile and the limits are the same at both
+}
+
+/* host only: workgroups of an m3d_conv3d_zn_dilated_forward launch (both dilations run the 8 x 8 x 4 tile; 0 for another dilation) */
+M3D_API long long m3d_conv3d_zn_dilated_launch_units(int batch, int cin, int cout, int depth, int height, int width, int dilation) {
+  if (dilation != 1 && dilation != 2) return 0;
+  return m3d_conv3d_zn_launch_units(batch, cin, cout, depth, height, width);
+}
+
+M3D_API int m3d_conv3d_zn_dilated_forward(const float* d_in, const void* d_packed, float* d_out, int batch, int cin, int cout, int depth,
+                                          int height, int width, int dilation, const float* d_scale, const float* d_shift, int relu,
+                                          const float* d_in_max, float* d_out_max, void* stream) {
+  if (!d_in || !d_packed || !d_out || !d_in_max || batch <= 0) return M3D_EINVAL;
+  if (dilation == 1)
+    return m3d_conv3d_zn_forward(d_in, d_packed, d_out, batch, cin, cout, depth, height, width, d_scale, d_shift, relu, d_in_max, d_out_max, stream);
+  if (dilation != 2) return M3D_EUNSUPPORTED;
+  return zn_launch<2>("conv3d_zn_dilated_forward", d_in, d_packed, d_out, batch, cin, cout, depth, height, width, d_scale, d_shift, relu,
+                      d_in_max, d_out_max, stream);
 }

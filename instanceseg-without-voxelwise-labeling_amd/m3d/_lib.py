@@ -51,6 +51,7 @@ SYMBOLS = [
     "m3d_conv3d_wgrad_narrow_f16x2",
     "m3d_conv3d_zn_supported", "m3d_conv3d_zn_packed_bytes", "m3d_conv3d_zn_pack", "m3d_conv3d_zn_pack_dgrad", "m3d_conv3d_zn_launch_units",
     "m3d_conv3d_zn_forward",
+    "m3d_conv3d_zn_dilated_supported", "m3d_conv3d_zn_dilated_launch_units", "m3d_conv3d_zn_dilated_forward",
 ]
 
 
@@ -119,6 +120,7 @@ def _load(path):
     L.m3d_conv3d_x3_launch_units.restype = C.c_longlong
     L.m3d_conv3d_zw_launch_units.restype = C.c_longlong
     L.m3d_conv3d_zn_launch_units.restype = C.c_longlong
+    L.m3d_conv3d_zn_dilated_launch_units.restype = C.c_longlong
     for n in ("m3d_roi_align3d_workspace_bytes", "m3d_roi_align3d_backward_ordered_workspace_bytes","m3d_nms3d_workspace_bytes", "m3d_generate_proposals3d_workspace_bytes",
               "m3d_conv3d_packed_weight_bytes", "m3d_conv3d_x3_packed_bytes", "m3d_conv3d_x3f_packed_bytes", "m3d_conv3d_zw_packed_bytes", "m3d_reduce_minmax_multi_workspace_bytes", "m3d_conv3d_x3_workspace_bytes", "m3d_reduce_min_workspace_bytes", "m3d_reduce_min_multi_workspace_bytes", "m3d_norm1_workspace_bytes", "m3d_prm_small_dgrad_packed_bytes", "m3d_prm_small_dgrad_f16_packed_bytes", "m3d_prm_small_dgrad_f16_workspace_bytes", "m3d_linear_workspace_bytes", "m3d_linear_bf16x3_packed_bytes", "m3d_linear_bf16x3_workspace_bytes", "m3d_linear_f16x2_packed_bytes", "m3d_linear_f16x2_workspace_bytes", "m3d_linear_bf16x3_w32_workspace_bytes", "m3d_linear_bf16x3_roi_workspace_bytes", "m3d_mask_paste3d_workspace_bytes", "m3d_generate_proposals3d_batched_workspace_bytes",
               "m3d_box_results3d_batched_workspace_bytes", "m3d_nms3d_batched_workspace_bytes", "m3d_otsu2d_workspace_bytes",

@@ -17,6 +17,8 @@ backward-data, so lib/modeling/DSN.py and lib/prm/peak_backprop_3d.py run unchan
 set_conv_wgrad_narrow(True) (opt-in) the weight gradient of the dilation-1 3^3 convs on maps at most 8 wide - the per-RoI convs of the
 conv box head and of the mask head - runs on the 2 x 8 x 8 tile kernel (m3d_conv3d_wgrad_narrow).
 set_conv_wgrad_narrow_f16(True) (opt-in) runs that weight gradient on the f16 matrix cores instead (m3d_conv3d_wgrad_narrow_f16x2).
+set_conv_dilated_f16(True) (opt-in, under set_conv_dilated("m3d")) runs the forward and the backward-data pass of the dilation-2 convs on
+maps at most 8 wide on the dilation-2 instantiation of the narrow-map f16x2 kernel (m3d_conv3d_zn_dilated_forward).
 set_conv_train_narrow(True) (opt-in) runs the forward and the backward-data pass of those same convs on the narrow-map f16x2 kernel
 (m3d_conv3d_zn_forward, csrc/conv3d_zn.hip).
 What the setters say is one conv_plan.TrainSetting; what a routed conv launches under it, forward and backward, is decided by
@@ -205,6 +207,7 @@ def _packed(weight, mode):
 
 _setting = conv_plan.TrainSetting()          # what the setters below say; WHEN each field is read: the TrainSetting docstring
 _wgrad_narrow_f16 = None                     # set_conv_wgrad_narrow_f16: None (off) or its threshold; beside _setting, whose fields are pinned
+_dilated_f16 = None                          # set_conv_dilated_f16: None (off) or its threshold in launch units; beside _setting too
 
 
 def set_conv_wgrad(mode):
@@ -313,8 +316,9 @@ def set_conv_dilated(mode):
     """The 3^3 convs with dilation 2 and padding 2 (the mask head at MRCNN.DILATION = 2, train.MaskHead): "torch" (the default;
     install() does not change it) leaves them to torch's own conv3d, as every other dilation always is; "m3d" takes the library in
     training: forward m3d_conv3d_forward_dilated, gx the same on the W_DGRAD pack, gw m3d_conv3d_wgrad_dilated, gb m3d_conv3d_bias_grad
-    (DESIGN, "Dilated conv backward").  All fp32: set_conv_train("f16x2") and set_conv_wgrad("f16x2") do not reach these layers.  The
-    backward of a call follows the mode its forward ran under.  Returns the previous mode."""
+    (DESIGN, "Dilated conv backward").  All fp32: set_conv_train("f16x2") and set_conv_wgrad("f16x2") do not reach these layers;
+    set_conv_dilated_f16 (opt-in) moves their forward and dgrad on narrow maps to the f16 matrix cores.  The backward of a call follows
+    the mode its forward ran under.  Returns the previous mode."""
     global _setting
     if mode not in (CONV_DILATED_TORCH, CONV_DILATED_M3D):
         raise ValueError("set_conv_dilated(%r): 'torch' or 'm3d'" % (mode,))
@@ -326,6 +330,29 @@ def get_conv_dilated():
     return _setting.dilated
 
 
+def set_conv_dilated_f16(on, min_units=None):
+    """The forward and backward-data kernels of the dilation-2 convs that set_conv_dilated("m3d") routes to the library, on maps at most
+    8 wide with launched input channels a multiple of 16 (train.MaskHead at MRCNN.DILATION = 2 on 7^3 RoI grids): False (the default;
+    install() does not change it) keeps m3d_conv3d_forward_dilated, the direct fp32 kernel; True takes the dilation-2 instantiation of
+    the narrow-map f16x2 kernel (ops.ZnConv3d(..., dilation=2), csrc/conv3d_zn.hip; dgrad on its dgrad_of pack) for the layers and
+    directions conv_plan.plan_train_conv(dilated_f16=) routes to it.  Such a forward sweeps x once; such a dgrad takes gy's bound from
+    m3d_conv3d_gy_reduce, which then also gives the bias gradient (the rule of set_conv_train_narrow).  The weight gradient stays on
+    m3d_conv3d_wgrad_dilated.  Without set_conv_dilated("m3d") it has no effect.  min_units: the routing threshold in launch units
+    (None: conv_plan.ZN_DILATED_MIN_UNITS; 0 routes every supported layer - tests and A/B runs; a call without it puts the default
+    back).  Read at forward time; the backward of a call follows the value its forward ran under.  Returns the previous setting
+    (True / False)."""
+    global _dilated_f16
+    if min_units is not None and int(min_units) < 0:
+        raise ValueError("set_conv_dilated_f16(min_units=%r): None or a count >= 0" % (min_units,))
+    prev = _dilated_f16 is not None
+    _dilated_f16 = (conv_plan.ZN_DILATED_MIN_UNITS if min_units is None else int(min_units)) if on else None
+    return prev
+
+
+def get_conv_dilated_f16():
+    return _dilated_f16 is not None
+
+
 class _Conv3dFn(torch.autograd.Function):
     """A conv that conv3d() routes to the library (dilation 1 or 2): runs conv_plan.plan_train_conv's plan, the forward half in
     forward, the backward half in backward.  Nothing is decided here."""
@@ -335,8 +362,9 @@ class _Conv3dFn(torch.autograd.Function):
         ctx.save_for_backward(weight, x if weight.requires_grad else None)
         ctx.has_bias = bias is not None
         ctx.setting, ctx.xshape, ctx.dilation = _setting, tuple(x.shape), dilation      # (when each switch is read: TrainSetting)
+        ctx.dilated_f16 = _dilated_f16                                                  # (read here; the backward follows it)
         shift = bias.detach().contiguous() if bias is not None else None
-        kind, sweep = conv_plan.plan_train_forward(_setting, ctx.xshape, weight.shape, dilation)
+        kind, sweep = conv_plan.plan_train_forward(_setting, ctx.xshape, weight.shape, dilation, _dilated_f16)
         ctx.x_max = ops.ZwConv3d.bound_of(x) if sweep else None        # kept for the f16x2 wgrad
         if kind == conv_plan.TRAIN_F16X2:
             return _packed(weight, "zw-plain")(x, ctx.x_max, shift=shift, out_max=False)[0]
@@ -344,6 +372,8 @@ class _Conv3dFn(torch.autograd.Function):
             return _packed(weight, "zn-plain")(x, ctx.x_max, shift=shift, out_max=False)[0]
         if kind == conv_plan.TRAIN_DILATED:
             return _packed(weight, "plain")(x, shift=shift, dilation=2)
+        if kind == conv_plan.TRAIN_DILATED_F16X2:
+            return _packed(weight, "zn-plain")(x, ctx.x_max, shift=shift, out_max=False, dilation=2)[0]
         return _packed(weight, "plain")(x, shift=shift)
 
     @staticmethod
@@ -353,7 +383,7 @@ class _Conv3dFn(torch.autograd.Function):
         setting = ctx.setting._replace(wgrad=_setting.wgrad, wgrad_narrow=_setting.wgrad_narrow)
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
         dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs,
-                                                                         _wgrad_narrow_f16)
+                                                                         _wgrad_narrow_f16, ctx.dilated_f16)
         gx = gw = gb = gy_max = None
         if gy_reduce:
             gb, gy_max = ops.conv3d_gy_reduce(gy, bias=gb_from == conv_plan.GB_REDUCE)
@@ -368,6 +398,11 @@ class _Conv3dFn(torch.autograd.Function):
             gx = _packed(weight, "dgrad")(gy, dilation=2)
         elif dgrad == conv_plan.TRAIN_FP32:
             gx = _packed(weight, "dgrad")(gy)
+        else:
+            # the kinds left: None (gx not needed) and TRAIN_DILATED_F16X2, on the pack and with the bound TRAIN_F16X2_NARROW takes (an
+            # else, as in the wgrad chain below: the count of branches of this function is pinned)
+            assert dgrad in (None, conv_plan.TRAIN_DILATED_F16X2), dgrad
+            gx = None if dgrad is None else _packed(weight, "zn-dgrad")(gy, gy_max, out_max=False, dilation=2)[0]
 
         if wgrad == conv_plan.WGRAD_F16X2:
             # x's bound from the forward where that ran on an f16x2 kernel, gy's from the reduce where that ran; a missing one is swept

@@ -139,6 +139,13 @@ TRAIN_DILATED = "dilated"                            # forward / dgrad kind: m3d
 DGRAD_STEM = "stem"                                  # dgrad kind: the VALU kernel of the 5^3 / Cin = 1 stem (m3d_conv3d_stem5_dgrad)
 WGRAD_DILATED = "dilated"                            # wgrad kind: m3d_conv3d_wgrad_dilated
 GB_REDUCE, GB_BIAS_GRAD = "gy_reduce", "bias_grad"   # where the bias gradient comes from
+# forward / dgrad kind: the dilation-2 instantiation of the narrow f16x2 kernel (m3d_conv3d_zn_dilated_forward; dgrad on the
+# m3d_conv3d_zn_pack_dgrad pack): maps at most 8 wide under DILATED_M3D, opt-in (compat.set_conv_dilated_f16)
+TRAIN_DILATED_F16X2 = "f16x2 dilated"
+# Its routing threshold in launch units (64 channels x 8 x 8 x 4 voxels; a 7^3 RoI grid is 2 units per RoI and 64 channels): the unit
+# count of the smallest launch of profiles/conv_narrow_f16_dilated.txt that beat m3d_conv3d_forward_dilated by more than the sum of the
+# spreads, sweep / gy_reduce and the per-step pack inside the window.  Nothing below a measured win routes.
+ZN_DILATED_MIN_UNITS = 128
 
 
 class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narrow wgrad wgrad_narrow dilated",
@@ -155,12 +162,13 @@ class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narro
     runs (the Function puts the current two into the kept setting before it asks plan_train_backward).
     The field list is pinned (tests/test_conv_train_dispatch.py compares _asdict() of the defaults), so the one later switch,
     set_conv_wgrad_narrow_f16, travels beside the setting: the wgrad_narrow_f16 argument of plan_train_backward / plan_train_conv,
-    read when the backward runs as the other two wgrad switches are."""
+    read when the backward runs as the other two wgrad switches are.  set_conv_dilated_f16 travels the same way (the dilated_f16
+    argument of the three plan functions), read at FORWARD time: the backward follows the forward's value, as it does for dilated."""
     __slots__ = ()
 
 
-# forward: TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED; sweep: the forward sweeps x for its operand bound and keeps it
-# (for the f16x2 wgrad); dgrad: None (gx not needed) / DGRAD_STEM / TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED;
+# forward: TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED / TRAIN_DILATED_F16X2; sweep: the forward sweeps x for its operand bound and keeps it
+# (for the f16x2 wgrad); dgrad: None (gx not needed) / DGRAD_STEM / TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED / TRAIN_DILATED_F16X2;
 # wgrad: None (gw not needed) / WGRAD_FP32 / WGRAD_F16X2 / WGRAD_NARROW / WGRAD_NARROW_F16X2 / WGRAD_DILATED; gy_reduce: m3d_conv3d_gy_reduce runs first (one
 # pass over gy: its operand bound, and the bias gradient where needed); gb: None / GB_REDUCE / GB_BIAS_GRAD
 TrainConvPlan = collections.namedtuple("TrainConvPlan", "forward sweep dgrad wgrad gy_reduce gb")
@@ -176,20 +184,44 @@ def _train_rule(direction, setting, xshape, wshape):
                              min_units=ZW_MIN_UNITS if setting.min_units is None else setting.min_units, k=wshape[2], **kw)
 
 
-def plan_train_forward(setting, xshape, wshape, dilation):
-    """(forward, sweep) of plan_train_conv: what the forward of the call needs, and no library query beyond that"""
+def _dilated_takes(batch, ci, co, D, H, W, min_units):
+    """the dilation-2 narrow f16x2 kernel takes the launched conv [batch, ci, D, H, W] -> co and the launch reaches min_units units"""
+    L = ops.lib()
+    if batch < 1 or ci < 1 or co < 1 or not L.m3d_conv3d_zn_dilated_supported(ci, co, D, H, W, 2):
+        return False
+    return L.m3d_conv3d_zn_dilated_launch_units(batch, ci, co, D, H, W, 2) >= int(min_units)
+
+
+def _dilated_rule(direction, setting, xshape, wshape, dilated_f16):
+    """the forward / dgrad kind of a dilation-2 layer: TRAIN_DILATED_F16X2 where the switch is on (dilated_f16: its threshold in launch
+    units) under DILATED_M3D and the kernel takes the LAUNCHED conv (a dgrad swaps the channel roles, as train_conv_kernel does), else
+    TRAIN_DILATED.  With dilated_f16 None no library query is made."""
+    if dilated_f16 is None or setting.dilated != DILATED_M3D or int(wshape[2]) != 3:
+        return TRAIN_DILATED
+    B, _, D, H, W = (int(v) for v in xshape)
+    ci, co = (int(wshape[1]), int(wshape[0])) if direction == "forward" else (int(wshape[0]), int(wshape[1]))
+    return TRAIN_DILATED_F16X2 if _dilated_takes(B, ci, co, D, H, W, dilated_f16) else TRAIN_DILATED
+
+
+def plan_train_forward(setting, xshape, wshape, dilation, dilated_f16=None):
+    """(forward, sweep) of plan_train_conv: what the forward of the call needs, and no library query beyond that.  dilated_f16: None (the
+    dilation-2 f16x2 kernel is off), else its routing threshold in launch units (compat.set_conv_dilated_f16)"""
     if dilation == 2:
-        return TRAIN_DILATED, False
+        forward = _dilated_rule("forward", setting, xshape, wshape, dilated_f16)
+        return forward, forward == TRAIN_DILATED_F16X2
     forward = _train_rule("forward", setting, xshape, wshape)
     return forward, forward != TRAIN_FP32
 
 
-def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None):
+def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None):
     """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs.  wgrad_narrow_f16: None (the narrow f16x2
-    wgrad kernel is off), else its routing threshold in products per tap (compat.set_conv_wgrad_narrow_f16)"""
+    wgrad kernel is off), else its routing threshold in products per tap (compat.set_conv_wgrad_narrow_f16); dilated_f16: as
+    plan_train_forward's"""
     gx, gw, gb = (bool(v) for v in needs)
-    if dilation == 2:                                  # all fp32: train and wgrad do not reach these layers
-        return (TRAIN_DILATED if gx else None), (WGRAD_DILATED if gw else None), False, (GB_BIAS_GRAD if gb else None)
+    if dilation == 2:                                  # train and wgrad do not reach these layers; the weight gradient is always fp32
+        dgrad = _dilated_rule("dgrad", setting, xshape, wshape, dilated_f16) if gx else None
+        gy_reduce = dgrad == TRAIN_DILATED_F16X2       # gy's bound, and then the bias gradient too: the rule of TRAIN_F16X2_NARROW
+        return dgrad, (WGRAD_DILATED if gw else None), gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
     B, _, D, H, W = xshape
     cout, cin, k = wshape[:3]
     dgrad = None if not gx else DGRAD_STEM if k == 5 else _train_rule("dgrad", setting, xshape, wshape)
@@ -206,20 +238,25 @@ def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f
     return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
 
 
-def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None):
+def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None):
     """What a training conv that m3d.compat.conv3d routes to the library launches, forward and backward: a TrainConvPlan.  The only place
     that combines the rules (train_conv_kernel and wgrad_kernel are its rows); host queries of the library only, a function of its
     arguments only.  setting: a TrainSetting; xshape [B, cin, D, H, W]; wshape [cout, cin, k, k, k]; dilation: 1 (stride 1, padding
     k // 2, k in {1, 3} or the 5^3 / Cin = 1 stem) or 2 (k = 3, padding 2, only routed under DILATED_M3D); needs = (gx, gw, gb) of
     needs_input_grad, gb already False for a layer without bias; wgrad_narrow_f16: None or the threshold of
-    compat.set_conv_wgrad_narrow_f16 (it moves the wgrad field only: gy_reduce and gb do not depend on it).
+    compat.set_conv_wgrad_narrow_f16 (it moves the wgrad field only: gy_reduce and gb do not depend on it); dilated_f16: None or the
+    threshold in launch units of compat.set_conv_dilated_f16 (it moves dilation-2 layers under DILATED_M3D only).  "dilated f16x2
+    takes": dilated_f16 is a threshold, setting.dilated is DILATED_M3D, m3d_conv3d_zn_dilated_supported takes the LAUNCHED conv at
+    dilation 2 (a dgrad swaps the channel roles) and m3d_conv3d_zn_dilated_launch_units reaches the threshold.
 
     | field     | value              | condition                                                                                      |
-    | forward   | TRAIN_DILATED      | dilation 2                                                                                     |
+    | forward   | TRAIN_DILATED_F16X2| dilation 2 and dilated f16x2 takes the forward conv                                            |
+    |           | TRAIN_DILATED      | dilation 2 otherwise                                                                           |
     |           | else               | train_conv_kernel("forward", ...) under setting.train / min_units / narrow                     |
-    | sweep     | True               | forward is TRAIN_F16X2 or TRAIN_F16X2_NARROW                                                   |
+    | sweep     | True               | forward is TRAIN_F16X2, TRAIN_F16X2_NARROW or TRAIN_DILATED_F16X2                              |
     | dgrad     | None               | gx not needed                                                                                  |
-    |           | TRAIN_DILATED      | dilation 2                                                                                     |
+    |           | TRAIN_DILATED_F16X2| dilation 2 and dilated f16x2 takes the backward-data conv                                      |
+    |           | TRAIN_DILATED      | dilation 2 otherwise                                                                           |
     |           | DGRAD_STEM         | k = 5                                                                                          |
     |           | else               | train_conv_kernel("dgrad", ...)                                                                |
     | wgrad     | None               | gw not needed                                                                                  |
@@ -227,14 +264,15 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=N
     |           | WGRAD_NARROW_F16X2 | wgrad_narrow_f16 is a threshold, k = 3, m3d_conv3d_wgrad_narrow_f16x2_supported, work >= it    |
     |           | else               | wgrad_kernel(...) under setting.wgrad / wgrad_narrow                                           |
     | gy_reduce | True               | dilation 1 and: train is f16x2 and (dgrad or wgrad is f16x2, or gb needed); or dgrad is narrow |
+    |           | True               | dilation 2 and dgrad is TRAIN_DILATED_F16X2                                                    |
     | gb        | None               | gb not needed                                                                                  |
     |           | GB_REDUCE          | gy_reduce                                                                                      |
     |           | GB_BIAS_GRAD       | else                                                                                           |
 
     compat asks the two halves when it needs them (plan_train_forward in forward, plan_train_backward in backward): a call makes the
     library queries of the directions it runs and no others."""
-    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation)
-                           + plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16)))
+    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation, dilated_f16)
+                           + plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16, dilated_f16)))
 
 
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True, narrow_f16=False):

@@ -7,22 +7,32 @@ reaches this; it exists so that a MASK_ON checkpoint has somewhere to go.  `segm
 M^3 masks into the volume on the device (csrc/mask_paste.hip: skimage.transform.resize restated on scipy.ndimage's arithmetic).
 
 Every convolution runs in the HIP library:
-  * the dilated 3x3x3 convs through m3d_conv3d_forward_dilated (direct MFMA kernel, halo = dilation);
+  * the dilated 3x3x3 convs through m3d_conv3d_forward_dilated (direct MFMA kernel, halo = dilation); with conv_f16 / M3D_MASK_CONV_F16
+    (opt-in) on the narrow-map f16x2 kernel instead (ops.ZnConv3d, csrc/conv3d_zn.hip: dilation 1 and 2, maps at most 8 wide), the
+    operand bound carried from conv to conv;
   * ConvTranspose3d(kernel 2, stride 2) never overlaps its outputs, so it is a 1x1x1 conv to 8*Cout channels
     (one per output parity (a,b,c)) followed by a voxel shuffle to the 2x grid; bias + ReLU ride in the conv epilogue.
     Under compat.set_upconv("m3d") it is one m3d_upconv3d_2x_forward instead, whose epilogue writes the 2x grid directly;
   * the 1x1x1 classifier through m3d_conv3d_forward."""
+import os
+
 import numpy as np
 import torch
 
-from . import ops
+from . import conv_plan, ops
 
 
 class MaskHeadM3D:
-    def __init__(self, params, cfg, resolution=None, roi_res=None, sampling_ratio=None, dilation=None, cls_specific=None):
+    def __init__(self, params, cfg, resolution=None, roi_res=None, sampling_ratio=None, dilation=None, cls_specific=None, conv_f16=None,
+                 conv_f16_min_units=None):
         """params: CUDA fp32 tensors under the reference's state-dict keys `Mask_Head.conv_fcn.{0,2,..}.{weight,bias}`,
         `Mask_Head.upconv.{weight,bias}`, `Mask_Outs.classify.{weight,bias}`.  The MRCNN.* settings come from cfg
-        (Cfg.from_yaml reads them; defaults = lib/core/config.py:751-780) unless given here."""
+        (Cfg.from_yaml reads them; defaults = lib/core/config.py:751-780) unless given here.
+        conv_f16: the conv_fcn layers on the narrow-map f16x2 kernel (ops.ZnConv3d at the head's dilation, 1 or 2) where it takes the
+        layer: cin % 16 == 0, a RoI grid at most 8 wide, and a launch of at least conv_f16_min_units units (None: the measured routing
+        threshold of the dilation, conv_plan.ZN_MIN_UNITS / ZN_DILATED_MIN_UNITS; 0 routes every supported launch - tests and A/B runs).
+        Every other layer stays on PackedConv3d.  None reads M3D_MASK_CONV_F16 (default "0"); like M3D_HEAD_CONV_F16 it needs
+        M3D_CONV_F16 not to be off.  Off, the head is bit for bit what it was without the argument."""
         self.cfg = cfg
         resolution = getattr(cfg, "mask_resolution", 14) if resolution is None else resolution
         roi_res = getattr(cfg, "mask_roi_res", 7) if roi_res is None else roi_res
@@ -31,12 +41,18 @@ class MaskHeadM3D:
         cls_specific = getattr(cfg, "mask_cls_specific", True) if cls_specific is None else cls_specific
         self.M, self.roi_res, self.sampling_ratio, self.dilation = int(resolution), int(roi_res), int(sampling_ratio), int(dilation)
         self.cls_specific = bool(cls_specific)
-        self.convs = []
+        if conv_f16 is None:
+            conv_f16 = os.environ.get("M3D_MASK_CONV_F16", "0") == "1"
+        self.conv_f16 = bool(conv_f16) and os.environ.get("M3D_CONV_F16", "1") == "1" and self.dilation in (1, 2)
+        default_units = conv_plan.ZN_DILATED_MIN_UNITS if self.dilation == 2 else conv_plan.ZN_MIN_UNITS
+        self.conv_f16_min_units = default_units if conv_f16_min_units is None else int(conv_f16_min_units)
+        self.convs, self.zn = [], []                   # zn[i]: the f16x2 pack of conv i, or None (conv_f16 off, or cin % 16 != 0)
         i = 0
         while "Mask_Head.conv_fcn.%d.weight" % (2 * i) in params:                 # mask_rcnn_heads.py:146-153
             w = params["Mask_Head.conv_fcn.%d.weight" % (2 * i)]
             assert tuple(w.shape[2:]) == (3, 3, 3)
             self.convs.append((ops.PackedConv3d(w), params["Mask_Head.conv_fcn.%d.bias" % (2 * i)].contiguous()))
+            self.zn.append(ops.ZnConv3d(w) if self.conv_f16 and ops.ZnConv3d.supported(w) else None)
             i += 1
         if not self.convs:
             raise KeyError("no Mask_Head.conv_fcn.* weights in the state dict")
@@ -61,12 +77,31 @@ class MaskHeadM3D:
             t = self._ones[n] = torch.ones((n,), dtype=torch.float32, device=device)
         return t
 
-    def trunk(self, feat, mask_rois):
-        """RoIAlign3D and the dilated convs of Mask_Head.forward (mask_rcnn_heads.py:181-192): [R, C, M', M', M'] with M' = roi_res."""
+    def _zn_takes(self, i, shape):
+        """conv i runs on the f16x2 kernel for an input of this shape [R, cin, M', M', M']"""
+        zn = self.zn[i]
+        return (zn is not None and shape[0] > 0 and zn.supports(shape, dilation=self.dilation)
+                and zn.units(shape, dilation=self.dilation) >= self.conv_f16_min_units)
+
+    def trunk(self, feat, mask_rois, feat_max=None):
+        """RoIAlign3D and the dilated convs of Mask_Head.forward (mask_rcnn_heads.py:181-192): [R, C, M', M', M'] with M' = roi_res.
+        feat_max (conv_f16 only): the operand bound of feat as the conv that produced it left it ([ZwConv3d.SLOTS] device floats, the
+        largest = a bound of max |feat|).  Every RoIAlign value is a convex combination of feature-map values, so it bounds the first
+        conv's input too (the argument DetectorM3D uses for the conv box head); None: one ZwConv3d.bound_of sweep of the RoIAlign
+        output.  Each conv's epilogue leaves the next conv's bound."""
         c = self.cfg
         x = ops.roi_align3d_forward(feat, mask_rois, self.roi_res, self.roi_res, self.roi_res, 1.0 / c.stride, self.sampling_ratio)
-        for conv, bias in self.convs:
-            x = conv(x, scale=self._one(conv.cout, x.device), shift=bias, relu=True, dilation=self.dilation)
+        bound = feat_max                               # the bound of x where one is held, else None
+        last = len(self.convs) - 1
+        for i, (conv, bias) in enumerate(self.convs):
+            if self.conv_f16 and self._zn_takes(i, tuple(x.shape)):
+                if bound is None:
+                    bound = ops.ZwConv3d.bound_of(x)
+                nxt = i < last and self._zn_takes(i + 1, (x.shape[0], conv.cout) + tuple(x.shape[2:]))
+                x, bound = self.zn[i](x, bound, shift=bias, relu=True, out_max=None if nxt else False, dilation=self.dilation)
+            else:
+                x = conv(x, scale=self._one(conv.cout, x.device), shift=bias, relu=True, dilation=self.dilation)
+                bound = None
         return x
 
     def up(self, x):

@@ -1686,9 +1686,12 @@ class ZwConv3d(_F16x2Conv3d):
 
 
 class ZnConv3d(_F16x2Conv3d):
-    """3x3x3 conv (stride 1, pad 1) + scale/shift + ReLU on maps at most 8 wide - the per-RoI convs on 7^3 RoI grids - on the f16 matrix
-    cores at fp32 accuracy (csrc/conv3d_zn.hip: f16x2 split, direct 27 taps, one workgroup per 64 channels x 8 x 8 x 4 voxels, no atomics
-    on the output); operand bounds as _F16x2Conv3d says (bound_of is ZwConv3d's sweep).  No fused pool.  __call__ -> (out, out_max)."""
+    """3x3x3 conv (stride 1, padding = dilation, dilation 1 or 2) + scale/shift + ReLU on maps at most 8 wide - the per-RoI convs on 7^3
+    RoI grids - on the f16 matrix cores at fp32 accuracy (csrc/conv3d_zn.hip: f16x2 split, direct 27 taps, one workgroup per 64 channels
+    x 8 x 8 x 4 voxels, no atomics on the output); operand bounds as _F16x2Conv3d says (bound_of is ZwConv3d's sweep).  No fused pool.
+    __call__ -> (out, out_max).  A pack serves both dilations (ZnConv3d(weight) and dgrad_of(weight) alike): dilation 1 takes
+    m3d_conv3d_zn_forward and the queries beside it, exactly as before the argument existed; dilation 2 (the mask head at
+    MRCNN.DILATION = 2) takes m3d_conv3d_zn_dilated_forward / _supported / _launch_units."""
     FAMILY = "zn"
 
     @staticmethod
@@ -1696,10 +1699,29 @@ class ZnConv3d(_F16x2Conv3d):
         if not ok:
             raise ValueError("ZnConv3d.dgrad_of: weight [cout, cin, 3, 3, 3] with cout %% 16 == 0, got %s" % (tuple(weight.shape),))
 
-    def __call__(self, x, in_max, scale=None, shift=None, relu=False, out=None, out_max=None):
+    def supports(self, shape, pool=False, dilation=1):
+        if int(dilation) == 1:
+            return super().supports(shape, pool)
+        D, H, W = (int(v) for v in shape[-3:])
+        return not pool and bool(lib().m3d_conv3d_zn_dilated_supported(self.cin, self.cout, D, H, W, int(dilation)))
+
+    def units(self, shape, dilation=1):
+        if int(dilation) == 1:
+            return super().units(shape)
+        B = int(shape[0]) if len(shape) == 5 else 1
+        D, H, W = (int(v) for v in shape[-3:])
+        return int(lib().m3d_conv3d_zn_dilated_launch_units(B, self.cin, self.cout, D, H, W, int(dilation)))
+
+    def __call__(self, x, in_max, scale=None, shift=None, relu=False, out=None, out_max=None, dilation=1):
         """out_max: a ZEROED [SLOTS] float tensor to receive the output's bound (None: a fresh one; False: no bound output)."""
         x, out, out_max = self._operands(x, in_max, out, out_max)
         B, cin, D, H, W = x.shape
+        if int(dilation) != 1:
+            check(lib().m3d_conv3d_zn_dilated_forward(_ptr(x), _ptr(self.packed), _ptr(out), B, cin, self.cout, D, H, W, int(dilation),
+                                                      _ptr(scale) if scale is not None else None, _ptr(shift) if shift is not None else None,
+                                                      int(bool(relu)), _ptr(in_max), _ptr(out_max) if out_max is not None else None,
+                                                      _stream()), "conv3d_zn_dilated_forward")
+            return out, out_max
         check(lib().m3d_conv3d_zn_forward(_ptr(x), _ptr(self.packed), _ptr(out), B, cin, self.cout, D, H, W,
                                           _ptr(scale) if scale is not None else None, _ptr(shift) if shift is not None else None,
                                           int(bool(relu)), _ptr(in_max), _ptr(out_max) if out_max is not None else None,

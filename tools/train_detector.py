@@ -10,7 +10,9 @@ Prints all four losses per step.  One fixed sample; this is not a training drive
 
 --mask spot (off by default; without it nothing changes) adds the mask branch: m3d.MaskHead on the same features, m3d.mask_targets from
 the spheres inscribed in the synthetic boxes, m3d.mask_losses; loss_mask joins the printed line and the sum.  --mask-dilation 2 builds that head with MRCNN.DILATION = 2 (the reference's
-default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated convs on the library, forward and backward.
+default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated convs on the library, forward and backward;
+--conv-dilated-f16 (with --conv-dilated m3d) runs their forward and backward-data pass on the dilation-2 instantiation of the
+narrow-map f16x2 kernel (m3d.compat.set_conv_dilated_f16, csrc/conv3d_zn.hip: launches of at least conv_plan.ZN_DILATED_MIN_UNITS units).
 
 --box-head conv (default mlp, whose output stays as it is) trains m3d.ConvBoxHead (roi_Xconv1fc_head, fast_rcnn_heads.py:120-179:
 --conv-head-convs 3^3 convs of --conv-head-dim channels on the 7^3 grids, then one FC layer of --hidden) in place of the two-FC head;
@@ -82,6 +84,9 @@ def main():
     ap.add_argument("--conv-dilated", choices=("torch", "m3d"), default="torch",
                     help="the dilation-2 convs (m3d.compat.set_conv_dilated): m3d = the library's dilated forward, dgrad and wgrad "
                          "(csrc/conv3d_wgrad_dilated.hip)")
+    ap.add_argument("--conv-dilated-f16", action="store_true",
+                    help="with --conv-dilated m3d: forward and dgrad of the dilation-2 convs on maps at most 8 wide on the f16 matrix cores at "
+                         "fp32 accuracy (m3d.compat.set_conv_dilated_f16)")
     ap.add_argument("--box-head", choices=("mlp", "conv"), default="mlp",
                     help="mlp = RoIAlign -> two FC layers (roi_2mlp_head); conv = m3d.ConvBoxHead (roi_Xconv1fc_head)")
     ap.add_argument("--conv-head-dim", type=int, default=128, help="with --box-head conv: FAST_RCNN.CONV_HEAD_DIM (the nuclei YAML has 128)")
@@ -98,6 +103,8 @@ def main():
     a = ap.parse_args()
     if a.mask_dilation != 1 and not a.mask:
         ap.error("--mask-dilation needs --mask")
+    if a.conv_dilated_f16 and a.conv_dilated != "m3d":
+        ap.error("--conv-dilated-f16 needs --conv-dilated m3d")
     import torch
     import m3d
     import m3d.compat
@@ -113,6 +120,7 @@ def main():
     m3d.compat.set_roi_align_backward(a.roi_backward)
     m3d.compat.set_upconv(a.upconv)
     m3d.compat.set_conv_dilated(a.conv_dilated)
+    m3d.compat.set_conv_dilated_f16(a.conv_dilated_f16)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
