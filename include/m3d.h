@@ -382,6 +382,27 @@ int m3d_conv3d_wgrad_narrow_f16x2_plan(int batch, int cin, int cout, int depth, 
 int m3d_conv3d_wgrad_narrow_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
                                   int depth, int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws,
                                   size_t ws_bytes, void* stream);
+/* m3d_conv3d_wgrad_narrow_f16x2 with a dilation (the second instantiation of the same kernel): `dilation` 1 is that call, bit for bit;
+ * `dilation` 2 is the weight gradient of the k = 3, dilation 2, padding 2 convs (the mask head at MRCNN.DILATION = 2 on 7^3 RoI grids),
+ *   dW[co,ci,dz,dy,dx] = sum_{b,z,y,x} gy[b,co,z,y,x] * x[b,ci,z+2(dz-1),y+2(dy-1),x+2(dx-1)]   (zeros outside the map)
+ * with the same cut, contract, tile, slot rule and reduce launch.  The halo image of x grows to 6 x 12 rows (92,160 bytes of LDS, one
+ * workgroup per CU); the +-2 shift along x is a move of whole dwords in registers with a zero dword shifted in, since x = -2, -1, 8 and
+ * 9 are outside every map this kernel takes.  The number of MFMAs per tile does not depend on the dilation: _plan reports the tile_z,
+ * slots, tiles_per_slot, chain and folds of m3d_conv3d_wgrad_narrow_f16x2_plan for the same shape, and workspace_bytes is the same
+ * slots * 27 * cin * cout * 4.
+ *   supported   dilation 1 or 2 and what m3d_conv3d_wgrad_narrow_f16x2_supported takes (width <= 8, cin and cout multiples of 32 and at
+ *               most 4096, the same tile-count and workgroup-count limits).  Any other dilation is unsupported (workspace_bytes 0).
+ * Refusals, before any pointer is followed or anything is launched, in the order of the dilation-1 entry.  M3D_EINVAL: a NULL pointer, a
+ * float pointer that is not 4-byte aligned, a d_ws that is not 16-byte aligned, a non-positive extent, dilation < 1, ws_bytes below
+ * workspace_bytes.  M3D_EUNSUPPORTED: whatever `supported` rejects, dilation > 2 among it. */
+int m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width, int dilation);
+size_t m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width,
+                                                             int dilation);
+int m3d_conv3d_wgrad_narrow_dilated_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int dilation, int* tile_z,
+                                               int* slots, int* tiles_per_slot, int* chain, int* folds);
+int m3d_conv3d_wgrad_narrow_dilated_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                          int depth, int height, int width, int dilation, const float* d_in_max, const float* d_gy_max,
+                                          void* d_ws, size_t ws_bytes, void* stream);
 /* One pass over a conv layer's output gradient d_gy [batch, cout, depth, height, width] (csrc/conv3d_gy_reduce.hip) for the bias gradient
  * and the operand bound the f16x2 dgrad (m3d_conv3d_zw_forward on an m3d_conv3d_zw_pack_dgrad pack) and m3d_conv3d_wgrad_f16x2 take:
  *   d_grad_bias  (or NULL) [cout]: gb[c] = fp32(S), S = the sum of d_gy[:, c] taken in fp64 over spans of one (image, channel) slab whose

@@ -208,6 +208,7 @@ def _packed(weight, mode):
 _setting = conv_plan.TrainSetting()          # what the setters below say; WHEN each field is read: the TrainSetting docstring
 _wgrad_narrow_f16 = None                     # set_conv_wgrad_narrow_f16: None (off) or its threshold; beside _setting, whose fields are pinned
 _dilated_f16 = None                          # set_conv_dilated_f16: None (off) or its threshold in launch units; beside _setting too
+_wgrad_dilated_f16 = None                    # set_conv_wgrad_dilated_f16: None (off) or its threshold in products per tap; beside _setting too
 
 
 def set_conv_wgrad(mode):
@@ -353,6 +354,28 @@ def get_conv_dilated_f16():
     return _dilated_f16 is not None
 
 
+def set_conv_wgrad_dilated_f16(on, min_work=None):
+    """The weight gradient of the dilation-2 convs that set_conv_dilated("m3d") routes to the library, on maps at most 8 wide with channel
+    counts that are multiples of 32 (train.MaskHead at MRCNN.DILATION = 2 on 7^3 RoI grids): False (the default; install() does not
+    change it) keeps m3d_conv3d_wgrad_dilated, the fp32 kernel; True takes m3d_conv3d_wgrad_narrow_dilated_f16x2 (the f16 matrix cores
+    at fp32 accuracy on the 2 x 8 x 8 tile, dilation 2) for the layers conv_plan.plan_train_conv(wgrad_dilated_f16=) routes to it.  x's
+    bound comes from the forward and gy's from m3d_conv3d_gy_reduce where set_conv_dilated_f16 ran them, else the kernel's wrapper
+    sweeps; forward, dgrad and the bias gradient are the same with the switch on or off.  Without set_conv_dilated("m3d") it has no
+    effect.  min_work: the routing threshold in products per tap, batch D H W cin cout (None:
+    conv_plan.WGRAD_DILATED_F16X2_MIN_WORK; 0 routes every supported layer - tests and A/B runs; a call without it puts the default
+    back).  Read when the backward runs.  Returns the previous setting (True / False)."""
+    global _wgrad_dilated_f16
+    if min_work is not None and int(min_work) < 0:
+        raise ValueError("set_conv_wgrad_dilated_f16(min_work=%r): None or a count >= 0" % (min_work,))
+    prev = _wgrad_dilated_f16 is not None
+    _wgrad_dilated_f16 = (conv_plan.WGRAD_DILATED_F16X2_MIN_WORK if min_work is None else int(min_work)) if on else None
+    return prev
+
+
+def get_conv_wgrad_dilated_f16():
+    return _wgrad_dilated_f16 is not None
+
+
 class _Conv3dFn(torch.autograd.Function):
     """A conv that conv3d() routes to the library (dilation 1 or 2): runs conv_plan.plan_train_conv's plan, the forward half in
     forward, the backward half in backward.  Nothing is decided here."""
@@ -383,7 +406,7 @@ class _Conv3dFn(torch.autograd.Function):
         setting = ctx.setting._replace(wgrad=_setting.wgrad, wgrad_narrow=_setting.wgrad_narrow)
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
         dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs,
-                                                                         _wgrad_narrow_f16, ctx.dilated_f16)
+                                                                         _wgrad_narrow_f16, ctx.dilated_f16, _wgrad_dilated_f16)
         gx = gw = gb = gy_max = None
         if gy_reduce:
             gb, gy_max = ops.conv3d_gy_reduce(gy, bias=gb_from == conv_plan.GB_REDUCE)
@@ -414,10 +437,11 @@ class _Conv3dFn(torch.autograd.Function):
         elif wgrad == conv_plan.WGRAD_FP32:
             gw = ops.conv3d_wgrad(x, gy, weight.shape[2])
         else:
-            # the kinds left: None (gw not needed) and WGRAD_NARROW_F16X2, with the bounds WGRAD_F16X2 takes.  (An else, since the count of
+            # the kinds left: None (gw not needed), WGRAD_NARROW_F16X2 and WGRAD_DILATED_F16X2 - one kernel at the call's dilation (1: the
+            # wrapper makes the calls it made without the keyword), with the bounds WGRAD_F16X2 takes.  (An else, since the count of
             # branches of this function is pinned: tests/test_conv_train_dispatch.py::test_backward_has_no_routing_left)
-            assert wgrad in (None, conv_plan.WGRAD_NARROW_F16X2), wgrad
-            gw = None if wgrad is None else ops.conv3d_wgrad_narrow_f16x2(x, gy, ctx.x_max, gy_max)
+            assert (wgrad, ctx.dilation) in ((None, 1), (None, 2), (conv_plan.WGRAD_NARROW_F16X2, 1), (conv_plan.WGRAD_DILATED_F16X2, 2)), wgrad
+            gw = None if wgrad is None else ops.conv3d_wgrad_narrow_f16x2(x, gy, ctx.x_max, gy_max, dilation=ctx.dilation)
 
         if gb_from == conv_plan.GB_BIAS_GRAD:
             gb = ops.conv3d_bias_grad(gy)

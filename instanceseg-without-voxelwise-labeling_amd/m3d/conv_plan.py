@@ -146,6 +146,14 @@ TRAIN_DILATED_F16X2 = "f16x2 dilated"
 # count of the smallest launch of profiles/conv_narrow_f16_dilated.txt that beat m3d_conv3d_forward_dilated by more than the sum of the
 # spreads, sweep / gy_reduce and the per-step pack inside the window.  Nothing below a measured win routes.
 ZN_DILATED_MIN_UNITS = 128
+# wgrad kind: the dilation-2 instantiation of the narrow f16x2 wgrad kernel (m3d_conv3d_wgrad_narrow_dilated_f16x2): maps at most 8 wide,
+# cin and cout multiples of 32, under DILATED_M3D, opt-in (compat.set_conv_wgrad_dilated_f16)
+WGRAD_DILATED_F16X2 = "f16x2 dilated"
+# Its routing threshold in products per tap, batch x voxels x cin x cout, as WGRAD_NARROW_F16X2_MIN_WORK is: the work of the smallest
+# shape measured to beat m3d_conv3d_wgrad_dilated by more than the sum of the spreads, both operand sweeps inside the window
+# (profiles/conv_wgrad_dilated_f16.txt: 256 -> 256 on 7^3 at R = 4, 4 x 343 x 256 x 256, 0.259 -> 0.101 ms, 2.56 x); all six larger
+# measured shapes win too (2.66 x .. 3.12 x).  Nothing smaller was measured: below it nothing routes.
+WGRAD_DILATED_F16X2_MIN_WORK = 4 * 343 * 256 * 256
 
 
 class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narrow wgrad wgrad_narrow dilated",
@@ -163,13 +171,14 @@ class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narro
     The field list is pinned (tests/test_conv_train_dispatch.py compares _asdict() of the defaults), so the one later switch,
     set_conv_wgrad_narrow_f16, travels beside the setting: the wgrad_narrow_f16 argument of plan_train_backward / plan_train_conv,
     read when the backward runs as the other two wgrad switches are.  set_conv_dilated_f16 travels the same way (the dilated_f16
-    argument of the three plan functions), read at FORWARD time: the backward follows the forward's value, as it does for dilated."""
+    argument of the three plan functions), read at FORWARD time: the backward follows the forward's value, as it does for dilated.
+    set_conv_wgrad_dilated_f16 is the wgrad_dilated_f16 argument of plan_train_backward / plan_train_conv, read when the BACKWARD runs."""
     __slots__ = ()
 
 
 # forward: TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED / TRAIN_DILATED_F16X2; sweep: the forward sweeps x for its operand bound and keeps it
 # (for the f16x2 wgrad); dgrad: None (gx not needed) / DGRAD_STEM / TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED / TRAIN_DILATED_F16X2;
-# wgrad: None (gw not needed) / WGRAD_FP32 / WGRAD_F16X2 / WGRAD_NARROW / WGRAD_NARROW_F16X2 / WGRAD_DILATED; gy_reduce: m3d_conv3d_gy_reduce runs first (one
+# wgrad: None (gw not needed) / WGRAD_FP32 / WGRAD_F16X2 / WGRAD_NARROW / WGRAD_NARROW_F16X2 / WGRAD_DILATED / WGRAD_DILATED_F16X2; gy_reduce: m3d_conv3d_gy_reduce runs first (one
 # pass over gy: its operand bound, and the bias gradient where needed); gb: None / GB_REDUCE / GB_BIAS_GRAD
 TrainConvPlan = collections.namedtuple("TrainConvPlan", "forward sweep dgrad wgrad gy_reduce gb")
 
@@ -213,15 +222,31 @@ def plan_train_forward(setting, xshape, wshape, dilation, dilated_f16=None):
     return forward, forward != TRAIN_FP32
 
 
-def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None):
+def _wgrad_dilated_rule(setting, xshape, wshape, wgrad_dilated_f16):
+    """the wgrad kind of a dilation-2 layer: WGRAD_DILATED_F16X2 where the switch is on (wgrad_dilated_f16: its threshold in products per
+    tap) under DILATED_M3D, k = 3, m3d_conv3d_wgrad_narrow_dilated_f16x2_supported takes the shape at dilation 2 and the work reaches the
+    threshold, else WGRAD_DILATED.  With wgrad_dilated_f16 None no library query is made."""
+    if wgrad_dilated_f16 is None or setting.dilated != DILATED_M3D or int(wshape[2]) != 3:
+        return WGRAD_DILATED
+    B, _, D, H, W = (int(v) for v in xshape)
+    cout, cin = int(wshape[0]), int(wshape[1])
+    if ops.conv3d_wgrad_narrow_f16x2_supported(B, cin, cout, D, H, W, dilation=2) and B * D * H * W * cin * cout >= int(wgrad_dilated_f16):
+        return WGRAD_DILATED_F16X2
+    return WGRAD_DILATED
+
+
+def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None, wgrad_dilated_f16=None):
     """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs.  wgrad_narrow_f16: None (the narrow f16x2
     wgrad kernel is off), else its routing threshold in products per tap (compat.set_conv_wgrad_narrow_f16); dilated_f16: as
-    plan_train_forward's"""
+    plan_train_forward's; wgrad_dilated_f16: None (the dilation-2 f16x2 wgrad kernel is off: the result is what it was without the
+    argument, and no further library query is made), else its routing threshold in products per tap (compat.set_conv_wgrad_dilated_f16)"""
     gx, gw, gb = (bool(v) for v in needs)
-    if dilation == 2:                                  # train and wgrad do not reach these layers; the weight gradient is always fp32
+    if dilation == 2:                                  # train, wgrad and wgrad_narrow_f16 do not reach these layers
         dgrad = _dilated_rule("dgrad", setting, xshape, wshape, dilated_f16) if gx else None
         gy_reduce = dgrad == TRAIN_DILATED_F16X2       # gy's bound, and then the bias gradient too: the rule of TRAIN_F16X2_NARROW
-        return dgrad, (WGRAD_DILATED if gw else None), gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
+        # WGRAD_DILATED_F16X2 asks for nothing, as WGRAD_NARROW_F16X2 does not: it takes gy's bound where the pass ran and sweeps otherwise
+        wgrad = _wgrad_dilated_rule(setting, xshape, wshape, wgrad_dilated_f16) if gw else None
+        return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
     B, _, D, H, W = xshape
     cout, cin, k = wshape[:3]
     dgrad = None if not gx else DGRAD_STEM if k == 5 else _train_rule("dgrad", setting, xshape, wshape)
@@ -238,7 +263,7 @@ def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f
     return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
 
 
-def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None):
+def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None, wgrad_dilated_f16=None):
     """What a training conv that m3d.compat.conv3d routes to the library launches, forward and backward: a TrainConvPlan.  The only place
     that combines the rules (train_conv_kernel and wgrad_kernel are its rows); host queries of the library only, a function of its
     arguments only.  setting: a TrainSetting; xshape [B, cin, D, H, W]; wshape [cout, cin, k, k, k]; dilation: 1 (stride 1, padding
@@ -247,7 +272,9 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=N
     compat.set_conv_wgrad_narrow_f16 (it moves the wgrad field only: gy_reduce and gb do not depend on it); dilated_f16: None or the
     threshold in launch units of compat.set_conv_dilated_f16 (it moves dilation-2 layers under DILATED_M3D only).  "dilated f16x2
     takes": dilated_f16 is a threshold, setting.dilated is DILATED_M3D, m3d_conv3d_zn_dilated_supported takes the LAUNCHED conv at
-    dilation 2 (a dgrad swaps the channel roles) and m3d_conv3d_zn_dilated_launch_units reaches the threshold.
+    dilation 2 (a dgrad swaps the channel roles) and m3d_conv3d_zn_dilated_launch_units reaches the threshold.  wgrad_dilated_f16: None
+    or the threshold in products per tap of compat.set_conv_wgrad_dilated_f16 (it moves the wgrad field of dilation-2 layers under
+    DILATED_M3D only: gy_reduce and gb do not depend on it, and wgrad_narrow_f16 keeps not touching these layers).
 
     | field     | value              | condition                                                                                      |
     | forward   | TRAIN_DILATED_F16X2| dilation 2 and dilated f16x2 takes the forward conv                                            |
@@ -260,7 +287,9 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=N
     |           | DGRAD_STEM         | k = 5                                                                                          |
     |           | else               | train_conv_kernel("dgrad", ...)                                                                |
     | wgrad     | None               | gw not needed                                                                                  |
-    |           | WGRAD_DILATED      | dilation 2                                                                                     |
+    |           | WGRAD_DILATED_F16X2| dilation 2, wgrad_dilated_f16 is a threshold, DILATED_M3D, k = 3,                              |
+    |           |                    | m3d_conv3d_wgrad_narrow_dilated_f16x2_supported at dilation 2, work >= it                      |
+    |           | WGRAD_DILATED      | dilation 2 otherwise                                                                           |
     |           | WGRAD_NARROW_F16X2 | wgrad_narrow_f16 is a threshold, k = 3, m3d_conv3d_wgrad_narrow_f16x2_supported, work >= it    |
     |           | else               | wgrad_kernel(...) under setting.wgrad / wgrad_narrow                                           |
     | gy_reduce | True               | dilation 1 and: train is f16x2 and (dgrad or wgrad is f16x2, or gb needed); or dgrad is narrow |
@@ -272,7 +301,8 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=N
     compat asks the two halves when it needs them (plan_train_forward in forward, plan_train_backward in backward): a call makes the
     library queries of the directions it runs and no others."""
     return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation, dilated_f16)
-                           + plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16, dilated_f16)))
+                           + plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16, dilated_f16,
+                                                 wgrad_dilated_f16)))
 
 
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True, narrow_f16=False):

@@ -2019,25 +2019,34 @@ def conv3d_wgrad_f16x2(x, grad_out, x_max=None, gy_max=None):
     return dw
 
 
-def conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, D, H, W):
+def conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, D, H, W, dilation=1):
     """m3d_conv3d_wgrad_narrow_f16x2_supported (host only): the k = 3 weight gradient of this shape runs on the f16 matrix cores on the
-    2 x 8 x 8 voxel tile (W <= 8, cin and cout multiples of 32)"""
-    return bool(lib().m3d_conv3d_wgrad_narrow_f16x2_supported(int(batch), int(cin), int(cout), int(D), int(H), int(W)))
+    2 x 8 x 8 voxel tile (W <= 8, cin and cout multiples of 32).  dilation: 1 (left out: that query) or another one, asked of
+    m3d_conv3d_wgrad_narrow_dilated_f16x2_supported (which takes 1 and 2)"""
+    if dilation == 1:
+        return bool(lib().m3d_conv3d_wgrad_narrow_f16x2_supported(int(batch), int(cin), int(cout), int(D), int(H), int(W)))
+    return bool(lib().m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(int(batch), int(cin), int(cout), int(D), int(H), int(W), int(dilation)))
 
 
-def conv3d_wgrad_narrow_f16x2_plan(batch, cin, cout, D, H, W):
-    """The host decision of the launch (m3d_conv3d_wgrad_narrow_f16x2_plan): dict(tile_z, slots, tiles_per_slot, chain, folds)"""
+def conv3d_wgrad_narrow_f16x2_plan(batch, cin, cout, D, H, W, dilation=1):
+    """The host decision of the launch (m3d_conv3d_wgrad_narrow_f16x2_plan; with a dilation other than 1
+    m3d_conv3d_wgrad_narrow_dilated_f16x2_plan): dict(tile_z, slots, tiles_per_slot, chain, folds)"""
     v = [C.c_int(0) for _ in range(5)]
-    check(lib().m3d_conv3d_wgrad_narrow_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), *[C.byref(a) for a in v]),
-          "conv3d_wgrad_narrow_f16x2_plan")
+    if dilation == 1:
+        check(lib().m3d_conv3d_wgrad_narrow_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), *[C.byref(a) for a in v]),
+              "conv3d_wgrad_narrow_f16x2_plan")
+    else:
+        check(lib().m3d_conv3d_wgrad_narrow_dilated_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), int(dilation),
+                                                               *[C.byref(a) for a in v]), "conv3d_wgrad_narrow_dilated_f16x2_plan")
     return dict(zip(("tile_z", "slots", "tiles_per_slot", "chain", "folds"), (a.value for a in v)))
 
 
-def conv3d_wgrad_narrow_f16x2(x, grad_out, x_max=None, gy_max=None):
+def conv3d_wgrad_narrow_f16x2(x, grad_out, x_max=None, gy_max=None, dilation=1):
     """conv3d_wgrad_f16x2 for maps at most 8 wide (m3d_conv3d_wgrad_narrow_f16x2: the same cut on the 2 x 8 x 8 voxel tile): x
     [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA) -> dW [cout,cin,3,3,3].  x_max / gy_max: [ZwConv3d.SLOTS] device floats whose
-    largest bounds |x| / |grad_out|; a missing one is swept (ZwConv3d.bound_of).  An unsupported shape is an error: ask
-    conv3d_wgrad_narrow_f16x2_supported (or conv_plan.wgrad_kernel)."""
+    largest bounds |x| / |grad_out|; a missing one is swept (ZwConv3d.bound_of).  dilation: 1 (left out: the calls above), or 2: the
+    weight gradient of the dilation-2, padding-2 conv (m3d_conv3d_wgrad_narrow_dilated_f16x2).  An unsupported shape or dilation is an
+    error: ask conv3d_wgrad_narrow_f16x2_supported (or conv_plan.plan_train_conv)."""
     _need_gpu(x, grad_out, x_max, gy_max)
     x, grad_out = _f32c(x), _f32c(grad_out)
     B, cin, D, H, W = x.shape
@@ -2049,10 +2058,17 @@ def conv3d_wgrad_narrow_f16x2(x, grad_out, x_max=None, gy_max=None):
         gy_max = ZwConv3d.bound_of(grad_out)
     assert x_max.numel() == ZwConv3d.SLOTS and gy_max.numel() == ZwConv3d.SLOTS and x_max.dtype == gy_max.dtype == torch.float32
     dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    wsb = lib().m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(B, cin, cout, D, H, W)
+    if dilation == 1:
+        wsb = lib().m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(B, cin, cout, D, H, W)
+        ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
+        check(lib().m3d_conv3d_wgrad_narrow_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, _ptr(x_max), _ptr(gy_max),
+                                                  _ptr(ws), C.c_size_t(wsb), _stream()), "conv3d_wgrad_narrow_f16x2")
+        return dw
+    wsb = lib().m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes(B, cin, cout, D, H, W, int(dilation))
     ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
-    check(lib().m3d_conv3d_wgrad_narrow_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, _ptr(x_max), _ptr(gy_max),
-                                              _ptr(ws), C.c_size_t(wsb), _stream()), "conv3d_wgrad_narrow_f16x2")
+    check(lib().m3d_conv3d_wgrad_narrow_dilated_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, int(dilation), _ptr(x_max),
+                                                      _ptr(gy_max), _ptr(ws), C.c_size_t(wsb), _stream()),
+          "conv3d_wgrad_narrow_dilated_f16x2")
     return dw
 
 

@@ -12,7 +12,10 @@ Prints all four losses per step.  One fixed sample; this is not a training drive
 the spheres inscribed in the synthetic boxes, m3d.mask_losses; loss_mask joins the printed line and the sum.  --mask-dilation 2 builds that head with MRCNN.DILATION = 2 (the reference's
 default; both shipped YAMLs set 1), and --conv-dilated m3d runs its dilated convs on the library, forward and backward;
 --conv-dilated-f16 (with --conv-dilated m3d) runs their forward and backward-data pass on the dilation-2 instantiation of the
-narrow-map f16x2 kernel (m3d.compat.set_conv_dilated_f16, csrc/conv3d_zn.hip: launches of at least conv_plan.ZN_DILATED_MIN_UNITS units).
+narrow-map f16x2 kernel (m3d.compat.set_conv_dilated_f16, csrc/conv3d_zn.hip: launches of at least conv_plan.ZN_DILATED_MIN_UNITS units);
+--wgrad-dilated-f16 (with --mask spot --mask-dilation 2 --conv-dilated m3d) runs their weight gradient on the dilation-2 instantiation
+of the narrow-map f16x2 wgrad kernel (m3d.compat.set_conv_wgrad_dilated_f16, csrc/conv3d_wgrad_narrow_f16.hip: layers of at least
+conv_plan.WGRAD_DILATED_F16X2_MIN_WORK products per tap).
 
 --box-head conv (default mlp, whose output stays as it is) trains m3d.ConvBoxHead (roi_Xconv1fc_head, fast_rcnn_heads.py:120-179:
 --conv-head-convs 3^3 convs of --conv-head-dim channels on the 7^3 grids, then one FC layer of --hidden) in place of the two-FC head;
@@ -100,11 +103,16 @@ def main():
     ap.add_argument("--wgrad-narrow-f16", action="store_true",
                     help="weight gradients of those convs (cin and cout multiples of 32) on the f16 matrix cores at fp32 accuracy on the "
                          "2 x 8 x 8 tile (m3d.compat.set_conv_wgrad_narrow_f16)")
+    ap.add_argument("--wgrad-dilated-f16", action="store_true",
+                    help="with --mask spot --mask-dilation 2 --conv-dilated m3d: weight gradients of the dilation-2 convs on maps at most 8 "
+                         "wide (cin and cout multiples of 32) on the f16 matrix cores at fp32 accuracy (m3d.compat.set_conv_wgrad_dilated_f16)")
     a = ap.parse_args()
     if a.mask_dilation != 1 and not a.mask:
         ap.error("--mask-dilation needs --mask")
     if a.conv_dilated_f16 and a.conv_dilated != "m3d":
         ap.error("--conv-dilated-f16 needs --conv-dilated m3d")
+    if a.wgrad_dilated_f16 and not (a.mask == "spot" and a.mask_dilation == 2 and a.conv_dilated == "m3d"):
+        ap.error("--wgrad-dilated-f16 needs --mask spot --mask-dilation 2 --conv-dilated m3d")
     import torch
     import m3d
     import m3d.compat
@@ -121,6 +129,7 @@ def main():
     m3d.compat.set_upconv(a.upconv)
     m3d.compat.set_conv_dilated(a.conv_dilated)
     m3d.compat.set_conv_dilated_f16(a.conv_dilated_f16)
+    m3d.compat.set_conv_wgrad_dilated_f16(a.wgrad_dilated_f16)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
