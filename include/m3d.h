@@ -1490,6 +1490,35 @@ size_t m3d_upconv3d_2x_wgrad_workspace_bytes(int R, int Cin, int Cout, int D, in
 int m3d_upconv3d_2x_wgrad(const float* d_gy, const float* d_y_mask, const float* d_x, float* d_gw, float* d_gb, int R, int Cin, int Cout,
                           int D, int H, int W, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The up-conv's FORWARD on the f16 matrix cores at fp32 accuracy, and the mask head's tail in one launch (upconv3d_f16.hip; DESIGN,
+ * "Mask-head tail on the f16 pipe").  The f16x2 cut of the ZnConv3d kernels: x and the weight scaled by the power of two of their
+ * bounds, cut into hi + lo fp16, three f16 MFMA products per fp32 product, fp32 accumulation, exact un-scaling.  x is cut while it is
+ * staged from the fp32 tensor; the weight by the pack call, once: m3d_upconv3d_2x_f16x2_packed_bytes(Cin, Cout) bytes (0: refused)
+ * that hold the fragments and, behind them, fl(max|W|) computed on the device (no host read, no atomics).
+ *   m3d_upconv3d_2x_forward_f16x2  d_y [R,Cout,2D,2H,2W] as m3d_upconv3d_2x_forward writes it (bias, optional ReLU)
+ *   m3d_mask_tail_f16x2            d_out[r,k,2z+a,2y+b,2x+c] = act(d_cls_bias[k] + sum_co d_cls_weight[k,co] max(y[r,co,..], 0)), y the
+ *                                  up-conv with d_up_bias; d_cls_weight [K,Cout], 1 <= K <= 8; act = identity (sigmoid 0) or the device
+ *                                  sigmoid of m3d_conv3d_forward_split_sigmoid (sigmoid 1: bit-equal to torch.sigmoid of the sigmoid-0
+ *                                  output).  The [R,Cout,2D,2H,2W] tensor is never written; no workspace.
+ * d_in_max: the [m3d_conv3d_zw_slots()] device floats whose largest bounds max|x| (what the conv before left, or
+ * m3d_conv3d_zw_bound_of).  No atomics, every output element written by the call, bit-identical run to run, no scratch; an Inf / NaN
+ * operand gives NaN, never a finite number.  Error bounds per element: tests/upconv_f16_cases.py (c1 = 3.01, n_acc = 3 Cin / 16,
+ * m = Cout + 2).
+ * m3d_upconv3d_2x_f16x2_supported (host only): Cin % 16 == 0, Cout, D, H, W >= 1, R >= 0, and x, y and the padded pack below 2^31
+ * elements.  Refusals, all before a pointer is followed: M3D_EINVAL for R < 0 or Cin, Cout, D, H or W < 1, a NULL required pointer, a
+ * pointer that is not 4-byte aligned; M3D_EUNSUPPORTED for a shape _supported refuses, K outside 1..8, the tail's output of 2^31
+ * elements or more, d_packed not 16-byte or the output not 8-byte aligned.  R == 0 does nothing (no pointer is looked at).
+ * ------------------------------------------------------------------------------------------------------- */
+int m3d_upconv3d_2x_f16x2_supported(int R, int Cin, int Cout, int D, int H, int W);
+size_t m3d_upconv3d_2x_f16x2_packed_bytes(int Cin, int Cout);
+int m3d_upconv3d_2x_f16x2_pack(const float* d_weight, int Cin, int Cout, void* d_packed, void* stream);
+int m3d_upconv3d_2x_forward_f16x2(const float* d_x, const void* d_packed, const float* d_bias, float* d_y, int R, int Cin, int Cout, int D,
+                                  int H, int W, int relu, const float* d_in_max, void* stream);
+int m3d_mask_tail_f16x2(const float* d_x, const void* d_packed, const float* d_up_bias, const float* d_cls_weight, const float* d_cls_bias,
+                        float* d_out, int R, int Cin, int Cout, int K, int D, int H, int W, int sigmoid, const float* d_in_max,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

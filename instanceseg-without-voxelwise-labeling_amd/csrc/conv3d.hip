@@ -145,7 +145,7 @@ __device__ inline void store_block(const Epilogue& ep, float* __restrict__ out, 
       if (co < cout) {
         float v = a[g] * A.sc[g] + A.sh[g];
         if (ep.relu) v = fmaxf(v, 0.f);
-        if (co < ep.split_at) out[((size_t)b * ep.split_at + co) * DHW + sp] = 1.f / (1.f + expf(-v));      // torch.sigmoid's own formula
+        if (co < ep.split_at) out[((size_t)b * ep.split_at + co) * DHW + sp] = m3d::sigmoid_f32(v);           // torch.sigmoid's own formula
         else ep.out2[((size_t)b * (cout - ep.split_at) + (co - ep.split_at)) * DHW + sp] = v;
       }
     }

@@ -54,4 +54,6 @@ __device__ __forceinline__ void f16_scale_of(float bound, float& s, float& inv) 
   s = __uint_as_float((unsigned)f << 23);
   inv = __uint_as_float((unsigned)(254 - f) << 23);
 }
+// torch.sigmoid's own formula (tests/test_gpu_ops.py holds it bit-equal): the one device sigmoid of the library
+__device__ __forceinline__ float sigmoid_f32(float v) { return 1.f / (1.f + expf(-v)); }
 }  // namespace m3d

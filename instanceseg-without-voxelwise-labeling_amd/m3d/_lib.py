@@ -54,6 +54,8 @@ SYMBOLS = [
     "m3d_conv3d_zn_supported", "m3d_conv3d_zn_packed_bytes", "m3d_conv3d_zn_pack", "m3d_conv3d_zn_pack_dgrad", "m3d_conv3d_zn_launch_units",
     "m3d_conv3d_zn_forward",
     "m3d_conv3d_zn_dilated_supported", "m3d_conv3d_zn_dilated_launch_units", "m3d_conv3d_zn_dilated_forward",
+    "m3d_upconv3d_2x_f16x2_supported", "m3d_upconv3d_2x_f16x2_packed_bytes", "m3d_upconv3d_2x_f16x2_pack", "m3d_upconv3d_2x_forward_f16x2",
+    "m3d_mask_tail_f16x2",
 ]
 
 
@@ -133,7 +135,8 @@ def _load(path):
               "m3d_mask_loss_workspace_bytes", "m3d_conv3d_wgrad_f16x2_workspace_bytes", "m3d_peak_stimulation3d_workspace_bytes",
               "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes",
               "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_narrow_workspace_bytes", "m3d_conv3d_zn_packed_bytes",
-              "m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes", "m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes"):
+              "m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes", "m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes",
+              "m3d_upconv3d_2x_f16x2_packed_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

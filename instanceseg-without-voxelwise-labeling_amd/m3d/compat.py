@@ -184,6 +184,7 @@ _PACKS = {                # pack kind -> constructor from the detached weight
     "stem-dgrad": ops.conv3d_stem5_dgrad_weights,            # tap-flipped [C,125] weights of the 5^3 / Cin = 1 stem's backward-data
     "zw-plain": ops.ZwConv3d, "zw-dgrad": ops.ZwConv3d.dgrad_of,       # the f16x2 kernel (set_conv_train)
     "zn-plain": ops.ZnConv3d, "zn-dgrad": ops.ZnConv3d.dgrad_of,       # the narrow-map f16x2 kernel (set_conv_train_narrow)
+    "upconv-f16": ops.UpConvF16,                             # the up-conv's f16x2 forward (set_upconv_f16)
 }
 
 
@@ -632,6 +633,24 @@ def set_upconv(mode):
 
 def get_upconv():
     return _upconv
+
+
+_upconv_f16 = False
+
+
+def set_upconv_f16(on):
+    """The FORWARD of m3d.upconv3d_2x (train.MaskHead under set_upconv("m3d")) on the f16 matrix cores (ops.UpConvF16, csrc/upconv3d_f16.hip:
+    the f16x2 cut at fp32 accuracy, one bound sweep of x per call, the pack served through the pack cache) where the kernel takes the
+    shape (Cin % 16 == 0); the backward stays on m3d_upconv3d_2x_dgrad / _wgrad, which take the ReLU mask from the saved output whichever
+    kernel wrote it.  Off by default, install() does not touch it, and it has no effect without set_upconv("m3d").  Returns the
+    previous setting."""
+    global _upconv_f16
+    prev, _upconv_f16 = _upconv_f16, bool(on)
+    return prev
+
+
+def get_upconv_f16():
+    return _upconv_f16
 
 
 def _upconv_qualifies(x, weight, bias, stride, padding, output_padding, groups, dilation):

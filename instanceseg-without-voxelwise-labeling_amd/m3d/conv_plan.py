@@ -146,6 +146,12 @@ TRAIN_DILATED_F16X2 = "f16x2 dilated"
 # count of the smallest launch of profiles/conv_narrow_f16_dilated.txt that beat m3d_conv3d_forward_dilated by more than the sum of the
 # spreads, sweep / gy_reduce and the per-step pack inside the window.  Nothing below a measured win routes.
 ZN_DILATED_MIN_UNITS = 128
+# The mask head's tail (up-conv + ReLU + classifier + sigmoid) as ONE f16x2 launch (ops.UpConvF16.tail, csrc/upconv3d_f16.hip), opt-in
+# (MaskHeadM3D(tail_f16=) / M3D_MASK_TAIL_F16).  Its routing threshold in RoIs: the smallest RoI count of profiles/mask_tail_f16.txt
+# (256 -> 256 channels, 7^3 -> 14^3, K = 2) at which the fused call, its own bound sweep inside the window, beat the fp32 up-conv +
+# classify conv + torch.sigmoid by more than the sum of the spreads (16 is the smallest count measured: x1.20 with the sweep, x1.47
+# without).  Smaller launches do not route.
+MASK_TAIL_F16_MIN_ROIS = 16
 # wgrad kind: the dilation-2 instantiation of the narrow f16x2 wgrad kernel (m3d_conv3d_wgrad_narrow_dilated_f16x2): maps at most 8 wide,
 # cin and cout multiples of 32, under DILATED_M3D, opt-in (compat.set_conv_wgrad_dilated_f16)
 WGRAD_DILATED_F16X2 = "f16x2 dilated"

@@ -13,7 +13,10 @@ Every convolution runs in the HIP library:
   * ConvTranspose3d(kernel 2, stride 2) never overlaps its outputs, so it is a 1x1x1 conv to 8*Cout channels
     (one per output parity (a,b,c)) followed by a voxel shuffle to the 2x grid; bias + ReLU ride in the conv epilogue.
     Under compat.set_upconv("m3d") it is one m3d_upconv3d_2x_forward instead, whose epilogue writes the 2x grid directly;
-  * the 1x1x1 classifier through m3d_conv3d_forward."""
+  * the 1x1x1 classifier through m3d_conv3d_forward;
+  * with tail_f16 / M3D_MASK_TAIL_F16 (opt-in) `mask_net` runs trunk -> ONE launch for up-conv + ReLU + classifier + sigmoid
+    (ops.UpConvF16.tail, csrc/upconv3d_f16.hip: the f16x2 cut on the f16 matrix cores); the [R, C, 2M', 2M', 2M'] tensor is never
+    written.  `up` and `outputs` stay what they are for callers that use them directly."""
 import os
 
 import numpy as np
@@ -24,7 +27,7 @@ from . import conv_plan, ops
 
 class MaskHeadM3D:
     def __init__(self, params, cfg, resolution=None, roi_res=None, sampling_ratio=None, dilation=None, cls_specific=None, conv_f16=None,
-                 conv_f16_min_units=None):
+                 conv_f16_min_units=None, tail_f16=None, tail_f16_min_rois=None):
         """params: CUDA fp32 tensors under the reference's state-dict keys `Mask_Head.conv_fcn.{0,2,..}.{weight,bias}`,
         `Mask_Head.upconv.{weight,bias}`, `Mask_Outs.classify.{weight,bias}`.  The MRCNN.* settings come from cfg
         (Cfg.from_yaml reads them; defaults = lib/core/config.py:751-780) unless given here.
@@ -32,6 +35,11 @@ class MaskHeadM3D:
         layer: cin % 16 == 0, a RoI grid at most 8 wide, and a launch of at least conv_f16_min_units units (None: the measured routing
         threshold of the dilation, conv_plan.ZN_MIN_UNITS / ZN_DILATED_MIN_UNITS; 0 routes every supported launch - tests and A/B runs).
         Every other layer stays on PackedConv3d.  None reads M3D_MASK_CONV_F16 (default "0"); like M3D_HEAD_CONV_F16 it needs
+        M3D_CONV_F16 not to be off.  Off, the head is bit for bit what it was without the argument.
+        tail_f16: `mask_net` runs the up-conv, its ReLU, the classifier and the sigmoid as one f16x2 launch (ops.UpConvF16.tail) where the
+        kernel takes the shape (upconv Cin % 16 == 0, at most 8 mask classes) and the call has at least tail_f16_min_rois RoIs (None:
+        conv_plan.MASK_TAIL_F16_MIN_ROIS, the measured threshold; 0 routes every supported call).  The operand bound comes from the last
+        trunk conv where that ran on the narrow f16x2 kernel, else from one sweep.  None reads M3D_MASK_TAIL_F16 (default "0"); it needs
         M3D_CONV_F16 not to be off.  Off, the head is bit for bit what it was without the argument."""
         self.cfg = cfg
         resolution = getattr(cfg, "mask_resolution", 14) if resolution is None else resolution
@@ -69,6 +77,13 @@ class MaskHeadM3D:
         assert tuple(wc.shape[2:]) == (1, 1, 1) and wc.shape[0] == (cfg.num_classes if self.cls_specific else 1)
         self.classify = ops.PackedConv3d(wc)
         self.classify_bias = params["Mask_Outs.classify.bias"].contiguous()
+        if tail_f16 is None:
+            tail_f16 = os.environ.get("M3D_MASK_TAIL_F16", "0") == "1"
+        self.tail_f16 = (bool(tail_f16) and os.environ.get("M3D_CONV_F16", "1") == "1" and ops.UpConvF16.supported(wu)
+                         and int(wc.shape[0]) <= ops.UpConvF16.MAX_CLASSES)
+        self.tail_f16_min_rois = conv_plan.MASK_TAIL_F16_MIN_ROIS if tail_f16_min_rois is None else int(tail_f16_min_rois)
+        self.up_f16 = ops.UpConvF16(wu) if self.tail_f16 else None
+        self.classify_weight = wc.reshape(int(wc.shape[0]), cout).contiguous() if self.tail_f16 else None
         self._ones = {}
 
     def _one(self, n, device):
@@ -83,12 +98,18 @@ class MaskHeadM3D:
         return (zn is not None and shape[0] > 0 and zn.supports(shape, dilation=self.dilation)
                 and zn.units(shape, dilation=self.dilation) >= self.conv_f16_min_units)
 
-    def trunk(self, feat, mask_rois, feat_max=None):
+    def _tail_takes(self, shape):
+        """`mask_net` runs the fused tail on a trunk output of this shape [R, C, M', M', M']"""
+        return (self.tail_f16 and shape[0] > 0 and shape[0] >= self.tail_f16_min_rois and self.up_f16.supports(shape))
+
+    def trunk(self, feat, mask_rois, feat_max=None, want_bound=False):
         """RoIAlign3D and the dilated convs of Mask_Head.forward (mask_rcnn_heads.py:181-192): [R, C, M', M', M'] with M' = roi_res.
         feat_max (conv_f16 only): the operand bound of feat as the conv that produced it left it ([ZwConv3d.SLOTS] device floats, the
         largest = a bound of max |feat|).  Every RoIAlign value is a convex combination of feature-map values, so it bounds the first
         conv's input too (the argument DetectorM3D uses for the conv box head); None: one ZwConv3d.bound_of sweep of the RoIAlign
-        output.  Each conv's epilogue leaves the next conv's bound."""
+        output.  Each conv's epilogue leaves the next conv's bound.
+        want_bound: -> (x, bound): the last conv, where it runs on the f16x2 kernel, leaves the bound of its output for the fused tail
+        (None where it ran on the fp32 kernel).  Without it the last conv is asked for no bound, as before."""
         c = self.cfg
         x = ops.roi_align3d_forward(feat, mask_rois, self.roi_res, self.roi_res, self.roi_res, 1.0 / c.stride, self.sampling_ratio)
         bound = feat_max                               # the bound of x where one is held, else None
@@ -98,11 +119,12 @@ class MaskHeadM3D:
                 if bound is None:
                     bound = ops.ZwConv3d.bound_of(x)
                 nxt = i < last and self._zn_takes(i + 1, (x.shape[0], conv.cout) + tuple(x.shape[2:]))
+                nxt = nxt or (want_bound and i == last)
                 x, bound = self.zn[i](x, bound, shift=bias, relu=True, out_max=None if nxt else False, dilation=self.dilation)
             else:
                 x = conv(x, scale=self._one(conv.cout, x.device), shift=bias, relu=True, dilation=self.dilation)
                 bound = None
-        return x
+        return (x, bound) if want_bound else x
 
     def up(self, x):
         """upconv + ReLU (mask_rcnn_heads.py:193): [R, C, M', M', M'] -> [R, Cout, 2M', 2M', 2M'].  compat.set_upconv("m3d"): one
@@ -130,6 +152,9 @@ class MaskHeadM3D:
         if not torch.is_tensor(rois):
             rois = torch.from_numpy(np.ascontiguousarray(rois, dtype=np.float32))
         rois = rois.to(device=blob_conv.device, dtype=torch.float32)
+        if self.tail_f16 and self._tail_takes((int(rois.shape[0]), self.up_f16.cin) + (self.roi_res,) * 3):
+            x, bound = self.trunk(blob_conv, rois, want_bound=True)
+            return self.up_f16.tail(x, bound, self.up_bias_raw, self.classify_weight, self.classify_bias, sigmoid=True)
         return self.outputs(self.head(blob_conv, rois))
 
 

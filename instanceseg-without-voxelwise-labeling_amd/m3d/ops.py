@@ -12,7 +12,7 @@ from ._lib import lib, check, M3DError, SgdTensor, AdamTensor, GradTensor, BoxHe
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "UpConvF16", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_wgrad_narrow_f16x2", "conv3d_wgrad_narrow_f16x2_supported", "conv3d_wgrad_narrow_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "ZnConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -744,6 +744,84 @@ def upconv3d_2x_wgrad(gy, x, y=None, bias=True, out=None):
     check(lib().m3d_upconv3d_2x_wgrad(_ptr(gy), _ptr(y), _ptr(x), _ptr(out), _ptr(gb), R, cin, cout, D, H, W, _ptr(ws), C.c_size_t(wsb),
                                       _stream()), "upconv3d_2x_wgrad")
     return out, gb
+
+
+class UpConvF16(object):
+    """The FORWARD of ConvTranspose3d(kernel 2, stride 2, padding 0) on the f16 matrix cores at fp32 accuracy (csrc/upconv3d_f16.hip: the
+    f16x2 cut of ZnConv3d, x cut while it is staged, the weight [Cin, Cout, 2, 2, 2] cut once here), with two epilogues: __call__ writes
+    what upconv3d_2x_forward writes; `tail` goes on through ReLU, the 1x1x1 classifier and the sigmoid in the same launch and writes only
+    [R, K, 2D, 2H, 2W] (K <= 8).  The operand bound travels as for the f16x2 convs: in_max = the [ZwConv3d.SLOTS] device floats the conv
+    before left (None: one ZwConv3d.bound_of sweep of x)."""
+    MAX_CLASSES = 8
+
+    @staticmethod
+    def supported(weight):
+        """weight [Cin, Cout, 2, 2, 2] with Cin % 16 == 0"""
+        return (weight.dim() == 5 and tuple(weight.shape[2:]) == (2, 2, 2)
+                and lib().m3d_upconv3d_2x_f16x2_packed_bytes(int(weight.shape[0]), int(weight.shape[1])) > 0)
+
+    def __init__(self, weight):
+        _need_gpu(weight)
+        w = _f32c(weight)
+        if not self.supported(w):
+            raise ValueError("UpConvF16: weight [Cin, Cout, 2, 2, 2] with Cin %% 16 == 0, got %s" % (tuple(weight.shape),))
+        self.cin, self.cout = int(w.shape[0]), int(w.shape[1])
+        nbytes = lib().m3d_upconv3d_2x_f16x2_packed_bytes(self.cin, self.cout)
+        self.packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        check(lib().m3d_upconv3d_2x_f16x2_pack(_ptr(w), self.cin, self.cout, _ptr(self.packed), _stream()), "upconv3d_2x_f16x2_pack")
+
+    def supports(self, shape):
+        """an input of this shape [R, Cin, D, H, W] runs on the kernel (m3d_upconv3d_2x_f16x2_supported)"""
+        if len(shape) != 5 or int(shape[1]) != self.cin:
+            return False
+        R, _, D, H, W = (int(v) for v in shape)
+        return bool(lib().m3d_upconv3d_2x_f16x2_supported(R, self.cin, self.cout, D, H, W))
+
+    def _operands(self, x, in_max):
+        _need_gpu(x, in_max)
+        x = _f32c(x)
+        if x.dim() != 5 or int(x.shape[1]) != self.cin:
+            raise ValueError("UpConvF16: x is %s, Cin is %d" % (tuple(x.shape), self.cin))
+        if in_max is None:
+            in_max = ZwConv3d.bound_of(x) if x.numel() else torch.zeros((ZwConv3d.SLOTS,), dtype=torch.float32, device=x.device)
+        assert in_max.numel() == ZwConv3d.SLOTS and in_max.dtype == torch.float32
+        return x, in_max
+
+    def __call__(self, x, in_max, bias=None, relu=False, out=None):
+        x, in_max = self._operands(x, in_max)
+        R, _, D, H, W = (int(v) for v in x.shape)
+        if bias is not None:
+            _need_gpu(bias)
+            bias = _f32c(bias)
+            assert bias.numel() == self.cout
+        _claim(out)
+        if out is None:
+            out = torch.empty((R, self.cout, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+        assert tuple(out.shape) == (R, self.cout, 2 * D, 2 * H, 2 * W) and out.is_contiguous()
+        check(lib().m3d_upconv3d_2x_forward_f16x2(_ptr(x), _ptr(self.packed), _ptr(bias), _ptr(out), R, self.cin, self.cout, D, H, W,
+                                                  int(bool(relu)), _ptr(in_max), _stream()), "upconv3d_2x_forward_f16x2")
+        return out
+
+    def tail(self, x, in_max, up_bias, cls_weight, cls_bias, sigmoid=True, out=None):
+        """act(cls_bias[k] + sum_co cls_weight[k, co] relu(upconv(x) + up_bias)[co]) -> [R, K, 2D, 2H, 2W]; cls_weight [K, Cout] or the
+        conv's [K, Cout, 1, 1, 1]; act = torch.sigmoid's formula, or the identity (sigmoid=False: the logits)."""
+        x, in_max = self._operands(x, in_max)
+        R, _, D, H, W = (int(v) for v in x.shape)
+        _need_gpu(up_bias, cls_weight, cls_bias)
+        cls_weight = _f32c(cls_weight)
+        K = int(cls_weight.shape[0])
+        if cls_weight.numel() != K * self.cout:
+            raise ValueError("UpConvF16.tail: cls_weight is %s, Cout is %d" % (tuple(cls_weight.shape), self.cout))
+        up_bias = _f32c(up_bias) if up_bias is not None else None
+        cls_bias = _f32c(cls_bias) if cls_bias is not None else None
+        assert (up_bias is None or up_bias.numel() == self.cout) and (cls_bias is None or cls_bias.numel() == K)
+        _claim(out)
+        if out is None:
+            out = torch.empty((R, K, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+        assert tuple(out.shape) == (R, K, 2 * D, 2 * H, 2 * W) and out.is_contiguous()
+        check(lib().m3d_mask_tail_f16x2(_ptr(x), _ptr(self.packed), _ptr(up_bias), _ptr(cls_weight), _ptr(cls_bias), _ptr(out), R, self.cin,
+                                        self.cout, K, D, H, W, int(bool(sigmoid)), _ptr(in_max), _stream()), "mask_tail_f16x2")
+        return out
 
 
 class SplitLinear:

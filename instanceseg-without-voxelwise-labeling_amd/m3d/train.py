@@ -518,8 +518,16 @@ class _UpConv3d2x(torch.autograd.Function):
     computed; the bias gradient comes out of the wgrad launch."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        y = ops.upconv3d_2x_forward(x, weight.detach(), None if bias is None else bias.detach(), relu=relu)
+    def forward(ctx, x, weight, bias, relu, f16=False):
+        b = None if bias is None else bias.detach()
+        up = None
+        if f16 and ops.UpConvF16.supported(weight):          # compat.set_upconv_f16: the forward alone; the backward below does not change
+            from . import compat
+            up = compat._packed(weight, "upconv-f16")
+        if up is not None and x.shape[0] > 0 and up.supports(tuple(x.shape)):
+            y = up(x, None, bias=b, relu=relu)
+        else:
+            y = ops.upconv3d_2x_forward(x, weight.detach(), b, relu=relu)
         ctx.relu, ctx.has_bias = bool(relu), bias is not None
         ctx.save_for_backward(x, weight, y if relu else None)
         return y
@@ -536,7 +544,7 @@ class _UpConv3d2x(torch.autograd.Function):
             gw, gb = ops.upconv3d_2x_wgrad(gy, x.detach(), y=y, bias=want_gb)
             if not ctx.needs_input_grad[1]:
                 gw = None
-        return gx, gw, gb, None
+        return gx, gw, gb, None, None
 
 
 def upconv3d_2x(x, weight, bias=None, relu=False):
@@ -545,7 +553,9 @@ def upconv3d_2x(x, weight, bias=None, relu=False):
     for t in (x, weight, bias):
         if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
             raise ops.M3DError("upconv3d_2x: x, weight and bias must be CUDA (ROCm) tensors; there is no CPU path")
-    return _UpConv3d2x.apply(x.contiguous(), weight.contiguous(), bias, bool(relu))
+    from . import compat
+    f16 = compat.get_upconv_f16() and compat.get_upconv() == compat.UPCONV_M3D
+    return _UpConv3d2x.apply(x.contiguous(), weight.contiguous(), bias, bool(relu), bool(f16))
 
 
 class MaskHead(torch.nn.Module):

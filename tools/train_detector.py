@@ -82,6 +82,9 @@ def main():
     ap.add_argument("--upconv", choices=("torch", "m3d"), default="torch",
                     help="with --mask: the mask head's ConvTranspose3d + ReLU (m3d.compat.set_upconv): m3d = csrc/upconv3d.hip, forward and "
                          "backward, bias and ReLU fused")
+    ap.add_argument("--upconv-f16", action="store_true",
+                    help="with --upconv m3d: the up-conv's FORWARD on the f16 matrix cores at fp32 accuracy (m3d.compat.set_upconv_f16, "
+                         "csrc/upconv3d_f16.hip); the backward stays on the fp32 kernels")
     ap.add_argument("--mask-dilation", type=int, choices=(1, 2), default=1,
                     help="with --mask: MRCNN.DILATION of the mask head's 3^3 convs (MaskTrainCfg.dilation)")
     ap.add_argument("--conv-dilated", choices=("torch", "m3d"), default="torch",
@@ -109,6 +112,8 @@ def main():
     a = ap.parse_args()
     if a.mask_dilation != 1 and not a.mask:
         ap.error("--mask-dilation needs --mask")
+    if a.upconv_f16 and a.upconv != "m3d":
+        ap.error("--upconv-f16 needs --upconv m3d")
     if a.conv_dilated_f16 and a.conv_dilated != "m3d":
         ap.error("--conv-dilated-f16 needs --conv-dilated m3d")
     if a.wgrad_dilated_f16 and not (a.mask == "spot" and a.mask_dilation == 2 and a.conv_dilated == "m3d"):
@@ -127,6 +132,7 @@ def main():
     m3d.compat.set_conv_train(a.conv)
     m3d.compat.set_roi_align_backward(a.roi_backward)
     m3d.compat.set_upconv(a.upconv)
+    m3d.compat.set_upconv_f16(a.upconv_f16)
     m3d.compat.set_conv_dilated(a.conv_dilated)
     m3d.compat.set_conv_dilated_f16(a.conv_dilated_f16)
     m3d.compat.set_conv_wgrad_dilated_f16(a.wgrad_dilated_f16)
