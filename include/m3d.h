@@ -1414,6 +1414,35 @@ size_t m3d_linear_wgrad_workspace_bytes(int M, int N, int K);
 int m3d_linear_wgrad(const float* d_gy, const float* d_x, float* d_gw, float* d_gb, int M, int N, int K, void* d_ws, size_t ws_bytes,
                      void* stream);
 
+/* The same two GEMMs on the f16 matrix cores at fp32 accuracy (fc_backward_f16.hip; DESIGN, "Box-head backward on the f16 pipe"): the
+ * "f16x2 split" of m3d_linear_f16x2_forward on the raw fp32 operands - every value is multiplied by its tensor's power of two and cut
+ * into two fp16 numbers once, on its way to LDS; three v_mfma_f32_32x32x16_f16 products per fp32 product accumulate in fp32, an
+ * accumulator is folded into fp32 registers after at most 384 chained MFMAs.  No packed or transposed copy of any operand is made.
+ * d_gb (or NULL) is summed from the uncut fp32 values in a fixed order.  Split reduction, workspace partials added in slice order, no
+ * atomics: bit-identical run to run.
+ * Bounds: each operand's bound is a device pointer to `slots` floats whose LARGEST is >= the tensor's largest magnitude (1: an
+ * m3d_absmax result; m3d_conv3d_zw_slots(): a slot array), or NULL: the call sweeps that operand itself into d_ws (no host read).  A
+ * bound smaller than the largest magnitude overflows fp16; a bound up to 2^8 too large costs no accuracy.
+ * m3d_linear_backward_f16x2_supported: 1 where M >= 1, N >= 64, N % 4 == 0, K % 4 == 0 and no operand has 2^31 elements or more, else 0
+ * (cls_score / bbox_pred stay on m3d_linear_dgrad / m3d_linear_wgrad).
+ * The _plan functions (host only) give what the launch runs: slices = the slices of the reduction (1: no second launch), chain = the
+ * most MFMAs an accumulator chains (<= 384), folds = the folds of one slice's accumulator into fp32 registers (0: the accumulator is
+ * stored directly).  Any output pointer may be NULL.  An output element therefore sees at most chain * max(folds, 1) + folds + slices + 2
+ * roundings of its running sum (the last 2: the two scale multiplies) - the n_acc of tests/linear_backward_f16_cases.py.
+ * Checked before any pointer is followed, in this order: M < 0, N < 1, K < 1 -> M3D_EINVAL (the plans: M < 1 as well); a shape that
+ * _supported refuses -> M3D_EUNSUPPORTED; a NULL required pointer (d_ws is required: the sizes below are never 0 for a supported
+ * shape), slots outside 1..1024, a pointer that is not 4-byte aligned, ws_bytes too small -> M3D_EINVAL; an operand, output or d_ws
+ * that is not 16-byte aligned -> M3D_EUNSUPPORTED.  M == 0: as m3d_linear_dgrad / m3d_linear_wgrad. */
+int m3d_linear_backward_f16x2_supported(int M, int N, int K);
+int m3d_linear_dgrad_f16x2_plan(int M, int N, int K, int* slices, int* chain, int* folds);
+int m3d_linear_wgrad_f16x2_plan(int M, int N, int K, int* slices, int* chain, int* folds);
+size_t m3d_linear_dgrad_f16x2_workspace_bytes(int M, int N, int K);
+size_t m3d_linear_wgrad_f16x2_workspace_bytes(int M, int N, int K);
+int m3d_linear_dgrad_f16x2(const float* d_gy, const float* d_weight, float* d_gx, int M, int N, int K, const float* d_gy_bound,
+                           int gy_bound_slots, const float* d_w_bound, int w_bound_slots, void* d_ws, size_t ws_bytes, void* stream);
+int m3d_linear_wgrad_f16x2(const float* d_gy, const float* d_x, float* d_gw, float* d_gb, int M, int N, int K, const float* d_gy_bound,
+                           int gy_bound_slots, const float* d_x_bound, int x_bound_slots, void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Peak stimulation (peak_stim.hip; DESIGN, "Peak stimulation"): lib/prm/peak_stimulation_3d.py:6-52 on a response map
  * d_x fp32 [B,C,S,H,W], contiguous; win odd, o = win / 2.

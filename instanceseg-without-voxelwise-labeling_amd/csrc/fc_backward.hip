@@ -27,7 +27,9 @@
 //    neighbours - the N/128 wgrad tiles that share an x panel (the M/128 dgrad tiles that share a W panel) meet in one L2;
 //  * gb: the workgroups of the first column tile sum their staged gy tile column by column (row order, one thread per column, no
 //    atomics); with a split reduction the per-slice sums travel through the workspace like the partials.
-// Staying on the fp32-input MFMA is deliberate: see DESIGN.md, "Box-head backward".
+// These kernels stay on the fp32-input MFMA and stay the default.  The same two GEMMs on the f16 matrix cores (the f16x2 cut on the raw
+// operands, opt-in, 1.8 x - 2.2 x faster at the fc1 shapes and slower at fc2) are fc_backward_f16.hip: DESIGN.md, "Box-head backward on
+// the f16 pipe".
 #include "m3d_common.h"
 
 namespace {

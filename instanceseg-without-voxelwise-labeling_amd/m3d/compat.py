@@ -503,10 +503,51 @@ def _split_linear(weight, bias):
     return lin
 
 
+_linear_backward = (conv_plan.LINEAR_BACKWARD_FP32, None)      # set_linear_backward: (mode, min_work or None = the planner's constant)
+_wmax_cache = {}          # id(parameter) -> (weakref, _version, data_ptr, max|W| as a 1-element device tensor)
+
+
+def set_linear_backward(mode, min_work=None):
+    """The backward of the intercepted nn.Linear layers: "fp32" (the default; install() does not change it) keeps m3d_linear_dgrad /
+    m3d_linear_wgrad; "f16x2" takes m3d_linear_dgrad_f16x2 / m3d_linear_wgrad_f16x2 (csrc/fc_backward_f16.hip: the f16 matrix cores at
+    fp32 accuracy, operands cut while they are staged) for the layers conv_plan.linear_backward_kernel routes to them.  gy is swept once
+    per backward and its bound shared by both GEMMs, max|W| is cached per parameter like the packs (invalidate_packs() drops it), x is
+    swept by the wgrad call.  The forward keeps its kernel and its bits.  min_work: the routing threshold in M N K (None:
+    conv_plan.LINEAR_BACKWARD_F16X2_MIN_WORK; 0 routes every supported layer - tests and A/B runs).  Read when the backward runs.
+    Returns the previous mode."""
+    global _linear_backward
+    if mode not in (conv_plan.LINEAR_BACKWARD_FP32, conv_plan.LINEAR_BACKWARD_F16X2):
+        raise ValueError("set_linear_backward(%r): 'fp32' or 'f16x2'" % (mode,))
+    if min_work is not None and int(min_work) < 0:
+        raise ValueError("set_linear_backward(min_work=%r): None or a count >= 0" % (min_work,))
+    prev, _linear_backward = _linear_backward[0], (mode, None if min_work is None else int(min_work))
+    return prev
+
+
+def get_linear_backward():
+    return _linear_backward[0]
+
+
+def _weight_max(weight):
+    """max|W| of an nn.Linear weight as a 1-element device tensor, cached like _split_linear's packs: only for live nn.Parameters at the
+    same version / address"""
+    if not isinstance(weight, torch.nn.Parameter):
+        return ops.absmax(weight.detach())
+    ent = _wmax_cache.get(id(weight))
+    if ent is not None:
+        ref, ver, ptr, wmax = ent
+        if ref() is weight and ver == weight._version and ptr == weight.data_ptr():
+            return wmax
+    wmax = ops.absmax(weight.detach())
+    _wmax_cache[id(weight)] = (weakref.ref(weight, lambda _r, k=id(weight): _wmax_cache.pop(k, None)), weight._version, weight.data_ptr(), wmax)
+    return wmax
+
+
 class _LinearFn(torch.autograd.Function):
     """x [M,K] . W[N,K]^T + b on libm3d's GEMMs: the bf16x3 split kernels (fp32 accuracy) where K % 32 == 0 and N >= 64 (fc1, fc2),
     else the fp32-input MFMA kernel (cls_score, bbox_pred).  Backward (training; off the inference path): libm3d's dgrad and wgrad
-    GEMMs on the saved operands as they are (csrc/fc_backward.hip) - no transposed copy, the bias gradient out of the wgrad launch."""
+    GEMMs on the saved operands as they are (csrc/fc_backward.hip) - no transposed copy, the bias gradient out of the wgrad launch;
+    under set_linear_backward("f16x2") the same two GEMMs of csrc/fc_backward_f16.hip where conv_plan.linear_backward_kernel says so."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -521,9 +562,19 @@ class _LinearFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         gy = gy.contiguous()
         gx = gw = gb = None
+        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
+        mode, min_work = _linear_backward
+        if conv_plan.linear_backward_kernel(gy.shape[0], gy.shape[1], x.shape[1], mode, min_work) == conv_plan.LINEAR_BACKWARD_F16X2:
+            gy_max = ops.absmax(gy)                                # one sweep, both GEMMs
+            if ctx.needs_input_grad[0]:
+                gx = ops.linear_dgrad_f16x2(gy, weight.detach(), gy_max, _weight_max(weight))
+            if ctx.needs_input_grad[1] or want_gb:
+                gw, gb = ops.linear_wgrad_f16x2(gy, x.detach(), gy_max, None, bias=want_gb)
+                if not ctx.needs_input_grad[1]:
+                    gw = None
+            return gx, gw, gb
         if ctx.needs_input_grad[0]:
             gx = ops.linear_dgrad(gy, weight.detach())
-        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_gb:
             gw, gb = ops.linear_wgrad(gy, x.detach(), bias=want_gb)
             if not ctx.needs_input_grad[1]:
@@ -552,6 +603,7 @@ def invalidate_packs():
     or update through the parameter itself (`with torch.no_grad(): p.mul_()`, `load_state_dict`), which does."""
     _pack_cache.clear()
     _lin_cache.clear()
+    _wmax_cache.clear()
 
 
 def install_linear():

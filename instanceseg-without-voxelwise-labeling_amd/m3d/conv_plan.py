@@ -80,6 +80,31 @@ def wgrad_kernel(batch, cin, cout, D, H, W, mode, k=3, narrow=False, narrow_f16=
     return WGRAD_FP32
 
 
+LINEAR_BACKWARD_FP32, LINEAR_BACKWARD_F16X2 = "fp32", "f16x2"    # nn.Linear backward: csrc/fc_backward.hip / csrc/fc_backward_f16.hip
+# The f16x2 backward pays a sweep of gy and of x per step and one of the weight per parameter version; a layer is routed to it from the
+# work M N K of the smallest row of profiles/linear_backward_f16.txt whose backward (dgrad + wgrad, the gy and x sweeps inside the
+# window, the weight's bound cached) beat the fp32 kernels by more than the sum of the two spreads: fc1 at the nuclei K with 64 rows,
+# 64 x 1024 x 87 808 (0.250 against 0.456 ms, 1.83 x); the four larger rows win too (1.89 x .. 2.17 x), and the one smaller row, fc2
+# (128 x 1024 x 1024), LOSES (0.053 against 0.037 ms: three more launches than it has work for).  Nothing smaller routes by default.
+LINEAR_BACKWARD_F16X2_MIN_WORK = 64 * 1024 * 87808
+
+
+def linear_backward_kernel(M, N, K, mode, min_work=None):
+    """Which kernels compute the backward of an nn.Linear with gy [M, N], weight [N, K]: LINEAR_BACKWARD_FP32 (m3d_linear_dgrad /
+    m3d_linear_wgrad) or LINEAR_BACKWARD_F16X2 (m3d_linear_dgrad_f16x2 / m3d_linear_wgrad_f16x2).  The one place that says so.  mode: the
+    caller's setting (compat.set_linear_backward): "fp32" keeps every layer where it is; "f16x2" moves the layers that
+    m3d_linear_backward_f16x2_supported takes (N >= 64, N and K multiples of 4: fc1 and fc2, never cls_score / bbox_pred) and whose work
+    M N K reaches min_work (None: LINEAR_BACKWARD_F16X2_MIN_WORK; 0: every supported layer).  A function of the shape only."""
+    if mode not in (LINEAR_BACKWARD_FP32, LINEAR_BACKWARD_F16X2):
+        raise ValueError("linear backward mode %r: 'fp32' or 'f16x2'" % (mode,))
+    if mode == LINEAR_BACKWARD_FP32:
+        return LINEAR_BACKWARD_FP32
+    floor = LINEAR_BACKWARD_F16X2_MIN_WORK if min_work is None else int(min_work)
+    if int(M) * int(N) * int(K) >= floor and ops.linear_backward_f16x2_supported(M, N, K):
+        return LINEAR_BACKWARD_F16X2
+    return LINEAR_BACKWARD_FP32
+
+
 TRAIN_FP32, TRAIN_F16X2 = "fp32", "f16x2"            # forward / dgrad kernels of a training conv: the direct fp32 MFMA kernel / conv3d_zw.hip
 TRAIN_F16X2_NARROW = "f16x2 narrow"                  # conv3d_zn.hip (ops.ZnConv3d): maps at most 8 wide, opt-in (compat.set_conv_train_narrow)
 # Output channels of the launched conv (forward: cout; dgrad: the forward cin) from which a direction routes to the f16x2 kernel.  Its

@@ -12,7 +12,7 @@ from ._lib import lib, check, M3DError, SgdTensor, AdamTensor, GradTensor, BoxHe
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "UpConvF16", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "linear_dgrad_f16x2", "linear_wgrad_f16x2", "linear_backward_f16x2_supported", "linear_dgrad_f16x2_plan", "linear_wgrad_f16x2_plan", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "UpConvF16", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_wgrad_narrow_f16x2", "conv3d_wgrad_narrow_f16x2_supported", "conv3d_wgrad_narrow_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "ZnConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -652,6 +652,88 @@ def linear_wgrad(gy, x, bias=True, out=None):
     wsb = lib().m3d_linear_wgrad_workspace_bytes(M, N, K)
     ws = torch.empty((wsb // 4,), dtype=torch.float32, device=gy.device) if wsb else None
     check(lib().m3d_linear_wgrad(_ptr(gy), _ptr(x), _ptr(out), _ptr(gb), M, N, K, _ptr(ws), C.c_size_t(wsb), _stream()), "linear_wgrad")
+    return out, gb
+
+
+def linear_backward_f16x2_supported(M, N, K):
+    """m3d_linear_backward_f16x2_supported (host only): linear_dgrad_f16x2 / linear_wgrad_f16x2 take gy [M,N], weight [N,K], x [M,K]:
+    M >= 1, N >= 64, N % 4 == 0, K % 4 == 0, no operand of 2^31 elements or more"""
+    return bool(lib().m3d_linear_backward_f16x2_supported(int(M), int(N), int(K)))
+
+
+def _linear_backward_f16x2_plan(fn, what, M, N, K):
+    v = [C.c_int(0) for _ in range(3)]
+    rc = fn(int(M), int(N), int(K), *[C.byref(a) for a in v])
+    if rc == -4:
+        return None
+    check(rc, what)
+    return dict(zip(("slices", "chain", "folds"), (a.value for a in v)))
+
+
+def linear_dgrad_f16x2_plan(M, N, K):
+    """What linear_dgrad_f16x2 runs for the shape (m3d_linear_dgrad_f16x2_plan, host only): dict(slices, chain, folds) - the slices of
+    the reduction over N, the most MFMAs one accumulator chains (<= 384) and the folds of a slice's accumulator into fp32 registers;
+    None where the shape is not supported."""
+    return _linear_backward_f16x2_plan(lib().m3d_linear_dgrad_f16x2_plan, "linear_dgrad_f16x2_plan", M, N, K)
+
+
+def linear_wgrad_f16x2_plan(M, N, K):
+    """linear_dgrad_f16x2_plan for linear_wgrad_f16x2 (m3d_linear_wgrad_f16x2_plan): the reduction runs over M"""
+    return _linear_backward_f16x2_plan(lib().m3d_linear_wgrad_f16x2_plan, "linear_wgrad_f16x2_plan", M, N, K)
+
+
+def _bound_arg(what, b):
+    """(pointer, slots) of an operand bound: None (the library sweeps), or 1 / ZwConv3d.SLOTS contiguous device floats (largest wins)"""
+    if b is None:
+        return _ptr(None), 0
+    _need_gpu(b)
+    if not (b.dtype == torch.float32 and b.is_contiguous() and b.numel() in (1, ZwConv3d.SLOTS)):
+        raise ValueError("%s: a bound is 1 or %d contiguous float32 device values" % (what, ZwConv3d.SLOTS))
+    return _ptr(b), int(b.numel())
+
+
+def linear_dgrad_f16x2(gy, weight, gy_max=None, w_max=None, out=None):
+    """linear_dgrad on the f16 matrix cores at fp32 accuracy (m3d_linear_dgrad_f16x2; csrc/fc_backward_f16.hip): gy [M,N] @ weight [N,K]
+    -> [M,K], both operands read as fp32 and cut while they are staged - no pack, no transposed copy.  gy_max / w_max: device floats
+    whose largest bounds |gy| / |weight| (ops.absmax, or a [ZwConv3d.SLOTS] array); None: the library sweeps that operand.  An
+    unsupported shape is an error: ask linear_backward_f16x2_supported (or conv_plan.linear_backward_kernel)."""
+    _need_gpu(gy, weight)
+    gy, weight = _f32c(gy), _f32c(weight)
+    M, N = gy.shape
+    K = weight.shape[1]
+    if weight.shape[0] != N:
+        raise ValueError("linear_dgrad_f16x2: gy is [%d,%d] but weight is %s" % (M, N, tuple(weight.shape)))
+    gp, gn = _bound_arg("linear_dgrad_f16x2", gy_max)
+    wp, wn = _bound_arg("linear_dgrad_f16x2", w_max)
+    _claim(out)
+    if out is None:
+        out = torch.empty((M, K), dtype=torch.float32, device=gy.device)
+    wsb = lib().m3d_linear_dgrad_f16x2_workspace_bytes(M, N, K)
+    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=gy.device)
+    check(lib().m3d_linear_dgrad_f16x2(_ptr(gy), _ptr(weight), _ptr(out), M, N, K, gp, gn, wp, wn, _ptr(ws), C.c_size_t(wsb), _stream()),
+          "linear_dgrad_f16x2")
+    return out
+
+
+def linear_wgrad_f16x2(gy, x, gy_max=None, x_max=None, bias=True, out=None):
+    """linear_wgrad on the f16 matrix cores at fp32 accuracy (m3d_linear_wgrad_f16x2): (gy.T @ x -> [N,K], gy.sum(0) -> [N] or None
+    without `bias`); the bias gradient is summed from the uncut fp32 values.  Bounds as linear_dgrad_f16x2."""
+    _need_gpu(gy, x)
+    gy, x = _f32c(gy), _f32c(x)
+    M, N = gy.shape
+    K = x.shape[1]
+    if x.shape[0] != M:
+        raise ValueError("linear_wgrad_f16x2: gy is [%d,%d] but x is %s" % (M, N, tuple(x.shape)))
+    gp, gn = _bound_arg("linear_wgrad_f16x2", gy_max)
+    xp, xn = _bound_arg("linear_wgrad_f16x2", x_max)
+    _claim(out)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=gy.device)
+    gb = torch.empty((N,), dtype=torch.float32, device=gy.device) if bias else None
+    wsb = lib().m3d_linear_wgrad_f16x2_workspace_bytes(max(M, 1), N, K)
+    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=gy.device)
+    check(lib().m3d_linear_wgrad_f16x2(_ptr(gy), _ptr(x), _ptr(out), _ptr(gb), M, N, K, gp, gn, xp, xn, _ptr(ws), C.c_size_t(wsb),
+                                       _stream()), "linear_wgrad_f16x2")
     return out, gb
 
 

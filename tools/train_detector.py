@@ -24,7 +24,10 @@ conv_plan.WGRAD_DILATED_F16X2_MIN_WORK products per tap).
 --conv-narrow f16x2 runs the forward and the backward-data pass of those convs on the narrow-map f16x2 kernel
 (m3d.compat.set_conv_train_narrow, csrc/conv3d_zn.hip); --wgrad-narrow-f16 runs their weight gradient on the f16 matrix cores on that
 2 x 8 x 8 tile (m3d.compat.set_conv_wgrad_narrow_f16, csrc/conv3d_wgrad_narrow_f16.hip: layers of at least
-conv_plan.WGRAD_NARROW_F16X2_MIN_WORK products per tap, whatever --wgrad and --wgrad-narrow say).  They compose."""
+conv_plan.WGRAD_NARROW_F16X2_MIN_WORK products per tap, whatever --wgrad and --wgrad-narrow say).  They compose.
+
+--linear-backward f16x2 (default fp32) runs the backward of the FC layers on the f16 matrix cores at fp32 accuracy
+(m3d.compat.set_linear_backward, csrc/fc_backward_f16.hip: layers of at least conv_plan.LINEAR_BACKWARD_F16X2_MIN_WORK M N K)."""
 import argparse
 import os
 import sys
@@ -109,6 +112,9 @@ def main():
     ap.add_argument("--wgrad-dilated-f16", action="store_true",
                     help="with --mask spot --mask-dilation 2 --conv-dilated m3d: weight gradients of the dilation-2 convs on maps at most 8 "
                          "wide (cin and cout multiples of 32) on the f16 matrix cores at fp32 accuracy (m3d.compat.set_conv_wgrad_dilated_f16)")
+    ap.add_argument("--linear-backward", choices=("fp32", "f16x2"), default="fp32",
+                    help="backward of the FC layers (m3d.compat.set_linear_backward): f16x2 = the f16 matrix cores at fp32 accuracy where "
+                         "conv_plan.linear_backward_kernel routes a layer")
     a = ap.parse_args()
     if a.mask_dilation != 1 and not a.mask:
         ap.error("--mask-dilation needs --mask")
@@ -136,6 +142,7 @@ def main():
     m3d.compat.set_conv_dilated(a.conv_dilated)
     m3d.compat.set_conv_dilated_f16(a.conv_dilated_f16)
     m3d.compat.set_conv_wgrad_dilated_f16(a.wgrad_dilated_f16)
+    m3d.compat.set_linear_backward(a.linear_backward)
     torch.manual_seed(a.seed)
     tile = tuple(a.tile)
     rcfg, bcfg = m3d.RpnTrainCfg.nuclei(max_size=max(tile)), m3d.BoxHeadTrainCfg.nuclei()
