@@ -26,27 +26,18 @@
 // 1 / s_x once (exact).  A second register set per wave would have been 144 more registers, one wave per SIMD instead of two; the
 // workspace costs 110 KB written and read per 16 tiles (2048 voxels x 64 channels x 4 bytes = 512 KB of operands, before the halo).
 // No atomics: bit-identical run to run.
-#include "m3d_common.h"
+// The cut, the MFMA triple and the bound slots are those of f16x2.h; the partial store, the reduce kernel and the slot rule those of
+// conv3d_wgrad_f16_common.h.
+#include "conv3d_wgrad_f16_common.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
 constexpr int WF_NT = 192;                                  // 3 waves: wave = dz
-constexpr int WF_SLOTS_IN = 32;                             // slots of an operand-bound array (m3d_conv3d_zw_slots)
 constexpr int TZ = 2, TY = 4, TX = 16;                      // voxel tile: 8 rows = 8 k-steps of 16
 constexpr int GROWS = TZ * TY, HZ = TZ + 2, HY = TY + 2, XROWS = HZ * HY;
 constexpr int MFMA_PER_TILE = GROWS * 3;                    // per accumulator: 8 k-steps x (hh + hl + lh)
-constexpr int WF_MAX_TILES = 16;                            // tiles of a slot
-constexpr int WF_CHAIN = WF_MAX_TILES * MFMA_PER_TILE;      // 384: the longest run of MFMAs into one accumulator
+constexpr int WF_CHAIN = WG_MAX_TILES * MFMA_PER_TILE;      // 384: the longest run of MFMAs into one accumulator
 static_assert(WF_CHAIN <= 512, "chain");
-constexpr int WF_TARGET_WGS = 512;                          // two workgroups per CU
-constexpr int RG = 8;                                       // strided groups of the reduce kernel
 constexpr long long WF_MAX_WGS = 0xFFFFFFFFll / WF_NT;      // a launch takes fewer than 2^32 threads
 constexpr int EDGE_OFF = XROWS * 32;                        // edge dwords of a channel behind its rows
 constexpr int XP = EDGE_OFF + XROWS * 4 + 16;               // 880: channel pitch of the x image
@@ -59,24 +50,6 @@ constexpr int X_ITEMS = 32 * XROWS * 6, G_ITEMS = 32 * GROWS * 4;
 static_assert(X_ITEMS % WF_NT == 0, "x staging items per thread");
 
 struct WfPlan { int tiles_x, tiles_y, tiles_z, NT, cbs, ibs, tps, slots; long long n; };
-
-__device__ __forceinline__ float bound_of_slots(const float* __restrict__ slots, int lane) {
-  float m = slots[lane & (WF_SLOTS_IN - 1)];
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  return m;
-}
-
-// the cut of the contract: v = a s (exact), h = fp16(v), l = fp16(v - h)
-__device__ __forceinline__ void cut(float a, float s, _Float16& h, _Float16& l) {
-  const float v = a * s;
-  h = (_Float16)v;
-  l = (_Float16)(v - (float)h);
-}
-
-__device__ __forceinline__ unsigned pack2(_Float16 a, _Float16 b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
 
 // four consecutive x of one row, zeros outside [0, W); p points at column xf of the row (never dereferenced outside the row)
 __device__ __forceinline__ f32x4 load_quad(const float* __restrict__ p, int xf, int W, bool row_ok) {
@@ -112,8 +85,8 @@ __global__ __launch_bounds__(WF_NT, 2) void conv3d_wgrad_f16_kernel(const float*
   const size_t HW = (size_t)H * W, DHW = HW * D;
 
   float sx, sg, inv_;
-  m3d::f16_scale_of(bound_of_slots(x_max, lane), sx, inv_);
-  m3d::f16_scale_of(bound_of_slots(g_max, lane), sg, inv_);
+  f16_scale_of(bound_of_slots(x_max, lane), sx, inv_);
+  f16_scale_of(bound_of_slots(g_max, lane), sg, inv_);
 
   f32x16 acc[3][3];
 #pragma unroll
@@ -213,55 +186,16 @@ __global__ __launch_bounds__(WF_NT, 2) void conv3d_wgrad_f16_kernel(const float*
         for (int dx = 0; dx < 3; ++dx) {
           const f16x8 bh = __builtin_bit_cast(f16x8, dx == 0 ? f0[0] : dx == 1 ? w[0] : f2[0]);
           const f16x8 bl = __builtin_bit_cast(f16x8, dx == 0 ? f0[1] : dx == 1 ? w[1] : f2[1]);
-          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[dy][dx], 0, 0, 0);
-          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[dy][dx], 0, 0, 0);
-          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[dy][dx], 0, 0, 0);
+          mfma3(ah, al, bh, bl, acc[dy][dx]);
         }
       }
     }
   }
-  // ---- this wave's nine taps of the slot's partial: acc[i = co][j = ci], col j = lane & 31, row i = (g & 3) + 8 (g >> 2) + 4 h
-  float* pp = partial + (size_t)slot * pl.n;
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int tap = dz * 9 + dy * 3 + dx;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int co = cb * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
-        pp[((size_t)tap * cout + co) * cin + ib * 32 + r] = acc[dy][dx][g];
-      }
-    }
-}
-
-// dW[co][ci][tap] = (sum over the slots in a fixed order) / s_g / s_x: a block is 32 consecutive partial elements x RG strided groups
-__global__ __launch_bounds__(256) void conv3d_wgrad_f16_reduce_kernel(const float* __restrict__ partial, int slots, long long n, int cin,
-                                                                      int cout, const float* __restrict__ x_max,
-                                                                      const float* __restrict__ g_max, float* __restrict__ dw) {
-  __shared__ float sm[RG][32];
-  const int e = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const long long i = (long long)blockIdx.x * 32 + e;                 // n is a multiple of 32 * 32 * 27
-  float s_, inv_x, inv_g;
-  m3d::f16_scale_of(bound_of_slots(x_max, threadIdx.x & 63), s_, inv_x);
-  m3d::f16_scale_of(bound_of_slots(g_max, threadIdx.x & 63), s_, inv_g);
-  float sum = 0.f;
-  for (int s = g; s < slots; s += RG) sum += partial[(size_t)s * n + i];
-  sm[g][e] = sum;
-  __syncthreads();
-  if (g == 0) {
-    float tot = sm[0][e];
-#pragma unroll
-    for (int k = 1; k < RG; ++k) tot += sm[k][e];
-    const long long cc = (long long)cout * cin;
-    const int tap = (int)(i / cc);
-    const long long rem = i - tap * cc;                                // co * cin + ci
-    dw[rem * 27 + tap] = tot * inv_g * inv_x;
-  }
+  store_partial(partial + (size_t)slot * pl.n, acc, dz, cb, ib, r, h, cin, cout);
 }
 
 bool wf_supported(int batch, int cin, int cout, int D, int H, int W) {
-  if (batch <= 0 || cin <= 0 || cout <= 0 || D <= 0 || H <= 0 || W <= 0) return false;
+  if (!extents_ok(batch, cin, cout, D, H, W)) return false;
   if (cin % 32 || cout % 32 || cin > 4096 || cout > 4096) return false;
   const long long tz = ((long long)D + TZ - 1) / TZ, ty = ((long long)H + TY - 1) / TY, tx = ((long long)W + TX - 1) / TX;
   if (tz * ty > (1ll << 30) || tz * ty * tx > (1ll << 30)) return false;       // each product below 2^61
@@ -272,11 +206,7 @@ WfPlan wf_plan(int batch, int cin, int cout, int D, int H, int W) {
   WfPlan p;
   p.tiles_x = (W + TX - 1) / TX; p.tiles_y = (H + TY - 1) / TY; p.tiles_z = (D + TZ - 1) / TZ;
   p.NT = batch * p.tiles_x * p.tiles_y * p.tiles_z;
-  p.cbs = cout / 32; p.ibs = cin / 32;
-  long long tps = (long long)p.NT * p.cbs * p.ibs / WF_TARGET_WGS;      // a function of the shape only
-  p.tps = (int)(tps < 1 ? 1 : tps > WF_MAX_TILES ? WF_MAX_TILES : tps);
-  p.slots = (p.NT + p.tps - 1) / p.tps;
-  p.n = (long long)cout * cin * 27;
+  slot_rule(p, cin, cout);
   return p;
 }
 
@@ -296,25 +226,17 @@ M3D_API size_t m3d_conv3d_wgrad_f16x2_workspace_bytes(int batch, int cin, int co
 
 M3D_API int m3d_conv3d_wgrad_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int* slots, int* tiles_per_slot,
                                         int* chain, int* folds) {
-  if (batch <= 0 || cin <= 0 || cout <= 0 || depth <= 0 || height <= 0 || width <= 0) return M3D_EINVAL;
+  if (!extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
   if (!m3d_conv3d_wgrad_f16x2_supported(batch, cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
-  const WfPlan p = wf_plan(batch, cin, cout, depth, height, width);
-  if (slots) *slots = p.slots;
-  if (tiles_per_slot) *tiles_per_slot = p.tps;
-  if (chain) *chain = p.tps * MFMA_PER_TILE;
-  // fp32 operations on an output behind its MFMA chain: the adds of its strided group (the first partial is added to 0), the RG - 1 adds
-  // of the group sums, the two scale multiplies
-  if (folds) *folds = (p.slots + RG - 1) / RG + (RG - 1) + 2;
+  report_plan(wf_plan(batch, cin, cout, depth, height, width), MFMA_PER_TILE, slots, tiles_per_slot, chain, folds);
   return M3D_OK;
 }
 
 M3D_API int m3d_conv3d_wgrad_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
                                    int depth, int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws,
                                    size_t ws_bytes, void* stream) {
-  if (!d_in || !d_grad_out || !d_grad_weight || !d_in_max || !d_gy_max || !d_ws) return M3D_EINVAL;
-  if (((uintptr_t)d_in | (uintptr_t)d_grad_out | (uintptr_t)d_grad_weight | (uintptr_t)d_in_max | (uintptr_t)d_gy_max) & 3) return M3D_EINVAL;
-  if ((uintptr_t)d_ws & 15) return M3D_EINVAL;
-  if (batch <= 0 || cin <= 0 || cout <= 0 || depth <= 0 || height <= 0 || width <= 0) return M3D_EINVAL;
+  if (check_args(d_in, d_grad_out, d_grad_weight, d_in_max, d_gy_max, d_ws) != M3D_OK) return M3D_EINVAL;
+  if (!extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
   if (!m3d_conv3d_wgrad_f16x2_supported(batch, cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
   if (ws_bytes < m3d_conv3d_wgrad_f16x2_workspace_bytes(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
   const WfPlan p = wf_plan(batch, cin, cout, depth, height, width);

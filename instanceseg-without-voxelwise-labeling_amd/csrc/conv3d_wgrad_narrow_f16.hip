@@ -34,28 +34,19 @@
 // loads, so a thread loads its share of the NEXT tile (12 rows of x, up to 3 of gy, whole 8-voxel rows) into registers before the MFMAs
 // of this tile and cuts and writes them behind the next barrier; 356 VGPRs, which one workgroup per CU has.  Tiles, slots, chain and
 // folds are those of dilation 1 for the same shape.  DESIGN, "Dilated narrow-map wgrad on the f16 pipe".
-#include "m3d_common.h"
+// The cut, the MFMA triple and the bound slots are those of f16x2.h; the partial store, the reduce kernel and the slot rule those of
+// conv3d_wgrad_f16_common.h.
+#include "conv3d_wgrad_f16_common.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
 constexpr int WN_NT = 192;                                  // 3 waves: wave = dz
-constexpr int WN_SLOTS_IN = 32;                             // slots of an operand-bound array (m3d_conv3d_zw_slots)
 constexpr int TZ = 2, TY = 8, TX = 8;                       // voxel tile: 16 rows = 8 k-steps of two rows
 constexpr int MAX_W = TX;
 constexpr int GROWS = TZ * TY, KSTEPS = GROWS / 2;
 constexpr int MFMA_PER_TILE = KSTEPS * 3;                   // per accumulator: 8 k-steps x (hh + hl + lh)
-constexpr int WN_MAX_TILES = 16;                            // tiles of a slot
-constexpr int WN_CHAIN = WN_MAX_TILES * MFMA_PER_TILE;      // 384: the longest run of MFMAs into one accumulator
+constexpr int WN_CHAIN = WG_MAX_TILES * MFMA_PER_TILE;      // 384: the longest run of MFMAs into one accumulator
 static_assert(WN_CHAIN <= 384, "chain");
-constexpr int WN_TARGET_WGS = 512;                          // two workgroups per CU
-constexpr int RG = 8;                                       // strided groups of the reduce kernel
 constexpr long long WN_MAX_WGS = 0xFFFFFFFFll / WN_NT;      // a launch takes fewer than 2^32 threads
 constexpr int GP = GROWS * 16 + 16;                         // 272: channel pitch of the gy image
 constexpr int G_PART = 32 * GP;
@@ -76,24 +67,6 @@ struct Halo {
 static_assert(Halo<1>::LDS_BYTES == 59392 && Halo<2>::LDS_BYTES == 92160 && Halo<2>::XP == 1168, "LDS budget");
 
 struct WnPlan { int tiles_y, tiles_z, NT, cbs, ibs, tps, slots; long long n; };
-
-__device__ __forceinline__ float bound_of_slots(const float* __restrict__ slots, int lane) {
-  float m = slots[lane & (WN_SLOTS_IN - 1)];
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  return m;
-}
-
-// the cut of the contract: v = a s (exact), h = fp16(v), l = fp16(v - h)
-__device__ __forceinline__ void cut(float a, float s, _Float16& h, _Float16& l) {
-  const float v = a * s;
-  h = (_Float16)v;
-  l = (_Float16)(v - (float)h);
-}
-
-__device__ __forceinline__ unsigned pack2(_Float16 a, _Float16 b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
 
 // four consecutive x of one row from column xf >= 0, zeros at columns >= W; p points at column xf of the row and is not dereferenced
 // outside the row (so no load starts before the image or ends behind it)
@@ -140,8 +113,8 @@ __global__ __launch_bounds__(WN_NT, Halo<DIL>::WGS_PER_CU) void conv3d_wgrad_nar
   const size_t HW = (size_t)H * W, DHW = HW * D;
 
   float sx, sg, inv_;
-  m3d::f16_scale_of(bound_of_slots(x_max, lane), sx, inv_);
-  m3d::f16_scale_of(bound_of_slots(g_max, lane), sg, inv_);
+  f16_scale_of(bound_of_slots(x_max, lane), sx, inv_);
+  f16_scale_of(bound_of_slots(g_max, lane), sg, inv_);
 
   f32x16 acc[3][3];
 #pragma unroll
@@ -291,55 +264,12 @@ __global__ __launch_bounds__(WN_NT, Halo<DIL>::WGS_PER_CU) void conv3d_wgrad_nar
         for (int dx = 0; dx < 3; ++dx) {
           const f16x8 bh = __builtin_bit_cast(f16x8, dx == 0 ? f0[0] : dx == 1 ? w[0] : f2[0]);
           const f16x8 bl = __builtin_bit_cast(f16x8, dx == 0 ? f0[1] : dx == 1 ? w[1] : f2[1]);
-          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[dy][dx], 0, 0, 0);
-          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[dy][dx], 0, 0, 0);
-          acc[dy][dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[dy][dx], 0, 0, 0);
+          mfma3(ah, al, bh, bl, acc[dy][dx]);
         }
       }
     }
   }
-  // ---- this wave's nine taps of the slot's partial: acc[i = co][j = ci], col j = lane & 31, row i = (g & 3) + 8 (g >> 2) + 4 h
-  float* pp = partial + (size_t)slot * pl.n;
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int tap = dz * 9 + dy * 3 + dx;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int co = cb * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
-        pp[((size_t)tap * cout + co) * cin + ib * 32 + r] = acc[dy][dx][g];
-      }
-    }
-}
-
-// dW[co][ci][tap] = (sum over the slots in a fixed order) / s_g / s_x: a block is 32 consecutive partial elements x RG strided groups
-__global__ __launch_bounds__(256) void conv3d_wgrad_narrow_f16_reduce_kernel(const float* __restrict__ partial, int slots, long long n,
-                                                                             int cin, int cout, const float* __restrict__ x_max,
-                                                                             const float* __restrict__ g_max, float* __restrict__ dw) {
-  __shared__ float sm[RG][32];
-  const int e = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const long long i = (long long)blockIdx.x * 32 + e;                 // n is a multiple of 32 * 32 * 27
-  float s_, inv_x, inv_g;
-  m3d::f16_scale_of(bound_of_slots(x_max, threadIdx.x & 63), s_, inv_x);
-  m3d::f16_scale_of(bound_of_slots(g_max, threadIdx.x & 63), s_, inv_g);
-  float sum = 0.f;
-  for (int s = g; s < slots; s += RG) sum += partial[(size_t)s * n + i];
-  sm[g][e] = sum;
-  __syncthreads();
-  if (g == 0) {
-    float tot = sm[0][e];
-#pragma unroll
-    for (int k = 1; k < RG; ++k) tot += sm[k][e];
-    const long long cc = (long long)cout * cin;
-    const int tap = (int)(i / cc);
-    const long long rem = i - tap * cc;                                // co * cin + ci
-    dw[rem * 27 + tap] = tot * inv_g * inv_x;
-  }
-}
-
-bool extents_ok(int batch, int cin, int cout, int D, int H, int W) {
-  return batch > 0 && cin > 0 && cout > 0 && D > 0 && H > 0 && W > 0;
+  store_partial(partial + (size_t)slot * pl.n, acc, dz, cb, ib, r, h, cin, cout);
 }
 
 bool wn_shape_ok(int batch, int cin, int cout, int D, int H, int W) {
@@ -355,11 +285,7 @@ WnPlan wn_plan(int batch, int cin, int cout, int D, int H) {
   WnPlan p;
   p.tiles_y = (H + TY - 1) / TY; p.tiles_z = (D + TZ - 1) / TZ;
   p.NT = batch * p.tiles_y * p.tiles_z;
-  p.cbs = cout / 32; p.ibs = cin / 32;
-  long long tps = (long long)p.NT * p.cbs * p.ibs / WN_TARGET_WGS;      // a function of the shape only
-  p.tps = (int)(tps < 1 ? 1 : tps > WN_MAX_TILES ? WN_MAX_TILES : tps);
-  p.slots = (p.NT + p.tps - 1) / p.tps;
-  p.n = (long long)cout * cin * 27;
+  slot_rule(p, cin, cout);
   return p;
 }
 
@@ -376,79 +302,42 @@ int wn_launch(const float* d_in, const float* d_grad_out, float* d_grad_weight, 
                      depth, height, width, p);
   int rc = m3d::check_launch(DIL == 1 ? "conv3d_wgrad_narrow_f16x2" : "conv3d_wgrad_narrow_dilated_f16x2");
   if (rc != M3D_OK) return rc;
-  hipLaunchKernelGGL(conv3d_wgrad_narrow_f16_reduce_kernel, dim3((unsigned)(p.n / 32)), dim3(256), 0, st, partial, p.slots, p.n, cin,
+  hipLaunchKernelGGL(conv3d_wgrad_f16_reduce_kernel, dim3((unsigned)(p.n / 32)), dim3(256), 0, st, partial, p.slots, p.n, cin,
                      cout, d_in_max, d_gy_max, d_grad_weight);
   return m3d::check_launch(DIL == 1 ? "conv3d_wgrad_narrow_f16x2_reduce" : "conv3d_wgrad_narrow_dilated_f16x2_reduce");
 }
 
 }  // namespace
 
-M3D_API int m3d_conv3d_wgrad_narrow_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width) {
+// The entry points that take the dilation (1 or 2) do the work.  The tiles and the slot rule do not depend on it, so the shape checks,
+// the plan and the workspace are the same for both.
+M3D_API int m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width, int dilation) {
+  if (dilation != 1 && dilation != 2) return 0;
   if (!wn_shape_ok(batch, cin, cout, depth, height, width)) return 0;
   const WnPlan p = wn_plan(batch, cin, cout, depth, height);
   return (long long)p.slots * p.cbs * p.ibs <= WN_MAX_WGS ? 1 : 0;
 }
 
-M3D_API size_t m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width) {
-  if (!m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width)) return 0;
-  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
-  return (size_t)p.slots * (size_t)p.n * sizeof(float);
-}
-
-M3D_API int m3d_conv3d_wgrad_narrow_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int* tile_z, int* slots,
-                                               int* tiles_per_slot, int* chain, int* folds) {
-  if (!extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
-  if (!m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
-  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
-  if (tile_z) *tile_z = TZ;
-  if (slots) *slots = p.slots;
-  if (tiles_per_slot) *tiles_per_slot = p.tps;
-  if (chain) *chain = p.tps * MFMA_PER_TILE;
-  // fp32 operations on an output behind its MFMA chain: the adds of its strided group (the first partial is added to 0), the RG - 1 adds
-  // of the group sums, the two scale multiplies
-  if (folds) *folds = (p.slots + RG - 1) / RG + (RG - 1) + 2;
-  return M3D_OK;
-}
-
-M3D_API int m3d_conv3d_wgrad_narrow_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
-                                          int depth, int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws,
-                                          size_t ws_bytes, void* stream) {
-  if (!d_in || !d_grad_out || !d_grad_weight || !d_in_max || !d_gy_max || !d_ws) return M3D_EINVAL;
-  if (((uintptr_t)d_in | (uintptr_t)d_grad_out | (uintptr_t)d_grad_weight | (uintptr_t)d_in_max | (uintptr_t)d_gy_max) & 3) return M3D_EINVAL;
-  if ((uintptr_t)d_ws & 15) return M3D_EINVAL;
-  if (!extents_ok(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
-  if (!m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width)) return M3D_EUNSUPPORTED;
-  if (ws_bytes < m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(batch, cin, cout, depth, height, width)) return M3D_EINVAL;
-  return wn_launch<1>(d_in, d_grad_out, d_grad_weight, batch, cin, cout, depth, height, width, d_in_max, d_gy_max, (float*)d_ws,
-                      wn_plan(batch, cin, cout, depth, height), m3d::as_stream(stream));
-}
-
-// The entry points that take the dilation (1 or 2).  The tiles and the slot rule do not depend on it, so the shape checks, the plan and
-// the workspace are those above; dilation 1 is the launch above.
-M3D_API int m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width, int dilation) {
-  if (dilation != 1 && dilation != 2) return 0;
-  return m3d_conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, depth, height, width);
-}
-
 M3D_API size_t m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width,
                                                                      int dilation) {
-  if (dilation != 1 && dilation != 2) return 0;
-  return m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(batch, cin, cout, depth, height, width);
+  if (!m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(batch, cin, cout, depth, height, width, dilation)) return 0;
+  const WnPlan p = wn_plan(batch, cin, cout, depth, height);
+  return (size_t)p.slots * (size_t)p.n * sizeof(float);
 }
 
 M3D_API int m3d_conv3d_wgrad_narrow_dilated_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int dilation,
                                                        int* tile_z, int* slots, int* tiles_per_slot, int* chain, int* folds) {
   if (!extents_ok(batch, cin, cout, depth, height, width) || dilation < 1) return M3D_EINVAL;
-  if (dilation > 2) return M3D_EUNSUPPORTED;
-  return m3d_conv3d_wgrad_narrow_f16x2_plan(batch, cin, cout, depth, height, width, tile_z, slots, tiles_per_slot, chain, folds);
+  if (!m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(batch, cin, cout, depth, height, width, dilation)) return M3D_EUNSUPPORTED;
+  if (tile_z) *tile_z = TZ;
+  report_plan(wn_plan(batch, cin, cout, depth, height), MFMA_PER_TILE, slots, tiles_per_slot, chain, folds);
+  return M3D_OK;
 }
 
 M3D_API int m3d_conv3d_wgrad_narrow_dilated_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin,
                                                   int cout, int depth, int height, int width, int dilation, const float* d_in_max,
                                                   const float* d_gy_max, void* d_ws, size_t ws_bytes, void* stream) {
-  if (!d_in || !d_grad_out || !d_grad_weight || !d_in_max || !d_gy_max || !d_ws) return M3D_EINVAL;
-  if (((uintptr_t)d_in | (uintptr_t)d_grad_out | (uintptr_t)d_grad_weight | (uintptr_t)d_in_max | (uintptr_t)d_gy_max) & 3) return M3D_EINVAL;
-  if ((uintptr_t)d_ws & 15) return M3D_EINVAL;
+  if (check_args(d_in, d_grad_out, d_grad_weight, d_in_max, d_gy_max, d_ws) != M3D_OK) return M3D_EINVAL;
   if (!extents_ok(batch, cin, cout, depth, height, width) || dilation < 1) return M3D_EINVAL;
   if (!m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(batch, cin, cout, depth, height, width, dilation)) return M3D_EUNSUPPORTED;
   if (ws_bytes < m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes(batch, cin, cout, depth, height, width, dilation)) return M3D_EINVAL;
@@ -457,4 +346,25 @@ M3D_API int m3d_conv3d_wgrad_narrow_dilated_f16x2(const float* d_in, const float
   return dilation == 1
              ? wn_launch<1>(d_in, d_grad_out, d_grad_weight, batch, cin, cout, depth, height, width, d_in_max, d_gy_max, (float*)d_ws, p, st)
              : wn_launch<2>(d_in, d_grad_out, d_grad_weight, batch, cin, cout, depth, height, width, d_in_max, d_gy_max, (float*)d_ws, p, st);
+}
+
+// The entry points without the argument: dilation 1.
+M3D_API int m3d_conv3d_wgrad_narrow_f16x2_supported(int batch, int cin, int cout, int depth, int height, int width) {
+  return m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(batch, cin, cout, depth, height, width, 1);
+}
+
+M3D_API size_t m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(int batch, int cin, int cout, int depth, int height, int width) {
+  return m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes(batch, cin, cout, depth, height, width, 1);
+}
+
+M3D_API int m3d_conv3d_wgrad_narrow_f16x2_plan(int batch, int cin, int cout, int depth, int height, int width, int* tile_z, int* slots,
+                                               int* tiles_per_slot, int* chain, int* folds) {
+  return m3d_conv3d_wgrad_narrow_dilated_f16x2_plan(batch, cin, cout, depth, height, width, 1, tile_z, slots, tiles_per_slot, chain, folds);
+}
+
+M3D_API int m3d_conv3d_wgrad_narrow_f16x2(const float* d_in, const float* d_grad_out, float* d_grad_weight, int batch, int cin, int cout,
+                                          int depth, int height, int width, const float* d_in_max, const float* d_gy_max, void* d_ws,
+                                          size_t ws_bytes, void* stream) {
+  return m3d_conv3d_wgrad_narrow_dilated_f16x2(d_in, d_grad_out, d_grad_weight, batch, cin, cout, depth, height, width, 1, d_in_max,
+                                               d_gy_max, d_ws, ws_bytes, stream);
 }

@@ -20,7 +20,7 @@
 // Roofline: MFMA (bf16, 2.5 PFLOP/s dense): 6 x 2 x 27 x Cin x Cout issued FLOP per voxel.
 #include <type_traits>
 
-#include "m3d_common.h"
+#include "f16x2.h"
 
 // timing-only ablation builds (make x3_ablate, tools/bench_x3.py; WRONG results): 1 = no MFMAs, 2 = no fragment reads, 4 = no weight
 // staging (loads, LDS writes), 8 = no per-step barrier, 16 = no flush
@@ -30,11 +30,9 @@
 
 namespace {
 
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TX = 16, TY = 4, TZ = 4, HX = TX + 2, HY = TY + 2, HZ = TZ + 2, NHV = HX * HY * HZ;   // 648 halo voxels
 constexpr int TM = 64;                                  // output channels per workgroup
@@ -52,7 +50,6 @@ constexpr int W_SLOTS = 3;
 constexpr int lds_bytes(int npl) { return (in_units(npl) + W_SLOTS * w_units(npl)) * 16; }
 constexpr int LDS_BYTES = lds_bytes(3);                                   // 80 640 B: two workgroups per CU (161 280 of 163 840); f16x2: 53 760 B
 constexpr int NTASK = (2 * NHV + NT - 1) / NT;          // staging tasks per thread and chunk: (halo voxel, 8-channel group)
-constexpr int acc_row(int g) { return (g & 3) + 8 * (g >> 2); }      // accumulator register g -> row of its 32 x 32 block (+ 4 * (lane >> 5))
 
 // packed[cout tile][step = chunk * 27 + tap][piece][k half][row 64] units of 8 bf16 <- weight [cout][cin][27] fp32 (relu: relu(W) first)
 __global__ __launch_bounds__(256) void conv3d_x3_pack_kernel(const float* __restrict__ w, int cin, int cout, int relu, u32x4* __restrict__ packed) {
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(256) void conv3d_x3_pack_kernel(const float* __rest
 __global__ __launch_bounds__(256) void conv3d_x3f_pack_kernel(const float* __restrict__ w, int cin, int cout, int relu, u32x4* __restrict__ packed,
                                                               const float* __restrict__ wamax) {
   float sw, inv;
-  m3d::f16_scale_of(*wamax, sw, inv);
+  f16_scale_of(*wamax, sw, inv);
   const int chunks = cin / 16, ntile = (cout + TM - 1) / TM;
   const long long total = (long long)ntile * chunks * 27 * 2 * TM;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
@@ -109,8 +106,7 @@ __global__ __launch_bounds__(256) void conv3d_x3f_pack_kernel(const float* __res
         float v = co < cout ? w[((size_t)co * cin + ch * 16 + 8 * kh + 2 * j + u) * 27 + tap] : 0.f;
         if (relu && !(v > 0.f)) v = 0.f;
         v *= sw;
-        const _Float16 h = (_Float16)v;
-        hh[u] = h; ll[u] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, u);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -184,8 +180,8 @@ __global__ __launch_bounds__(NT, 2) void conv3d_x3_kernel(X3Args a) {
   float xs = 1.f, inv_x = 1.f, inv_w = 1.f;                        // F16: operand scales (powers of two) and what undoes them at the flush
   if constexpr (F16) {
     float sw_;
-    m3d::f16_scale_of(*a.in_max - off, xs, inv_x);
-    m3d::f16_scale_of(*a.wamax, sw_, inv_w);
+    f16_scale_of(*a.in_max - off, xs, inv_x);
+    f16_scale_of(*a.wamax, sw_, inv_w);
   }
 
   // ---- staging tasks of this thread: task = tid + NT * i -> (8-channel group g = task / NHV, halo voxel hv = task % NHV)
@@ -226,8 +222,8 @@ __global__ __launch_bounds__(NT, 2) void conv3d_x3_kernel(X3Args a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float v0 = in ? (sx[i][2 * j] - off) * xs : 0.f, v1 = in ? (sx[i][2 * j + 1] - off) * xs : 0.f;
-          const f16x2 hh = {(_Float16)v0, (_Float16)v1};
-          const f16x2 ll = {(_Float16)(v0 - (float)hh[0]), (_Float16)(v1 - (float)hh[1])};
+          f16x2 hh, ll;
+          cut(v0, v1, hh, ll);
           ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
         }
         lds[t_dst[i]] = ph;

@@ -23,17 +23,13 @@
 // halo columns x < 0 and x >= 8 are padding in every chunk: they are written as zero units ONCE, before the first chunk, and staging
 // covers the 8 columns that can hold data - 12 x 8 x 8 voxels x 2 channel halves = 1536 items, exactly 6 per thread (48 raw registers
 // against the 40 of dilation 1), which keeps the kernel at two workgroups per CU without scratch.
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
 
 constexpr int ZN_NT = 256;
-constexpr int ZN_SLOTS = 32;                       // slots of an absmax array (m3d_conv3d_zw_slots)
 constexpr int ZN_STEP_UNITS = 2 * 2 * 2 * 32;      // packed weights of one (chunk, tap): [block 2][hi / lo][k half][row 32] 16-byte units
 constexpr int ZN_TY = 8, ZN_TZ = 4;                // tile: 8 x 8 x 4 voxels (x: the whole row)
 // the geometry of the halo tile at dilation DIL (1 or 2)
@@ -54,7 +50,6 @@ struct ZnGeom {
 };
 static_assert(ZnGeom<1>::PLANE == 104 && ZnGeom<1>::ITEMS == 1200 && ZnGeom<1>::PER == 5 && !ZnGeom<1>::DYNAMIC, "dilation 1 as it was");
 static_assert(ZnGeom<2>::PLANE == 152 && ZnGeom<2>::ITEMS == 1536 && ZnGeom<2>::PER == 6 && ZnGeom<2>::LDS_BYTES == 77824, "dilation 2");
-constexpr int acc_row(int g) { return (g & 3) + 8 * (g >> 2); }
 
 // column (lane % 32) of a column block -> (x, row y, row z) inside the block's 8 x 2 x 2 voxels
 __device__ __forceinline__ void col_xyz(int c, int* x, int* y, int* z) {
@@ -74,7 +69,7 @@ template <bool DGRAD>
 __global__ __launch_bounds__(256) void zn_pack_kernel(const float* __restrict__ w, int cin, int cout, u32x4* __restrict__ packed,
                                                       const float* __restrict__ wamax) {
   float sw, inv;
-  m3d::f16_scale_of(*wamax, sw, inv);
+  f16_scale_of(*wamax, sw, inv);
   const int chunks = cin / 16, ncg = (cout + 63) / 64;
   const long long total = (long long)ncg * chunks * 27 * 2 * 64;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
@@ -94,8 +89,7 @@ __global__ __launch_bounds__(256) void zn_pack_kernel(const float* __restrict__ 
           const int ci = ch * 16 + 8 * kh + 2 * j + u;
           v = (DGRAD ? w[((size_t)ci * cout + co) * 27 + (26 - tap)] : w[((size_t)co * cin + ci) * 27 + tap]) * sw;
         }
-        const _Float16 h = (_Float16)v;
-        hh[u] = h; ll[u] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, u);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -133,12 +127,12 @@ __global__ __launch_bounds__(ZN_NT, DIL) void conv3d_zn_kernel(ZnArgs a) {
   // ---- operand scales (powers of two): the input's bound = the largest slot, the weights' as packed
   float xs, inv_x, inv_w;
   {
-    float im = a.in_max[lane & (ZN_SLOTS - 1)];
+    float im = a.in_max[lane & (kBoundSlots - 1)];      // max_of_slot_lanes of f16x2.h, open-coded: see there
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) im = fmaxf(im, __shfl_xor(im, o));
     float sw_;
-    m3d::f16_scale_of(im, xs, inv_x);
-    m3d::f16_scale_of(*a.wamax, sw_, inv_w);
+    f16_scale_of(im, xs, inv_x);
+    f16_scale_of(*a.wamax, sw_, inv_w);
   }
   const float un = inv_x * inv_w;
 
@@ -182,8 +176,7 @@ __global__ __launch_bounds__(ZN_NT, DIL) void conv3d_zn_kernel(ZnArgs a) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const float v = raw[q][2 * j + e] * xs;
-          const _Float16 h = (_Float16)v;
-          hh[e] = h; ll[e] = (_Float16)(v - (float)h);
+          cut(v, hh, ll, e);
         }
         ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
       }
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(ZN_NT, DIL) void conv3d_zn_kernel(ZnArgs a) {
     __syncthreads();
     if (tid == 0) {
       const float m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-      if (m > 0.f) atomicMax(a.out_max + (blockIdx.x & (ZN_SLOTS - 1)), __float_as_uint(m));
+      if (m > 0.f) atomicMax(a.out_max + (blockIdx.x & (kBoundSlots - 1)), __float_as_uint(m));
     }
   }
 }

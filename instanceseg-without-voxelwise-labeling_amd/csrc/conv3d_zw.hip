@@ -32,7 +32,7 @@
 // per MFMA, 5e-6 at 256 input channels - below the fp32 Winograd kernels' error; the accumulators run over all of K.
 #include <type_traits>
 
-#include "m3d_common.h"
+#include "f16x2.h"
 #include "conv3d_wino24.h"      // m3d_w24::PrepEpi: the fused `prepare` epilogue of the PRM strips (same contract as the fp32 kernel's)
 
 // diagnostic build only (make zw_stamps; tools/zw_stamps.py): s_memtime of wave 0 of every workgroup at every tap of its SECOND unit
@@ -46,16 +46,10 @@ M3D_API void m3d_debug_set_stamp_buffer_zw(void* p) { g_zw_stamps = (unsigned lo
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
 
 constexpr int ZW_NT = 512;
-constexpr int ZW_SLOTS = 32;                       // slots of an absmax array
 constexpr int ZW_STEP_UNITS = 4 * 2 * 128;         // packed weights of one (chunk, tap): [point 4][block 2][hi / lo][k half][row 32] 16-byte units
-constexpr int acc_row(int g) { return (g & 3) + 8 * (g >> 2); }
 
 template <int XB>
 struct ZwCfg {
@@ -92,7 +86,7 @@ template <bool DGRAD>
 __global__ __launch_bounds__(256) void zw_pack_kernel(const float* __restrict__ w, int cin, int cout, u32x4* __restrict__ packed,
                                                       const float* __restrict__ wamax) {
   float sw, inv;
-  m3d::f16_scale_of(1.5f * *wamax, sw, inv);        // |U1|, |U2| <= 1.5 max |g|
+  f16_scale_of(1.5f * *wamax, sw, inv);        // |U1|, |U2| <= 1.5 max |g|
   const int chunks = cin / 16, ncg = (cout + 63) / 64;
   const long long total = (long long)ncg * chunks * 9 * 4 * 2 * 64;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
@@ -115,8 +109,7 @@ __global__ __launch_bounds__(256) void zw_pack_kernel(const float* __restrict__ 
           const double t = point == 0 ? g0 : point == 1 ? 0.5 * (g0 + g1 + g2) : point == 2 ? 0.5 * (g0 - g1 + g2) : g2;
           v = (float)t * sw;
         }
-        const _Float16 h = (_Float16)v;
-        hh[u] = h; ll[u] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, u);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -162,12 +155,10 @@ __global__ __launch_bounds__(ZW_NT, 2) void conv3d_zw_kernel(ZwArgs a) {
   // ---- operand scales (powers of two): input bound = the largest slot x 2 (a V is a sum of two planes), weights as packed
   float xs, inv_x, inv_w;
   {
-    float im = a.col_bound ? 0.f : a.in_max[lane & (ZW_SLOTS - 1)];      // (strip mode: one scale per window, see Stage::xs)
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) im = fmaxf(im, __shfl_xor(im, o));
+    const float im = max_of_slot_lanes(a.col_bound ? 0.f : a.in_max[lane & (kBoundSlots - 1)]);      // (strip mode: one scale per window, see Stage::xs)
     float sw_;
-    m3d::f16_scale_of(2.f * im, xs, inv_x);
-    m3d::f16_scale_of(1.5f * *a.wamax, sw_, inv_w);
+    f16_scale_of(2.f * im, xs, inv_x);
+    f16_scale_of(1.5f * *a.wamax, sw_, inv_w);
   }
   const float un = inv_x * inv_w;
 
@@ -212,7 +203,7 @@ __global__ __launch_bounds__(ZW_NT, 2) void conv3d_zw_kernel(ZwArgs a) {
     if (a.col_bound) {                                  // this halo column's window: its own power-of-two scale
       const int p = min(max(sx, 0) / a.pitch, a.npeaks - 1);
       float inv_;
-      m3d::f16_scale_of(2.f * a.col_bound[32 * p], st.xs, inv_);
+      f16_scale_of(2.f * a.col_bound[32 * p], st.xs, inv_);
     }
     return st;
   };
@@ -247,8 +238,7 @@ __global__ __launch_bounds__(ZW_NT, 2) void conv3d_zw_kernel(ZwArgs a) {
         const int ch = 2 * j + u;
         const float da = raw[PA_[k]][ch], db = raw[PB_[k]][ch];
         const float v = (k == 1 ? da + db : da - db) * xs_;
-        const _Float16 h = (_Float16)v;
-        hh[u] = h; ll[u] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, u);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -307,7 +297,7 @@ __global__ __launch_bounds__(ZW_NT, 2) void conv3d_zw_kernel(ZwArgs a) {
     if (a.col_bound) {
       const int p = min((cur.x0 + 4 * ((lane & 31) % (XB / 4))) / a.pitch, a.npeaks - 1);
       float s_;
-      m3d::f16_scale_of(2.f * a.col_bound[32 * p], s_, inv_e);
+      f16_scale_of(2.f * a.col_bound[32 * p], s_, inv_e);
     }
     ZW_STAMP(0);
     commit_in(0, S.xs);
@@ -476,7 +466,6 @@ __global__ __launch_bounds__(ZW_NT, 2) void conv3d_zw_kernel(ZwArgs a) {
             const bool okr = ok & (qz >= 0) & (qz < pe.MD) & (qy >= 0) & (qy < pe.MH);
             rbase[zz] = okr ? qz * MHW + qy * pe.MW : -1;
           }
-          typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
           f32x4 xn[4][2], nn[4][2];
           float scv[4];
 #pragma unroll
@@ -612,7 +601,7 @@ __global__ __launch_bounds__(ZW_NT, 2) void conv3d_zw_kernel(ZwArgs a) {
       float m = wm[0];
 #pragma unroll
       for (int k = 1; k < 8; ++k) m = fmaxf(m, wm[k]);
-      if (m > 0.f) atomicMax(a.out_max + (blockIdx.x & (ZW_SLOTS - 1)), __float_as_uint(m));
+      if (m > 0.f) atomicMax(a.out_max + (blockIdx.x & (kBoundSlots - 1)), __float_as_uint(m));
     }
   }
 }
@@ -688,13 +677,13 @@ M3D_API int m3d_conv3d_zw_pack_dgrad(const float* d_weight, int cin, int cout, v
   return m3d::check_launch("conv3d_zw_pack_dgrad");
 }
 
-M3D_API int m3d_conv3d_zw_slots(void) { return ZW_SLOTS; }
+M3D_API int m3d_conv3d_zw_slots(void) { return kBoundSlots; }
 
 /* d_slots[0] = max |x|, the other 31 slots 0: an operand bound for m3d_conv3d_zw_forward from a sweep of x (the first layer of a chain) */
 M3D_API int m3d_conv3d_zw_bound_of(const float* d_x, long long n, float* d_slots, void* stream) {
   if (!d_slots) return M3D_EINVAL;
   hipStream_t st = m3d::as_stream(stream);
-  if (hipMemsetAsync(d_slots, 0, ZW_SLOTS * sizeof(float), st) != hipSuccess) return M3D_ELAUNCH;
+  if (hipMemsetAsync(d_slots, 0, kBoundSlots * sizeof(float), st) != hipSuccess) return M3D_ELAUNCH;
   return m3d_absmax(d_x, n, d_slots, stream);
 }
 

@@ -30,7 +30,7 @@
 // These kernels stay on the fp32-input MFMA and stay the default.  The same two GEMMs on the f16 matrix cores (the f16x2 cut on the raw
 // operands, opt-in, 1.8 x - 2.2 x faster at the fc1 shapes and slower at fc2) are fc_backward_f16.hip: DESIGN.md, "Box-head backward on
 // the f16 pipe".
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
@@ -40,7 +40,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int BT = 128, BR = 32, LSA = BR + 4;                     // tile edge, reduction chunk, padded row stride of dgrad's gy tile
 constexpr int kBFloats = BR * BT;                                  // the reduction-major tile: [32 reduction rows][128]
 constexpr int kSlots = 512;                                        // resident workgroups: 256 CUs x 2
-constexpr int KGmap(int g) { return (g & 3) + 8 * (g >> 2); }      // accumulator register g -> row inside a 32x32 block (+4*(lane>>5))
+using m3d::f16x2::acc_row;      // accumulator register g -> row inside a 32x32 block (+4*(lane>>5))
 
 struct FcbArgs {
   const float* gy; const float* b; float* out; float* part; float* gb; float* gb_part;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void fc_backward_kernel(FcbArgs a) {
     compute(lds);
   }
 
-  // ---- epilogue: register g of block (i, j) is out[r0 + wm*64 + i*32 + KG(g) + 4*fh][k0 + wn*64 + j*32 + fr]: for a fixed g the
+  // ---- epilogue: register g of block (i, j) is out[r0 + wm*64 + i*32 + acc_row(g) + 4*fh][k0 + wn*64 + j*32 + fr]: for a fixed g the
   // half-wave writes one 128-byte row segment
   const bool direct = a.slices == 1;
   float* dst = direct ? a.out : a.part + (size_t)slice * a.rows * K;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void fc_backward_kernel(FcbArgs a) {
       const int rb = r0 + wm * 64 + i * 32 + 4 * fh;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int r = rb + KGmap(g);
+        const int r = rb + acc_row(g);
         if (r < a.rows && k < a.K) dst[(size_t)r * K + k] = acc[i][j][g];
       }
     }

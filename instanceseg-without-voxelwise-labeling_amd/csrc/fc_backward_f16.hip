@@ -2,7 +2,7 @@
 // on the operands as PyTorch stores them - the two GEMMs of fc_backward.hip with v_mfma_f32_32x32x16_f16 instead of 32x32x2_f32:
 //     dgrad   gx[M,K] = gy[M,N] . W[N,K]           (reduction over N)
 //     wgrad   gw[N,K] = gy[M,N]^T . x[M,K]         (reduction over M),   gb[N] = sum_m gy[m,n] (uncut fp32) out of the same launch
-// Every operand value is multiplied by its tensor's power of two (m3d::f16_scale_of of the tensor's bound: one scale per operand) and cut
+// Every operand value is multiplied by its tensor's power of two (f16_scale_of of the tensor's bound: one scale per operand) and cut
 // into hi = fp16(v), lo = fp16(v - hi) ONCE, on its way from the global-load registers to LDS; three MFMA products (hh, hl, lh) per
 // fp32 product accumulate in fp32 and the scales are undone (exactly) in the epilogue.  No packed or transposed copy of W, x or gy
 // exists: the 360 MB matrix is read once (fp32) and its gradient written once.
@@ -39,15 +39,11 @@
 //  * gb: in the workgroups of the first column tile the threads that stage gy add their raw fp32 values, each its 8 rows of every chunk
 //    in row order, and the four k-group sums of a column are added in group order through LDS at the end; slices as the partials.
 //    No atomics anywhere; results are bit-identical run to run.
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
 
 constexpr int BT = 128, BR = 32;                                   // tile edge, reduction chunk
 constexpr int GSB = 128, GSD = 130;                                // fragments per k-group: reduction-major tiles / dgrad's gy tile
@@ -55,7 +51,6 @@ constexpr int kSlots = 512;                                        // resident w
 constexpr int kFoldChunks = 64;                                    // 64 chunks x 6 MFMAs = 384 per accumulator
 constexpr long long kSplitMinWork = 1ll << 24;                     // M N K below this: one launch, no split
 constexpr int kBoundBytes = 256;                                   // head of the workspace: the two swept bounds
-constexpr int KGmap(int g) { return (g & 3) + 8 * (g >> 2); }      // accumulator register g -> row inside a 32x32 block (+4*(lane>>5))
 
 struct FcbArgs {
   const float* gy; const float* b; float* out; float* part; float* gb; float* gb_part;
@@ -75,8 +70,8 @@ __device__ inline float bound_max(const float* __restrict__ b, int n) {
 __device__ __forceinline__ void cut8(const float (&v)[8], u32x4& hi, u32x4& lo) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const f16x2 hh = {(_Float16)v[2 * j], (_Float16)v[2 * j + 1]};
-    const f16x2 ll = {(_Float16)(v[2 * j] - (float)hh[0]), (_Float16)(v[2 * j + 1] - (float)hh[1])};
+    f16x2 hh, ll;
+    cut(v[2 * j], v[2 * j + 1], hh, ll);
     hi[j] = __builtin_bit_cast(unsigned, hh); lo[j] = __builtin_bit_cast(unsigned, ll);
   }
 }
@@ -100,8 +95,8 @@ __global__ __launch_bounds__(256, FOLD ? 1 : 2) void fc_backward_f16_kernel(FcbA
   const size_t N = (size_t)a.N, K = (size_t)a.K;
 
   float sa, ia, sb, ib;                                            // the two scales and their inverses
-  m3d::f16_scale_of(bound_max(a.gy_bound, a.gy_bound_n), sa, ia);
-  m3d::f16_scale_of(bound_max(a.b_bound, a.b_bound_n), sb, ib);
+  f16_scale_of(bound_max(a.gy_bound, a.gy_bound_n), sa, ia);
+  f16_scale_of(bound_max(a.b_bound, a.b_bound_n), sb, ib);
 
   // ---- staging.  Waves 0, 1: B.  Waves 2, 3: gy.  Reduction-major tiles: thread -> (q = t % 32, g = t / 32), rows 8 g + j of the chunk,
   // columns 4 q .. 4 q + 3 (a half-wave load = 512 contiguous bytes of one row).  dgrad's gy tile: thread -> (g = t % 4, row = t / 4 + 32 i),
@@ -219,11 +214,7 @@ __global__ __launch_bounds__(256, FOLD ? 1 : 2) void fc_backward_f16_kernel(FcbA
         bl[j] = __builtin_bit_cast(f16x8, cur[offB + 2 * s * GSB + j * 32 + kBFrags]);
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[j], 0, 0, 0);
-      }
+      for (int j = 0; j < 4; ++j) mfma3(ah, al, bh[j], bl[j], acc[j]);
     }
     if constexpr (FOLD) {
       if (++chained == kFoldChunks) {
@@ -262,14 +253,14 @@ __global__ __launch_bounds__(256, FOLD ? 1 : 2) void fc_backward_f16_kernel(FcbA
     }
   }
 
-  // ---- epilogue: register g of the four blocks is out[row][k0 + 4 fr .. + 3], row = r0 + wave*32 + KG(g) + 4 fh in dgrad and
-  // r0 + 4 (KG(g) + 4 fh) + wave in wgrad: one 16-byte store per lane, a half-wave writes one 512-byte row segment
+  // ---- epilogue: register g of the four blocks is out[row][k0 + 4 fr .. + 3], row = r0 + wave*32 + acc_row(g) + 4 fh in dgrad and
+  // r0 + 4 (acc_row(g) + 4 fh) + wave in wgrad: one 16-byte store per lane, a half-wave writes one 512-byte row segment
   const bool direct = a.slices == 1;
   float* dst = direct ? a.out : a.part + (size_t)slice * a.rows * K;
   const int k = k0 + 4 * fr;
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
-    const int rl = KGmap(g) + 4 * fh;
+    const int rl = acc_row(g) + 4 * fh;
     const int r = r0 + (WGRAD ? 4 * rl + wave : wave * 32 + rl);
     f32x4 v;
 #pragma unroll

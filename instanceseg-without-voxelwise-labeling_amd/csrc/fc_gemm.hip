@@ -22,16 +22,14 @@
 //    bias + ReLU).  slices == 1 stores directly.
 #include <type_traits>
 
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
 
 constexpr int BM = 128, BN = 128, BK = 32, LS = BK + 4;           // LS: padded LDS row stride (floats)
 constexpr int kStageFloats = (BM + BN) * LS;                       // one buffer
-constexpr int KGmap(int g) { return (g & 3) + 8 * (g >> 2); }      // accumulator register g -> row inside a 32x32 block (+4*(lane>>5))
 
 struct FcArgs {
   const float* x; const float* w; const float* bias; float* out; float* part;
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void fc_gemm_kernel(FcArgs a) {
       const int mb = m0 + rbk * 32 + 4 * fh;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int m = mb + KGmap(g);
+        const int m = mb + acc_row(g);
         if (m < a.M && n < a.N) {
           float v = t[j][g];
           if (direct) { v += b; if (a.relu) v = fmaxf(v, 0.f); }
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void fc_gemm_kernel(FcArgs a) {
     compute(lds);
   }
 
-  // ---- epilogue: register g of block (i, j) is out[m0 + wm*64 + i*32 + KG(g) + 4*fh][n0 + wn*64 + j*32 + fr]: for a fixed g the
+  // ---- epilogue: register g of block (i, j) is out[m0 + wm*64 + i*32 + acc_row(g) + 4*fh][n0 + wn*64 + j*32 + fr]: for a fixed g the
   // half-wave writes one 128-byte row segment
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -242,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void fc_gemm_kernel(FcArgs a) {
       const int mb = m0 + wm * 64 + i * 32 + 4 * fh;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int m = mb + KGmap(g);
+        const int m = mb + acc_row(g);
         if (m < a.M && n < a.N) {
           float v = acc[i][j][g];
           if (direct) { v += b; if (a.relu) v = fmaxf(v, 0.f); }
@@ -253,10 +251,9 @@ __global__ __launch_bounds__(256, 2) void fc_gemm_kernel(FcArgs a) {
   }
 }
 
-// Operand bounds that travel with the activations (as conv3d_zw.hip's in_max / out_max): an array of kBoundSlots floats whose largest
+// Operand bounds that travel with the activations (as conv3d_zw.hip's in_max / out_max): an array of kBoundSlots (f16x2.h) floats whose largest
 // entry is >= max |x|.  A consumer takes the largest of the n slots it is given (n = 1: a plain m3d_absmax result); a producer adds
 // the largest |value| it stores with ONE atomic per workgroup into slot (block % kBoundSlots) of a zeroed array.
-constexpr int kBoundSlots = 32;
 
 __device__ inline float bound_max(const float* __restrict__ b, int n) {
   float m = b[0];
@@ -345,7 +342,6 @@ __global__ __launch_bounds__(256) void fc_reduce_kernel(const float* __restrict_
 // SIMD sits in its load-wait / cut / barrier phase two others can issue MFMAs; the next chunk waits in registers during the MFMAs.
 // Roofline: MFMA (bf16, 2.5 PFLOP/s dense): 6 x 2MNK issued FLOP.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int X3_RSW = 16;                        // LDS row stride in dwords: 64 B, no pad; the 16-byte unit u of row r sits at u ^ ((r >> 2) & 3)
 constexpr int X3_PLANE = 128 * X3_RSW;            // dwords of one plane
@@ -394,10 +390,7 @@ __global__ __launch_bounds__(256) void fc_x3_pack_kernel(const float* __restrict
 // Scales: the weight's from its largest magnitude at pack time (kept beside the planes); x's from a caller-supplied bound of max|x|
 // (RoIAlign averages trilinear interpolations, convex combinations of feature-map values: max|feature map| bounds it and is 16 MB to
 // sweep instead of 440) or, without one, from a sweep of x itself.  Products are exact in fp32 (22 bits), sums stay below 2^47.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-using m3d::f16_scale_of;      // scale 2^k with bound * 2^k in [2^14, 2^15) and its inverse (m3d_common.h; no host read of the bound)
 
 __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, long long n, unsigned* __restrict__ out) {
   unsigned m = 0;
@@ -440,8 +433,7 @@ __global__ __launch_bounds__(256) void fc_f16_pack_kernel(const float* __restric
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const float v = (n < N ? w[(size_t)n * K + (size_t)c * 32 + 8 * q + 2 * j + t] : 0.f) * sw;
-        const _Float16 h = (_Float16)v;
-        hh[t] = h; ll[t] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, t);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -571,8 +563,8 @@ __global__ __launch_bounds__(128 * WR, WR == 2 ? 2 : 1) void fc_x3_gemm_kernel(F
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float v0 = sx[i][j >> 1][2 * (j & 1)] * xs, v1 = sx[i][j >> 1][2 * (j & 1) + 1] * xs;
-          const f16x2 hh = {(_Float16)v0, (_Float16)v1};
-          const f16x2 ll = {(_Float16)(v0 - (float)hh[0]), (_Float16)(v1 - (float)hh[1])};
+          f16x2 hh, ll;
+          cut(v0, v1, hh, ll);
           ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
         }
         unsigned* d = lds + (row0 + (NT / 4) * i) * X3_RSW + swq;
@@ -679,7 +671,7 @@ __global__ __launch_bounds__(128 * WR, WR == 2 ? 2 : 1) void fc_x3_gemm_kernel(F
       const int mb = m0 + wm * 64 + i * 32 + 4 * fh;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int m = mb + KGmap(g);
+        const int m = mb + acc_row(g);
         if (m < a.M && n < a.N) {
           float v = acc[i][j][g];
           if constexpr (F16) v = (v * out_s0) * out_s1;            // undo the operand scales (powers of two: exact)
@@ -780,8 +772,8 @@ __global__ __launch_bounds__(512, 1) void fc_x3b_gemm_kernel(FcX3Args a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float v0 = sx[i][j >> 1][2 * (j & 1)] * xs, v1 = sx[i][j >> 1][2 * (j & 1) + 1] * xs;
-          const f16x2 hh = {(_Float16)v0, (_Float16)v1};
-          const f16x2 ll = {(_Float16)(v0 - (float)hh[0]), (_Float16)(v1 - (float)hh[1])};
+          f16x2 hh, ll;
+          cut(v0, v1, hh, ll);
           ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
         }
         unsigned* d = lds + base + (row0 + 128 * i) * X3_RSW + swq;
@@ -940,7 +932,7 @@ __global__ __launch_bounds__(512, 1) void fc_x3b_gemm_kernel(FcX3Args a) {
       const int mb = m0 + wm * 64 + i * 32 + 4 * fh;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int m = mb + KGmap(g);
+        const int m = mb + acc_row(g);
         if (m < a.M && n < a.N) {
           float v = acc[i][j][g];
           if constexpr (F16) v = (v * out_s0) * out_s1;

@@ -14,14 +14,11 @@
 //   W image  [tap][plane][lane] units: the A fragments of the workgroup's 32 output channels.
 // One workgroup = 256 columns x 32 output channels, 8 waves, one accumulator block each; the next chunk's global loads are issued
 // before the chunk's 81 MFMAs per wave and cut / written to LDS after them.
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
 
 constexpr int kC16 = 16;                        // input channels per chunk = K of one MFMA
 constexpr int kWUnits = 27 * 2 * 64;            // 16-byte units of one (cout block, chunk) weight image
@@ -59,7 +56,7 @@ __global__ __launch_bounds__(1024) void relu_absmax_kernel(const float* __restri
 __global__ __launch_bounds__(256) void small_pack_f16_kernel(const float* __restrict__ w, int cout_fwd, int cin_fwd, u32x4* __restrict__ packed,
                                                              int nchunk, long long total, const float* __restrict__ wamax) {
   float sw, inv;
-  m3d::f16_scale_of(*wamax, sw, inv);
+  f16_scale_of(*wamax, sw, inv);
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
     const int lane = (int)(e & 63);
     long long r = e >> 6;
@@ -79,8 +76,7 @@ __global__ __launch_bounds__(256) void small_pack_f16_kernel(const float* __rest
           v = w[((size_t)ci * cin_fwd + co) * 27 + (26 - t)];
           v = v > 0.f ? v * sw : 0.f;
         }
-        const _Float16 h = (_Float16)v;
-        hh[u] = h; ll[u] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, u);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void prm_small_dgrad_f16_kernel(Smal
       if (pp < q.P) {
         g_src[i] = (int)(((long long)s * q.cin + 8 * g) * V + vv);
         float inv;
-        m3d::f16_scale_of(q.pamax[pp], g_s[i], inv);
+        f16_scale_of(q.pamax[pp], g_s[i], inv);
       }
     }
   }
@@ -182,8 +178,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void prm_small_dgrad_f16_kernel(Smal
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float v0 = sg[i][2 * j] * g_s[i], v1 = sg[i][2 * j + 1] * g_s[i];
-        const f16x2 hh = {(_Float16)v0, (_Float16)v1};
-        const f16x2 ll = {(_Float16)(v0 - (float)hh[0]), (_Float16)(v1 - (float)hh[1])};
+        f16x2 hh, ll;
+        cut(v0, v1, hh, ll);
         ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
       }
       lB[g_dst[i]] = ph;
@@ -220,8 +216,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void prm_small_dgrad_f16_kernel(Smal
   // channel 8*(e/4) + 4*h + e%4
   if (!col_ok) return;
   float sp, inv_p, swt, inv_w;
-  m3d::f16_scale_of(q.pamax[p], sp, inv_p);
-  m3d::f16_scale_of(*q.wamax, swt, inv_w);
+  f16_scale_of(q.pamax[p], sp, inv_p);
+  f16_scale_of(*q.wamax, swt, inv_w);
   const int qz = q.origins[3 * p] + vz, qy = q.origins[3 * p + 1] + vy, qx = q.origins[3 * p + 2] + vx;
   const bool in = (qz >= 0) & (qz < q.D) & (qy >= 0) & (qy < q.H) & (qx >= 0) & (qx < q.W);
   const size_t pos = in ? ((size_t)qz * q.H + qy) * q.W + qx : 0;

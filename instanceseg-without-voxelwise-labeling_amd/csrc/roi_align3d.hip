@@ -13,11 +13,13 @@
 // with oracle/m3d_oracle.c.
 #include <stddef.h>
 
-#include "m3d_common.h"
+#include "f16x2.h"
 
 #include "roi_align3d_geom.h"   // AxisSample, kMaxTable, make_sample, RoiGeom, roi_geom
 
 namespace {
+
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
 
 // exact reference operation order for output elements [c0,c1) x bins of RoI n (tables already in LDS)
 __device__ inline void roi_exact_forward_range(const float* __restrict__ feat, float* __restrict__ out, const RoiGeom& g,
@@ -573,10 +575,6 @@ template <int KS>
 __global__ __launch_bounds__(256) void roi_align3d_fwd_gemm_kernel(const float* __restrict__ feat, float* __restrict__ out, int B, int C, int S,
                                                                    int H, int W, const int* __restrict__ order, const int* __restrict__ tabs,
                                                                    const float* __restrict__ feat_absmax, int absmax_slots) {
-  typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef float f32x16 __attribute__((ext_vector_type(16)));
   constexpr int K = 16 * KS;
   constexpr int NCB = 2;                                     // channel blocks of 32 per wave and pass (C = 256: one pass)
   __shared__ V3Shared sh;
@@ -611,7 +609,7 @@ __global__ __launch_bounds__(256) void roi_align3d_fwd_gemm_kernel(const float* 
   float fs, inv_f;
   float fmax = feat_absmax[0];                                     // the bound: the largest of its slots (one: an m3d_absmax result)
   for (int i = 1; i < absmax_slots; ++i) fmax = fmaxf(fmax, feat_absmax[i]);
-  m3d::f16_scale_of(fmax, fs, inv_f);
+  f16_scale_of(fmax, fs, inv_f);
   constexpr float kMs = 16384.f, kInvMs = 1.f / 16384.f;     // operator scale 2^14: an axis weight is <= 2 (two samples on one voxel), the
                                                              // y row carries 1 / 8: M <= 2 * 2 * 0.25 = 1 -> <= 2^14 in fp16
   const float* fbase = feat + (size_t)g.batch * C * S * HW + (size_t)sh.rng[0] * HW + sh.rng[2] * W + sh.rng[4];
@@ -637,8 +635,7 @@ __global__ __launch_bounds__(256) void roi_align3d_fwd_gemm_kernel(const float* 
           const unsigned c = kzyx[k];
           float m = (wz[c & 255] * wy[(c >> 8) & 255]) * wx[(c >> 16) & 255];
           m *= (k < d.sub && bok) ? kMs : 0.f;                                 // (a select, not a branch around the table reads)
-          const _Float16 hv = (_Float16)m;
-          hh[u] = hv; ll[u] = (_Float16)(m - (float)hv);
+          cut(m, hh, ll, u);
         }
         ph4[j] = __builtin_bit_cast(unsigned, hh); pl4[j] = __builtin_bit_cast(unsigned, ll);
       }
@@ -669,8 +666,7 @@ __global__ __launch_bounds__(256) void roi_align3d_fwd_gemm_kernel(const float* 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float t = v[j] * fs;
-          const _Float16 hv = (_Float16)t;
-          vh[j] = hv; vl[j] = (_Float16)(t - (float)hv);
+          cut(t, vh, vl, j);
         }
         ah[q][st] = vh; al[q][st] = vl;
       }

@@ -34,7 +34,7 @@
 //  * unit order: blockIdx % 8 is the XCD; one XCD gets a contiguous run of units, and inside a column tile the row tiles are neighbours.
 #include <initializer_list>
 
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
@@ -46,7 +46,7 @@ enum { FWD = 0, DGRAD = 1, WGRAD = 2 };
 constexpr int BT = 128, BR = 32, LSA = BR + 4;                    // tile edge, reduction chunk, padded row stride of a reduction-contiguous tile
 constexpr int kRM = BR * BT, kRC = BT * LSA;                       // floats of a reduction-major / reduction-contiguous tile
 constexpr int kSlots = 512;                                        // resident workgroups: 256 CUs x 2
-constexpr int KGmap(int g) { return (g & 3) + 8 * (g >> 2); }      // accumulator register g -> row inside a 32x32 block (+4*(lane>>5))
+using m3d::f16x2::acc_row;      // accumulator register g -> row inside a 32x32 block (+4*(lane>>5))
 
 struct UpArgs {
   const float* w; const float* x; const float* g; const float* ym; const float* bias;
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void upconv_kernel(UpArgs a) {
     __syncthreads();
   }
 
-  // ---- epilogue: register g of block (i, j) is row r0 + wm*64 + i*32 + KG(g) + 4*fh, column k0 + wn*64 + j*32 + fr
+  // ---- epilogue: register g of block (i, j) is row r0 + wm*64 + i*32 + acc_row(g) + 4*fh, column k0 + wn*64 + j*32 + fr
   if constexpr (MODE == FWD) {
     // rows are n = (co,a,b,c): registers g, g+1 (g even) are c = 0, 1 - one float2 of the 2x tensor; lanes are neighbouring x
 #pragma unroll
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void upconv_kernel(UpArgs a) {
         const int nb = r0 + wm * 64 + i * 32 + 4 * fh;
 #pragma unroll
         for (int g = 0; g < 16; g += 2) {
-          const int n = nb + KGmap(g);
+          const int n = nb + acc_row(g);
           if (n >= a.NC) continue;
           const int co = n >> 3;
           const float bv = a.bias ? a.bias[co] : 0.f;
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void upconv_kernel(UpArgs a) {
         const int rbase = r0 + wm * 64 + i * 32 + 4 * fh;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const int r = rbase + KGmap(g);
+          const int r = rbase + acc_row(g);
           if (r < a.rows && k < a.cols) dst[(size_t)r * cols + k] = acc[i][j][g];
         }
       }

@@ -41,31 +41,27 @@
 //       order adds (the two lane halves).
 #include <initializer_list>
 
-#include "m3d_common.h"
+#include "f16x2.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace m3d::f16x2;      // the cut, its vector types and the bound slots: f16x2.h
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int UF_NT = 256;
-constexpr int UF_SLOTS = 32;                      // slots of an absmax array (m3d_conv3d_zw_slots)
 constexpr int UF_VT = 64;                         // columns of a workgroup
 constexpr int UF_KC = 256;                        // input channels of one staged chunk
 constexpr int UF_STEP_UNITS = 8 * 2 * 64;         // packed weights of one (channel block, k step): [parity 8][hi / lo][lane 64] 16-byte units
 constexpr int UF_MAXK = 8;
 constexpr unsigned UF_CUS = 256;                  // below this many column tiles the plain epilogue cuts the channel blocks into slices
-constexpr int acc_row(int g) { return (g & 3) + 8 * (g >> 2); }
 
 // packed[channel block 32][k step = ci / 16][parity p = 4a + 2b + c][hi / lo][lane] <- weight [Cin][Cout][2][2][2] fp32: lane (row = l % 32,
 // half = l / 32) holds W[ci = 16 step + 8 half + j][co = 32 block + row][p], j = 0..7; rows beyond Cout are zero
 __global__ __launch_bounds__(256) void upconv_f16_pack_kernel(const float* __restrict__ w, int cin, int cout, u32x4* __restrict__ packed,
                                                               const float* __restrict__ wamax) {
   float sw, inv;
-  m3d::f16_scale_of(*wamax, sw, inv);
+  f16_scale_of(*wamax, sw, inv);
   const int steps = cin / 16, ncb = (cout + 31) / 32;
   const long long total = (long long)ncb * steps * 8 * 64;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
@@ -81,8 +77,7 @@ __global__ __launch_bounds__(256) void upconv_f16_pack_kernel(const float* __res
       for (int u = 0; u < 2; ++u) {
         float v = 0.f;
         if (co < cout) v = w[((size_t)(ks * 16 + 8 * kh + 2 * j + u) * cout + co) * 8 + p] * sw;
-        const _Float16 h = (_Float16)v;
-        hh[u] = h; ll[u] = (_Float16)(v - (float)h);
+        cut(v, hh, ll, u);
       }
       ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
     }
@@ -111,12 +106,12 @@ __global__ __launch_bounds__(UF_NT, 2) void upconv_f16_kernel(UfArgs a) {
   // ---- operand scales (powers of two): the input's bound = the largest slot, the weights' as packed
   float xs, inv_x, inv_w;
   {
-    float im = a.in_max[lane & (UF_SLOTS - 1)];
+    float im = a.in_max[lane & (kBoundSlots - 1)];      // max_of_slot_lanes of f16x2.h, open-coded: see there
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) im = fmaxf(im, __shfl_xor(im, o));
     float sw_;
-    m3d::f16_scale_of(im, xs, inv_x);
-    m3d::f16_scale_of(*a.wamax, sw_, inv_w);
+    f16_scale_of(im, xs, inv_x);
+    f16_scale_of(*a.wamax, sw_, inv_w);
   }
   const float un = inv_x * inv_w;
 
@@ -144,8 +139,7 @@ __global__ __launch_bounds__(UF_NT, 2) void upconv_f16_kernel(UfArgs a) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const float v = raw[2 * j + e] * xs;
-          const _Float16 h = (_Float16)v;
-          hh[e] = h; ll[e] = (_Float16)(v - (float)h);
+          cut(v, hh, ll, e);
         }
         ph[j] = __builtin_bit_cast(unsigned, hh); pl[j] = __builtin_bit_cast(unsigned, ll);
       }
