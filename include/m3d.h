@@ -301,7 +301,7 @@ int m3d_conv3d_bias_grad(const float* d_grad_out, float* d_grad_bias, int batch,
  * nn.Conv3d(dim, dim, 3, 1, padding=d, dilation=d) layers of lib/modeling/mask_rcnn_heads.py:141-151 with MRCNN.DILATION = d in training:
  *   dW[co,ci,dz,dy,dx] = sum_{b,z,y,x} gy[b,co,z,y,x] * x[b,ci, z+d(dz-1), y+d(dy-1), x+d(dx-1)]          (zero outside the volume)
  *   dilation 1     m3d_conv3d_wgrad / m3d_conv3d_wgrad_workspace_bytes with the same arguments: bit-equal, every k it takes.
- *   k 3, dilation 2  csrc/conv3d_wgrad_dilated.hip: the fp32 MFMA implicit GEMM of m3d_conv3d_wgrad (v_mfma_f32_32x32x2_f32, fp32
+ *   k 3, dilation 2  csrc/conv3d_wgrad.hip: the fp32 MFMA implicit GEMM of m3d_conv3d_wgrad (v_mfma_f32_32x32x2_f32, fp32
  *                  operands and accumulation) on a voxel tile with a 2-voxel halo: 2 x 8 x 8 for maps at most 8 wide (the 7^3 RoI
  *                  grid), 2 x 4 x 16 beyond.  `slots` split-K partials (a function of the shape only, m3d_conv3d_wgrad_dilated_plan)
  *                  go to the workspace; a reduce launch adds them in slot order.  No atomics: bit-identical run to run.  Writes every
@@ -324,7 +324,7 @@ int m3d_conv3d_wgrad_dilated_tile(const float* d_in, const float* d_grad_out, fl
                                   void* stream);
 int m3d_conv3d_wgrad_dilated_plan(int batch, int cin, int cout, int depth, int height, int width, int k, int dilation, int tile_x,
                                   int* tile_x_out, int* tile_y_out, int* slots_out);
-/* The k = 3, dilation 1 weight gradient of m3d_conv3d_wgrad on maps at most 8 voxels wide (csrc/conv3d_wgrad_narrow.hip): the per-RoI
+/* The k = 3, dilation 1 weight gradient of m3d_conv3d_wgrad on maps at most 8 voxels wide (csrc/conv3d_wgrad.hip): the per-RoI
  * convs on 7^3 grids of lib/modeling/fast_rcnn_heads.py:120-179 (roi_Xconv1fc_head) and of the mask head at MRCNN.DILATION = 1.  The
  * scheme of the dilated kernel above (v_mfma_f32_32x32x2_f32, fp32 operands and accumulation, `slots` split-K partials in the
  * workspace, a reduce launch that adds them in slot order; no atomics: bit-identical run to run) on a 2 x 8 x 8 voxel tile with a

@@ -2076,40 +2076,59 @@ class StemWinoConv3d(object):
 
 
 # ------------------------------------------------------------------ conv backward-weights / bias gradient
+def _wgrad_operands(x, grad_out, k, *bounds):
+    """What every conv3d_wgrad* begins with: x [B,cin,D,H,W] and grad_out [B,cout,D,H,W] (and the bounds, where given) are CUDA tensors;
+    -> (x, grad_out) as contiguous fp32, the dW [cout,cin,k,k,k] to fill, (B, cin, cout, D, H, W)"""
+    _need_gpu(x, grad_out, *bounds)
+    x, grad_out = _f32c(x), _f32c(grad_out)
+    B, cin, D, H, W = x.shape
+    cout = grad_out.shape[1]
+    assert grad_out.shape == (B, cout, D, H, W)
+    return x, grad_out, torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device), (B, cin, cout, D, H, W)
+
+
+def _wgrad_f16_bounds(x, grad_out, x_max, gy_max):
+    """(x_max, gy_max) of an f16x2 weight gradient: a missing one is swept (ZwConv3d.bound_of); each is [ZwConv3d.SLOTS] fp32"""
+    if x_max is None:
+        x_max = ZwConv3d.bound_of(x)
+    if gy_max is None:
+        gy_max = ZwConv3d.bound_of(grad_out)
+    assert x_max.numel() == ZwConv3d.SLOTS and gy_max.numel() == ZwConv3d.SLOTS and x_max.dtype == gy_max.dtype == torch.float32
+    return x_max, gy_max
+
+
+def _wgrad_plan(entry, keys, *args):
+    """A host-only m3d_<entry> with one int out-parameter per key after `args` -> dict(key: value)"""
+    v = [C.c_int(0) for _ in keys]
+    check(getattr(lib(), "m3d_" + entry)(*[int(a) for a in args], *[C.byref(a) for a in v]), entry)
+    return dict(zip(keys, (a.value for a in v)))
+
+
 def conv3d_wgrad_dilated_plan(batch, cin, cout, D, H, W, tile_x=0):
     """What conv3d_wgrad(..., 3, dilation=2) launches for this shape (m3d_conv3d_wgrad_dilated_plan, host only): dict(tile_x, tile_y, slots);
     tile_x = 16 / 8 asks for that tile form instead of the library's choice."""
-    v = [C.c_int(0) for _ in range(3)]
-    check(lib().m3d_conv3d_wgrad_dilated_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), 3, 2, int(tile_x),
-                                              *[C.byref(a) for a in v]), "conv3d_wgrad_dilated_plan")
-    return dict(zip(("tile_x", "tile_y", "slots"), (a.value for a in v)))
+    return _wgrad_plan("conv3d_wgrad_dilated_plan", ("tile_x", "tile_y", "slots"), batch, cin, cout, D, H, W, 3, 2, tile_x)
 
 
 def conv3d_wgrad(x, grad_out, k, dilation=1, tile_x=0):
     """dW [cout,cin,k,k,k] of a stride-1 conv with padding dilation * (k // 2): x [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA).
     dilation 1 is m3d_conv3d_wgrad; k = 3 with dilation 2 is m3d_conv3d_wgrad_dilated (tile_x = 16 / 8: that voxel tile instead of the
     library's choice, for A/B runs and tests); any other dilation is an error."""
-    _need_gpu(x, grad_out)
-    x, grad_out = _f32c(x), _f32c(grad_out)
-    B, cin, D, H, W = x.shape
-    cout = grad_out.shape[1]
-    assert grad_out.shape == (B, cout, D, H, W)
-    dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
+    x, grad_out, dw, shape = _wgrad_operands(x, grad_out, k)
     if dilation != 1:
-        wsb = lib().m3d_conv3d_wgrad_dilated_workspace_bytes(B, cin, cout, D, H, W, k, int(dilation))
+        wsb = lib().m3d_conv3d_wgrad_dilated_workspace_bytes(*shape, k, int(dilation))
         ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
         if tile_x:
-            rc = lib().m3d_conv3d_wgrad_dilated_tile(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, k, int(dilation), int(tile_x),
-                                                     _ptr(ws), C.c_size_t(wsb), _stream())
+            rc = lib().m3d_conv3d_wgrad_dilated_tile(_ptr(x), _ptr(grad_out), _ptr(dw), *shape, k, int(dilation), int(tile_x), _ptr(ws),
+                                                     C.c_size_t(wsb), _stream())
         else:
-            rc = lib().m3d_conv3d_wgrad_dilated(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, k, int(dilation), _ptr(ws),
-                                                C.c_size_t(wsb), _stream())
+            rc = lib().m3d_conv3d_wgrad_dilated(_ptr(x), _ptr(grad_out), _ptr(dw), *shape, k, int(dilation), _ptr(ws), C.c_size_t(wsb),
+                                                _stream())
         check(rc, "conv3d_wgrad_dilated")
         return dw
-    wsb = lib().m3d_conv3d_wgrad_workspace_bytes(B, cin, cout, D, H, W, k)
+    wsb = lib().m3d_conv3d_wgrad_workspace_bytes(*shape, k)
     ws = torch.empty((wsb,), dtype=torch.uint8, device=x.device)
-    check(lib().m3d_conv3d_wgrad(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, k, _ptr(ws), C.c_size_t(wsb), _stream()),
-          "conv3d_wgrad")
+    check(lib().m3d_conv3d_wgrad(_ptr(x), _ptr(grad_out), _ptr(dw), *shape, k, _ptr(ws), C.c_size_t(wsb), _stream()), "conv3d_wgrad")
     return dw
 
 
@@ -2121,26 +2140,18 @@ def conv3d_wgrad_narrow_supported(batch, cin, cout, D, H, W, k=3):
 
 def conv3d_wgrad_narrow_plan(batch, cin, cout, D, H, W):
     """What conv3d_wgrad_narrow launches for this shape (m3d_conv3d_wgrad_narrow_plan, host only): dict(tile_x, tile_y, slots)"""
-    v = [C.c_int(0) for _ in range(3)]
-    check(lib().m3d_conv3d_wgrad_narrow_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), 3, *[C.byref(a) for a in v]),
-          "conv3d_wgrad_narrow_plan")
-    return dict(zip(("tile_x", "tile_y", "slots"), (a.value for a in v)))
+    return _wgrad_plan("conv3d_wgrad_narrow_plan", ("tile_x", "tile_y", "slots"), batch, cin, cout, D, H, W, 3)
 
 
 def conv3d_wgrad_narrow(x, grad_out):
     """dW [cout,cin,3,3,3] of a stride-1 pad-1 3^3 conv on a map at most 8 wide (m3d_conv3d_wgrad_narrow: fp32 MFMA on the 2 x 8 x 8
     voxel tile): x [B,cin,D,H,W], grad_out [B,cout,D,H,W] (fp32 CUDA).  An unsupported shape is an error: ask
     conv3d_wgrad_narrow_supported (or conv_plan.wgrad_kernel)."""
-    _need_gpu(x, grad_out)
-    x, grad_out = _f32c(x), _f32c(grad_out)
-    B, cin, D, H, W = x.shape
-    cout = grad_out.shape[1]
-    assert grad_out.shape == (B, cout, D, H, W)
-    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    wsb = lib().m3d_conv3d_wgrad_narrow_workspace_bytes(B, cin, cout, D, H, W, 3)
+    x, grad_out, dw, shape = _wgrad_operands(x, grad_out, 3)
+    wsb = lib().m3d_conv3d_wgrad_narrow_workspace_bytes(*shape, 3)
     ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
-    check(lib().m3d_conv3d_wgrad_narrow(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, 3, _ptr(ws), C.c_size_t(wsb),
-                                        _stream()), "conv3d_wgrad_narrow")
+    check(lib().m3d_conv3d_wgrad_narrow(_ptr(x), _ptr(grad_out), _ptr(dw), *shape, 3, _ptr(ws), C.c_size_t(wsb), _stream()),
+          "conv3d_wgrad_narrow")
     return dw
 
 
@@ -2151,34 +2162,25 @@ def conv3d_wgrad_f16x2_supported(batch, cin, cout, D, H, W):
 
 def conv3d_wgrad_f16x2_plan(batch, cin, cout, D, H, W):
     """The host decision of the launch (m3d_conv3d_wgrad_f16x2_plan): dict(slots, tiles_per_slot, chain, folds)"""
-    v = [C.c_int(0) for _ in range(4)]
-    check(lib().m3d_conv3d_wgrad_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), *[C.byref(a) for a in v]),
-          "conv3d_wgrad_f16x2_plan")
-    return dict(zip(("slots", "tiles_per_slot", "chain", "folds"), (a.value for a in v)))
+    return _wgrad_plan("conv3d_wgrad_f16x2_plan", ("slots", "tiles_per_slot", "chain", "folds"), batch, cin, cout, D, H, W)
 
 
 def conv3d_wgrad_f16x2(x, grad_out, x_max=None, gy_max=None):
     """dW [cout,cin,3,3,3] of a stride-1 pad-1 3^3 conv on the f16 matrix cores at fp32 accuracy (m3d_conv3d_wgrad_f16x2): x [B,cin,D,H,W],
     grad_out [B,cout,D,H,W] (fp32 CUDA).  x_max / gy_max: [ZwConv3d.SLOTS] device floats whose largest bounds |x| / |grad_out|; a missing
     one is swept (ZwConv3d.bound_of).  An unsupported shape is an error: ask conv3d_wgrad_f16x2_supported (or conv_plan.wgrad_kernel)."""
-    _need_gpu(x, grad_out, x_max, gy_max)
-    x, grad_out = _f32c(x), _f32c(grad_out)
-    B, cin, D, H, W = x.shape
-    cout = grad_out.shape[1]
-    assert grad_out.shape == (B, cout, D, H, W)
-    if x_max is None:
-        x_max = ZwConv3d.bound_of(x)
-    if gy_max is None:
-        gy_max = ZwConv3d.bound_of(grad_out)
-    assert x_max.numel() == ZwConv3d.SLOTS and gy_max.numel() == ZwConv3d.SLOTS and x_max.dtype == gy_max.dtype == torch.float32
-    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    wsb = lib().m3d_conv3d_wgrad_f16x2_workspace_bytes(B, cin, cout, D, H, W)
+    x, grad_out, dw, shape = _wgrad_operands(x, grad_out, 3, x_max, gy_max)
+    x_max, gy_max = _wgrad_f16_bounds(x, grad_out, x_max, gy_max)
+    wsb = lib().m3d_conv3d_wgrad_f16x2_workspace_bytes(*shape)
     ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
-    check(lib().m3d_conv3d_wgrad_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, _ptr(x_max), _ptr(gy_max), _ptr(ws),
-                                       C.c_size_t(wsb), _stream()), "conv3d_wgrad_f16x2")
+    check(lib().m3d_conv3d_wgrad_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), *shape, _ptr(x_max), _ptr(gy_max), _ptr(ws), C.c_size_t(wsb),
+                                       _stream()), "conv3d_wgrad_f16x2")
     return dw
 
 
+# The three narrow f16x2 wrappers below call the dilation-1 entry points when `dilation` is 1 and the ones that take the dilation
+# otherwise, although the former only forward to the latter: the launch records of tests/test_wgrad_dilated_f16_host.py and
+# tests/test_conv_train_dispatch_narrow_f16.py pin which symbol a dilation-1 call reaches.
 def conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, D, H, W, dilation=1):
     """m3d_conv3d_wgrad_narrow_f16x2_supported (host only): the k = 3 weight gradient of this shape runs on the f16 matrix cores on the
     2 x 8 x 8 voxel tile (W <= 8, cin and cout multiples of 32).  dilation: 1 (left out: that query) or another one, asked of
@@ -2191,14 +2193,10 @@ def conv3d_wgrad_narrow_f16x2_supported(batch, cin, cout, D, H, W, dilation=1):
 def conv3d_wgrad_narrow_f16x2_plan(batch, cin, cout, D, H, W, dilation=1):
     """The host decision of the launch (m3d_conv3d_wgrad_narrow_f16x2_plan; with a dilation other than 1
     m3d_conv3d_wgrad_narrow_dilated_f16x2_plan): dict(tile_z, slots, tiles_per_slot, chain, folds)"""
-    v = [C.c_int(0) for _ in range(5)]
+    keys = ("tile_z", "slots", "tiles_per_slot", "chain", "folds")
     if dilation == 1:
-        check(lib().m3d_conv3d_wgrad_narrow_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), *[C.byref(a) for a in v]),
-              "conv3d_wgrad_narrow_f16x2_plan")
-    else:
-        check(lib().m3d_conv3d_wgrad_narrow_dilated_f16x2_plan(int(batch), int(cin), int(cout), int(D), int(H), int(W), int(dilation),
-                                                               *[C.byref(a) for a in v]), "conv3d_wgrad_narrow_dilated_f16x2_plan")
-    return dict(zip(("tile_z", "slots", "tiles_per_slot", "chain", "folds"), (a.value for a in v)))
+        return _wgrad_plan("conv3d_wgrad_narrow_f16x2_plan", keys, batch, cin, cout, D, H, W)
+    return _wgrad_plan("conv3d_wgrad_narrow_dilated_f16x2_plan", keys, batch, cin, cout, D, H, W, dilation)
 
 
 def conv3d_wgrad_narrow_f16x2(x, grad_out, x_max=None, gy_max=None, dilation=1):
@@ -2207,28 +2205,13 @@ def conv3d_wgrad_narrow_f16x2(x, grad_out, x_max=None, gy_max=None, dilation=1):
     largest bounds |x| / |grad_out|; a missing one is swept (ZwConv3d.bound_of).  dilation: 1 (left out: the calls above), or 2: the
     weight gradient of the dilation-2, padding-2 conv (m3d_conv3d_wgrad_narrow_dilated_f16x2).  An unsupported shape or dilation is an
     error: ask conv3d_wgrad_narrow_f16x2_supported (or conv_plan.plan_train_conv)."""
-    _need_gpu(x, grad_out, x_max, gy_max)
-    x, grad_out = _f32c(x), _f32c(grad_out)
-    B, cin, D, H, W = x.shape
-    cout = grad_out.shape[1]
-    assert grad_out.shape == (B, cout, D, H, W)
-    if x_max is None:
-        x_max = ZwConv3d.bound_of(x)
-    if gy_max is None:
-        gy_max = ZwConv3d.bound_of(grad_out)
-    assert x_max.numel() == ZwConv3d.SLOTS and gy_max.numel() == ZwConv3d.SLOTS and x_max.dtype == gy_max.dtype == torch.float32
-    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    if dilation == 1:
-        wsb = lib().m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes(B, cin, cout, D, H, W)
-        ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
-        check(lib().m3d_conv3d_wgrad_narrow_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, _ptr(x_max), _ptr(gy_max),
-                                                  _ptr(ws), C.c_size_t(wsb), _stream()), "conv3d_wgrad_narrow_f16x2")
-        return dw
-    wsb = lib().m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes(B, cin, cout, D, H, W, int(dilation))
+    x, grad_out, dw, shape = _wgrad_operands(x, grad_out, 3, x_max, gy_max)
+    x_max, gy_max = _wgrad_f16_bounds(x, grad_out, x_max, gy_max)
+    name, dil = ("conv3d_wgrad_narrow_f16x2", ()) if dilation == 1 else ("conv3d_wgrad_narrow_dilated_f16x2", (int(dilation),))
+    wsb = getattr(lib(), "m3d_%s_workspace_bytes" % name)(*shape, *dil)
     ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
-    check(lib().m3d_conv3d_wgrad_narrow_dilated_f16x2(_ptr(x), _ptr(grad_out), _ptr(dw), B, cin, cout, D, H, W, int(dilation), _ptr(x_max),
-                                                      _ptr(gy_max), _ptr(ws), C.c_size_t(wsb), _stream()),
-          "conv3d_wgrad_narrow_dilated_f16x2")
+    check(getattr(lib(), "m3d_" + name)(_ptr(x), _ptr(grad_out), _ptr(dw), *shape, *dil, _ptr(x_max), _ptr(gy_max), _ptr(ws),
+                                        C.c_size_t(wsb), _stream()), name)
     return dw
 
 

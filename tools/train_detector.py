@@ -20,7 +20,7 @@ conv_plan.WGRAD_DILATED_F16X2_MIN_WORK products per tap).
 --box-head conv (default mlp, whose output stays as it is) trains m3d.ConvBoxHead (roi_Xconv1fc_head, fast_rcnn_heads.py:120-179:
 --conv-head-convs 3^3 convs of --conv-head-dim channels on the 7^3 grids, then one FC layer of --hidden) in place of the two-FC head;
 --wgrad-narrow moves the weight gradient of every intercepted dilation-1 conv on a map at most 8 wide (those head convs and, with
---mask, the mask head's) to the 2 x 8 x 8 tile kernel (m3d.compat.set_conv_wgrad_narrow, csrc/conv3d_wgrad_narrow.hip);
+--mask, the mask head's) to the 2 x 8 x 8 tile kernel (m3d.compat.set_conv_wgrad_narrow, csrc/conv3d_wgrad.hip);
 --conv-narrow f16x2 runs the forward and the backward-data pass of those convs on the narrow-map f16x2 kernel
 (m3d.compat.set_conv_train_narrow, csrc/conv3d_zn.hip); --wgrad-narrow-f16 runs their weight gradient on the f16 matrix cores on that
 2 x 8 x 8 tile (m3d.compat.set_conv_wgrad_narrow_f16, csrc/conv3d_wgrad_narrow_f16.hip: layers of at least
@@ -92,7 +92,7 @@ def main():
                     help="with --mask: MRCNN.DILATION of the mask head's 3^3 convs (MaskTrainCfg.dilation)")
     ap.add_argument("--conv-dilated", choices=("torch", "m3d"), default="torch",
                     help="the dilation-2 convs (m3d.compat.set_conv_dilated): m3d = the library's dilated forward, dgrad and wgrad "
-                         "(csrc/conv3d_wgrad_dilated.hip)")
+                         "(csrc/conv3d_wgrad.hip)")
     ap.add_argument("--conv-dilated-f16", action="store_true",
                     help="with --conv-dilated m3d: forward and dgrad of the dilation-2 convs on maps at most 8 wide on the f16 matrix cores at "
                          "fp32 accuracy (m3d.compat.set_conv_dilated_f16)")
