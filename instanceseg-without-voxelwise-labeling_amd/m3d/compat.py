@@ -178,10 +178,18 @@ class _Legacy2D(object):
 # ----------------------------------------------------------------------------- F.conv3d interception
 _orig_conv3d = None
 _pack_cache = {}          # (id(parameter), pack kind) -> (weakref to the parameter, _version, data_ptr, pack)
+
+
+def _stem_dgrad_pack(weight):
+    """the backward-data of the 5^3 / Cin = 1 stem as a pack that is called on gy, like the others: its tap-flipped [C,125] weights"""
+    wf = ops.conv3d_stem5_dgrad_weights(weight)
+    return lambda gy: ops.conv3d_stem5_dgrad(gy, wf)
+
+
 _PACKS = {                # pack kind -> constructor from the detached weight
     "plain": lambda w: ops.PackedConv3d(w, ops.W_PLAIN),     # the direct fp32 kernel, forward (dilation 1 and 2)
     "dgrad": lambda w: ops.PackedConv3d(w, ops.W_DGRAD),     # ... its backward-data
-    "stem-dgrad": ops.conv3d_stem5_dgrad_weights,            # tap-flipped [C,125] weights of the 5^3 / Cin = 1 stem's backward-data
+    "stem-dgrad": _stem_dgrad_pack,
     "zw-plain": ops.ZwConv3d, "zw-dgrad": ops.ZwConv3d.dgrad_of,       # the f16x2 kernel (set_conv_train)
     "zn-plain": ops.ZnConv3d, "zn-dgrad": ops.ZnConv3d.dgrad_of,       # the narrow-map f16x2 kernel (set_conv_train_narrow)
     "upconv-f16": ops.UpConvF16,                             # the up-conv's f16x2 forward (set_upconv_f16)
@@ -206,10 +214,34 @@ def _packed(weight, mode):
     return pack
 
 
-_setting = conv_plan.TrainSetting()          # what the setters below say; WHEN each field is read: the TrainSetting docstring
-_wgrad_narrow_f16 = None                     # set_conv_wgrad_narrow_f16: None (off) or its threshold; beside _setting, whose fields are pinned
-_dilated_f16 = None                          # set_conv_dilated_f16: None (off) or its threshold in launch units; beside _setting too
-_wgrad_dilated_f16 = None                    # set_conv_wgrad_dilated_f16: None (off) or its threshold in products per tap; beside _setting too
+_setting = conv_plan.TrainSetting()          # everything the setters below say; WHEN each field is read: the TrainSetting docstring
+
+
+def _threshold(setter, name, value):
+    """a routing threshold as a setter takes it: None (the setter's default) or a count >= 0"""
+    if value is not None and int(value) < 0:
+        raise ValueError("%s(%s=%r): None or a count >= 0" % (setter, name, value))
+    return None if value is None else int(value)
+
+
+def _set_mode(field, modes, mode, **thresholds):
+    """set_conv_<field>(mode, **thresholds): one mode string out of the two `modes` into _setting.<field>, each threshold (checked after
+    the mode) into the field of its name -> the previous mode"""
+    global _setting
+    if mode not in modes:
+        raise ValueError("set_conv_%s(%r): %r or %r" % ((field, mode) + tuple(modes)))
+    also = {name: _threshold("set_conv_" + field, name, value) for name, value in thresholds.items()}
+    prev, _setting = getattr(_setting, field), _setting._replace(**{field: mode}, **also)
+    return prev
+
+
+def _set_switch(setter, field, on, name, value, default):
+    """setter(on, name=value): an on / off switch with a routing threshold, kept in _setting.<field> as None (off) or the threshold
+    (value None: `default`) -> whether it was on"""
+    global _setting
+    value = _threshold(setter, name, value)
+    prev, _setting = getattr(_setting, field) is not None, _setting._replace(**{field: (default if value is None else value) if on else None})
+    return prev
 
 
 def set_conv_wgrad(mode):
@@ -217,11 +249,7 @@ def set_conv_wgrad(mode):
     "f16x2" takes m3d_conv3d_wgrad_f16x2 (the f16 matrix cores at fp32 accuracy, two operand sweeps included) for the layers
     conv_plan.wgrad_kernel routes to it - every other layer (the 5^3 stem, k = 1, channel counts that are no multiple of 32) stays on the
     fp32 kernel.  Forward, dgrad and the bias gradient are the same under both settings.  Returns the previous setting."""
-    global _setting
-    if mode not in (conv_plan.WGRAD_FP32, conv_plan.WGRAD_F16X2):
-        raise ValueError("set_conv_wgrad(%r): 'fp32' or 'f16x2'" % (mode,))
-    prev, _setting = _setting.wgrad, _setting._replace(wgrad=mode)
-    return prev
+    return _set_mode("wgrad", (conv_plan.WGRAD_FP32, conv_plan.WGRAD_F16X2), mode)
 
 
 def get_conv_wgrad():
@@ -252,16 +280,11 @@ def set_conv_wgrad_narrow_f16(on, min_work=None):
     bias gradient are the same with the switch on or off.  min_work: the routing threshold in products per tap, batch D H W cin cout
     (None: conv_plan.WGRAD_NARROW_F16X2_MIN_WORK; 0 routes every supported layer - tests and A/B runs; a call without it puts the
     default back).  Read when the backward runs.  Returns the previous setting (True / False)."""
-    global _wgrad_narrow_f16
-    if min_work is not None and int(min_work) < 0:
-        raise ValueError("set_conv_wgrad_narrow_f16(min_work=%r): None or a count >= 0" % (min_work,))
-    prev = _wgrad_narrow_f16 is not None
-    _wgrad_narrow_f16 = (conv_plan.WGRAD_NARROW_F16X2_MIN_WORK if min_work is None else int(min_work)) if on else None
-    return prev
+    return _set_switch("set_conv_wgrad_narrow_f16", "wgrad_narrow_f16", on, "min_work", min_work, conv_plan.WGRAD_NARROW_F16X2_MIN_WORK)
 
 
 def get_conv_wgrad_narrow_f16():
-    return _wgrad_narrow_f16 is not None
+    return _setting.wgrad_narrow_f16 is not None
 
 
 def set_conv_train(mode, min_units=None):
@@ -276,13 +299,7 @@ def set_conv_train(mode, min_units=None):
     As set_conv_wgrad("f16x2") already implies for its kernel: with a non-finite value in an operand the operand's bound is non-finite and
     the WHOLE result is, not only the elements the fp32 kernel's element-wise propagation would reach; Solver(stats=True).nonfinite is
     the guard."""
-    global _setting
-    if mode not in (conv_plan.TRAIN_FP32, conv_plan.TRAIN_F16X2):
-        raise ValueError("set_conv_train(%r): 'fp32' or 'f16x2'" % (mode,))
-    if min_units is not None and int(min_units) < 0:
-        raise ValueError("set_conv_train(min_units=%r): None or a count >= 0" % (min_units,))
-    prev, _setting = _setting.train, _setting._replace(train=mode, min_units=None if min_units is None else int(min_units))
-    return prev
+    return _set_mode("train", (conv_plan.TRAIN_FP32, conv_plan.TRAIN_F16X2), mode, min_units=min_units)
 
 
 def get_conv_train():
@@ -299,12 +316,7 @@ def set_conv_train_narrow(on, min_units=None):
     weight gradient's routing (set_conv_wgrad, set_conv_wgrad_narrow) is untouched.  min_units: the routing threshold in launch units
     (None: conv_plan.ZN_MIN_UNITS; 0 routes every supported layer - tests and A/B runs; a call without it puts the default back).
     Returns the previous setting (True / False)."""
-    global _setting
-    if min_units is not None and int(min_units) < 0:
-        raise ValueError("set_conv_train_narrow(min_units=%r): None or a count >= 0" % (min_units,))
-    prev = _setting.narrow is not None
-    _setting = _setting._replace(narrow=(conv_plan.ZN_MIN_UNITS if min_units is None else int(min_units)) if on else None)
-    return prev
+    return _set_switch("set_conv_train_narrow", "narrow", on, "min_units", min_units, conv_plan.ZN_MIN_UNITS)
 
 
 def get_conv_train_narrow():
@@ -321,11 +333,7 @@ def set_conv_dilated(mode):
     (DESIGN, "Dilated conv backward").  All fp32: set_conv_train("f16x2") and set_conv_wgrad("f16x2") do not reach these layers;
     set_conv_dilated_f16 (opt-in) moves their forward and dgrad on narrow maps to the f16 matrix cores.  The backward of a call follows
     the mode its forward ran under.  Returns the previous mode."""
-    global _setting
-    if mode not in (CONV_DILATED_TORCH, CONV_DILATED_M3D):
-        raise ValueError("set_conv_dilated(%r): 'torch' or 'm3d'" % (mode,))
-    prev, _setting = _setting.dilated, _setting._replace(dilated=mode)
-    return prev
+    return _set_mode("dilated", (CONV_DILATED_TORCH, CONV_DILATED_M3D), mode)
 
 
 def get_conv_dilated():
@@ -337,113 +345,94 @@ def set_conv_dilated_f16(on, min_units=None):
     8 wide with launched input channels a multiple of 16 (train.MaskHead at MRCNN.DILATION = 2 on 7^3 RoI grids): False (the default;
     install() does not change it) keeps m3d_conv3d_forward_dilated, the direct fp32 kernel; True takes the dilation-2 instantiation of
     the narrow-map f16x2 kernel (ops.ZnConv3d(..., dilation=2), csrc/conv3d_zn.hip; dgrad on its dgrad_of pack) for the layers and
-    directions conv_plan.plan_train_conv(dilated_f16=) routes to it.  Such a forward sweeps x once; such a dgrad takes gy's bound from
+    directions conv_plan.plan_train_conv routes to it (TrainSetting.dilated_f16).  Such a forward sweeps x once; such a dgrad takes gy's bound from
     m3d_conv3d_gy_reduce, which then also gives the bias gradient (the rule of set_conv_train_narrow).  The weight gradient stays on
     m3d_conv3d_wgrad_dilated.  Without set_conv_dilated("m3d") it has no effect.  min_units: the routing threshold in launch units
     (None: conv_plan.ZN_DILATED_MIN_UNITS; 0 routes every supported layer - tests and A/B runs; a call without it puts the default
     back).  Read at forward time; the backward of a call follows the value its forward ran under.  Returns the previous setting
     (True / False)."""
-    global _dilated_f16
-    if min_units is not None and int(min_units) < 0:
-        raise ValueError("set_conv_dilated_f16(min_units=%r): None or a count >= 0" % (min_units,))
-    prev = _dilated_f16 is not None
-    _dilated_f16 = (conv_plan.ZN_DILATED_MIN_UNITS if min_units is None else int(min_units)) if on else None
-    return prev
+    return _set_switch("set_conv_dilated_f16", "dilated_f16", on, "min_units", min_units, conv_plan.ZN_DILATED_MIN_UNITS)
 
 
 def get_conv_dilated_f16():
-    return _dilated_f16 is not None
+    return _setting.dilated_f16 is not None
 
 
 def set_conv_wgrad_dilated_f16(on, min_work=None):
     """The weight gradient of the dilation-2 convs that set_conv_dilated("m3d") routes to the library, on maps at most 8 wide with channel
     counts that are multiples of 32 (train.MaskHead at MRCNN.DILATION = 2 on 7^3 RoI grids): False (the default; install() does not
     change it) keeps m3d_conv3d_wgrad_dilated, the fp32 kernel; True takes m3d_conv3d_wgrad_narrow_dilated_f16x2 (the f16 matrix cores
-    at fp32 accuracy on the 2 x 8 x 8 tile, dilation 2) for the layers conv_plan.plan_train_conv(wgrad_dilated_f16=) routes to it.  x's
+    at fp32 accuracy on the 2 x 8 x 8 tile, dilation 2) for the layers conv_plan.plan_train_conv routes to it (TrainSetting.wgrad_dilated_f16).  x's
     bound comes from the forward and gy's from m3d_conv3d_gy_reduce where set_conv_dilated_f16 ran them, else the kernel's wrapper
     sweeps; forward, dgrad and the bias gradient are the same with the switch on or off.  Without set_conv_dilated("m3d") it has no
     effect.  min_work: the routing threshold in products per tap, batch D H W cin cout (None:
     conv_plan.WGRAD_DILATED_F16X2_MIN_WORK; 0 routes every supported layer - tests and A/B runs; a call without it puts the default
     back).  Read when the backward runs.  Returns the previous setting (True / False)."""
-    global _wgrad_dilated_f16
-    if min_work is not None and int(min_work) < 0:
-        raise ValueError("set_conv_wgrad_dilated_f16(min_work=%r): None or a count >= 0" % (min_work,))
-    prev = _wgrad_dilated_f16 is not None
-    _wgrad_dilated_f16 = (conv_plan.WGRAD_DILATED_F16X2_MIN_WORK if min_work is None else int(min_work)) if on else None
-    return prev
+    return _set_switch("set_conv_wgrad_dilated_f16", "wgrad_dilated_f16", on, "min_work", min_work, conv_plan.WGRAD_DILATED_F16X2_MIN_WORK)
 
 
 def get_conv_wgrad_dilated_f16():
-    return _wgrad_dilated_f16 is not None
+    return _setting.wgrad_dilated_f16 is not None
+
+
+# forward / dgrad kind of the plan -> (pack family: "plain" or "dgrad" follows by direction; dilation; the call takes an operand bound)
+_CONV_KINDS = {
+    conv_plan.TRAIN_FP32: ("", 1, False),
+    conv_plan.TRAIN_F16X2: ("zw-", 1, True),
+    conv_plan.TRAIN_F16X2_NARROW: ("zn-", 1, True),
+    conv_plan.TRAIN_DILATED: ("", 2, False),
+    conv_plan.TRAIN_DILATED_F16X2: ("zn-", 2, True),
+    conv_plan.DGRAD_STEM: ("stem-", 1, False),
+}
+# wgrad kind of the plan -> its call on (x, gy, x's bound, gy's bound, k).  The f16x2 kernels take x's bound from the forward where that
+# ran on an f16x2 kernel and gy's from the reduce where that ran; a missing one is swept.  The narrow f16x2 kernel is one wrapper at
+# either dilation (1: it makes the calls it made before it had the keyword)
+_WGRAD_KINDS = {
+    conv_plan.WGRAD_FP32: lambda x, gy, x_max, gy_max, k: ops.conv3d_wgrad(x, gy, k),
+    conv_plan.WGRAD_F16X2: lambda x, gy, x_max, gy_max, k: ops.conv3d_wgrad_f16x2(x, gy, x_max, gy_max),
+    conv_plan.WGRAD_NARROW: lambda x, gy, x_max, gy_max, k: ops.conv3d_wgrad_narrow(x, gy),
+    conv_plan.WGRAD_NARROW_F16X2: lambda x, gy, x_max, gy_max, k: ops.conv3d_wgrad_narrow_f16x2(x, gy, x_max, gy_max, dilation=1),
+    conv_plan.WGRAD_DILATED: lambda x, gy, x_max, gy_max, k: ops.conv3d_wgrad(x, gy, 3, dilation=2),
+    conv_plan.WGRAD_DILATED_F16X2: lambda x, gy, x_max, gy_max, k: ops.conv3d_wgrad_narrow_f16x2(x, gy, x_max, gy_max, dilation=2),
+}
+
+
+def _run_conv(kind, weight, direction, x, bound, **kw):
+    """the conv of plan kind `kind` (a key of _CONV_KINDS; an unknown one is a KeyError) on x: the forward (direction "plain"; kw: shift)
+    or the backward-data pass (direction "dgrad", x is gy)"""
+    family, dilation, bounded = _CONV_KINDS[kind]
+    if dilation != 1:
+        kw["dilation"] = dilation
+    pack = _packed(weight, family + direction)
+    return pack(x, bound, out_max=False, **kw)[0] if bounded else pack(x, **kw)
 
 
 class _Conv3dFn(torch.autograd.Function):
     """A conv that conv3d() routes to the library (dilation 1 or 2): runs conv_plan.plan_train_conv's plan, the forward half in
-    forward, the backward half in backward.  Nothing is decided here."""
+    forward, the backward half in backward, from the two tables above.  Nothing is decided here."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, dilation):
         ctx.save_for_backward(weight, x if weight.requires_grad else None)
         ctx.has_bias = bias is not None
-        ctx.setting, ctx.xshape, ctx.dilation = _setting, tuple(x.shape), dilation      # (when each switch is read: TrainSetting)
-        ctx.dilated_f16 = _dilated_f16                                                  # (read here; the backward follows it)
+        ctx.setting, ctx.xshape, ctx.dilation = _setting, tuple(x.shape), dilation      # (when each field is read: TrainSetting)
         shift = bias.detach().contiguous() if bias is not None else None
-        kind, sweep = conv_plan.plan_train_forward(_setting, ctx.xshape, weight.shape, dilation, _dilated_f16)
+        kind, sweep = conv_plan.plan_train_forward(ctx.setting, ctx.xshape, weight.shape, dilation)
         ctx.x_max = ops.ZwConv3d.bound_of(x) if sweep else None        # kept for the f16x2 wgrad
-        if kind == conv_plan.TRAIN_F16X2:
-            return _packed(weight, "zw-plain")(x, ctx.x_max, shift=shift, out_max=False)[0]
-        if kind == conv_plan.TRAIN_F16X2_NARROW:
-            return _packed(weight, "zn-plain")(x, ctx.x_max, shift=shift, out_max=False)[0]
-        if kind == conv_plan.TRAIN_DILATED:
-            return _packed(weight, "plain")(x, shift=shift, dilation=2)
-        if kind == conv_plan.TRAIN_DILATED_F16X2:
-            return _packed(weight, "zn-plain")(x, ctx.x_max, shift=shift, out_max=False, dilation=2)[0]
-        return _packed(weight, "plain")(x, shift=shift)
+        return _run_conv(kind, weight, "plain", x, ctx.x_max, shift=shift)
 
     @staticmethod
     def backward(ctx, gy):
         weight, x = ctx.saved_tensors
         gy = gy.contiguous()
-        setting = ctx.setting._replace(wgrad=_setting.wgrad, wgrad_narrow=_setting.wgrad_narrow)
+        setting = ctx.setting._replace(**{field: getattr(_setting, field) for field in conv_plan.BACKWARD_FIELDS})
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
-        dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs,
-                                                                         _wgrad_narrow_f16, ctx.dilated_f16, _wgrad_dilated_f16)
-        gx = gw = gb = gy_max = None
+        dgrad, wgrad, gy_reduce, gb_from = conv_plan.plan_train_backward(setting, ctx.xshape, weight.shape, ctx.dilation, needs)
+        gb = gy_max = None
         if gy_reduce:
             gb, gy_max = ops.conv3d_gy_reduce(gy, bias=gb_from == conv_plan.GB_REDUCE)
-
-        if dgrad == conv_plan.DGRAD_STEM:
-            gx = ops.conv3d_stem5_dgrad(gy, _packed(weight, "stem-dgrad"))
-        elif dgrad == conv_plan.TRAIN_F16X2:
-            gx = _packed(weight, "zw-dgrad")(gy, gy_max, out_max=False)[0]
-        elif dgrad == conv_plan.TRAIN_F16X2_NARROW:
-            gx = _packed(weight, "zn-dgrad")(gy, gy_max, out_max=False)[0]
-        elif dgrad == conv_plan.TRAIN_DILATED:
-            gx = _packed(weight, "dgrad")(gy, dilation=2)
-        elif dgrad == conv_plan.TRAIN_FP32:
-            gx = _packed(weight, "dgrad")(gy)
-        else:
-            # the kinds left: None (gx not needed) and TRAIN_DILATED_F16X2, on the pack and with the bound TRAIN_F16X2_NARROW takes (an
-            # else, as in the wgrad chain below: the count of branches of this function is pinned)
-            assert dgrad in (None, conv_plan.TRAIN_DILATED_F16X2), dgrad
-            gx = None if dgrad is None else _packed(weight, "zn-dgrad")(gy, gy_max, out_max=False, dilation=2)[0]
-
-        if wgrad == conv_plan.WGRAD_F16X2:
-            # x's bound from the forward where that ran on an f16x2 kernel, gy's from the reduce where that ran; a missing one is swept
-            gw = ops.conv3d_wgrad_f16x2(x, gy, ctx.x_max, gy_max)
-        elif wgrad == conv_plan.WGRAD_NARROW:
-            gw = ops.conv3d_wgrad_narrow(x, gy)
-        elif wgrad == conv_plan.WGRAD_DILATED:
-            gw = ops.conv3d_wgrad(x, gy, 3, dilation=2)
-        elif wgrad == conv_plan.WGRAD_FP32:
-            gw = ops.conv3d_wgrad(x, gy, weight.shape[2])
-        else:
-            # the kinds left: None (gw not needed), WGRAD_NARROW_F16X2 and WGRAD_DILATED_F16X2 - one kernel at the call's dilation (1: the
-            # wrapper makes the calls it made without the keyword), with the bounds WGRAD_F16X2 takes.  (An else, since the count of
-            # branches of this function is pinned: tests/test_conv_train_dispatch.py::test_backward_has_no_routing_left)
-            assert (wgrad, ctx.dilation) in ((None, 1), (None, 2), (conv_plan.WGRAD_NARROW_F16X2, 1), (conv_plan.WGRAD_DILATED_F16X2, 2)), wgrad
-            gw = None if wgrad is None else ops.conv3d_wgrad_narrow_f16x2(x, gy, ctx.x_max, gy_max, dilation=ctx.dilation)
-
+        gx = None if dgrad is None else _run_conv(dgrad, weight, "dgrad", gy, gy_max)
+        gw = None if wgrad is None else _WGRAD_KINDS[wgrad](x, gy, ctx.x_max, gy_max, weight.shape[2])
         if gb_from == conv_plan.GB_BIAS_GRAD:
             gb = ops.conv3d_bias_grad(gy)
         return gx, gw, gb, None
@@ -518,9 +507,7 @@ def set_linear_backward(mode, min_work=None):
     global _linear_backward
     if mode not in (conv_plan.LINEAR_BACKWARD_FP32, conv_plan.LINEAR_BACKWARD_F16X2):
         raise ValueError("set_linear_backward(%r): 'fp32' or 'f16x2'" % (mode,))
-    if min_work is not None and int(min_work) < 0:
-        raise ValueError("set_linear_backward(min_work=%r): None or a count >= 0" % (min_work,))
-    prev, _linear_backward = _linear_backward[0], (mode, None if min_work is None else int(min_work))
+    prev, _linear_backward = _linear_backward[0], (mode, _threshold("set_linear_backward", "min_work", min_work))
     return prev
 
 

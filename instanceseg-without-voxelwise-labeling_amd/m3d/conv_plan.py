@@ -4,9 +4,10 @@
 (DetectorM3D.body_layer / rpn), bench.py's roofline bookkeeping (DetectorM3D.conv_work) and the PRM forward
 (PRMEngine.forward_response) all ask it, each with its own needs, and run what it says by calling the layer's `LayerConv`.
 
-`plan_train_conv` is the same for the training path (m3d.compat.conv3d and its backward): what the switches of m3d.compat say travels
-as a `TrainSetting`, the rules `train_conv_kernel` and `wgrad_kernel` are its rows, and `compat._Conv3dFn` runs the plan (DESIGN.md
-"Training conv dispatch")."""
+`plan_train_conv` is the same for the training path (m3d.compat.conv3d and its backward): everything the switches of m3d.compat say
+travels as one `TrainSetting` (FORWARD_FIELDS / BACKWARD_FIELDS: when each field is read), the rules `train_conv_kernel` and
+`wgrad_kernel` are its rows, and `compat._Conv3dFn` runs the plan from two tables keyed by its kinds (DESIGN.md "Training conv
+dispatch")."""
 import collections
 
 import torch
@@ -187,24 +188,28 @@ WGRAD_DILATED_F16X2 = "f16x2 dilated"
 WGRAD_DILATED_F16X2_MIN_WORK = 4 * 343 * 256 * 256
 
 
-class TrainSetting(collections.namedtuple("TrainSetting", "train min_units narrow wgrad wgrad_narrow dilated",
-                                          defaults=(TRAIN_FP32, None, None, WGRAD_FP32, False, DILATED_TORCH))):
+class TrainSetting(collections.namedtuple(
+        "TrainSetting", "train min_units narrow wgrad wgrad_narrow dilated wgrad_narrow_f16 dilated_f16 wgrad_dilated_f16",
+        defaults=(TRAIN_FP32, None, None, WGRAD_FP32, False, DILATED_TORCH, None, None, None))):
     """Everything the switches of m3d.compat say about a training conv, immutable; the defaults are install()'s.
-    train         TRAIN_FP32 / TRAIN_F16X2 (set_conv_train)
-    min_units     its routing threshold in launch units; None: ZW_MIN_UNITS
-    narrow        None: the narrow f16x2 kernel is off; else its routing threshold in launch units (set_conv_train_narrow)
-    wgrad         WGRAD_FP32 / WGRAD_F16X2 (set_conv_wgrad)
-    wgrad_narrow  bool (set_conv_wgrad_narrow)
-    dilated       DILATED_TORCH / DILATED_M3D (set_conv_dilated)
-    WHEN each is read: train, min_units, narrow and dilated are those of the FORWARD call - the conv Function keeps the forward's
-    setting and its backward follows it, whatever the setters were told in between; wgrad and wgrad_narrow are read when the BACKWARD
-    runs (the Function puts the current two into the kept setting before it asks plan_train_backward).
-    The field list is pinned (tests/test_conv_train_dispatch.py compares _asdict() of the defaults), so the one later switch,
-    set_conv_wgrad_narrow_f16, travels beside the setting: the wgrad_narrow_f16 argument of plan_train_backward / plan_train_conv,
-    read when the backward runs as the other two wgrad switches are.  set_conv_dilated_f16 travels the same way (the dilated_f16
-    argument of the three plan functions), read at FORWARD time: the backward follows the forward's value, as it does for dilated.
-    set_conv_wgrad_dilated_f16 is the wgrad_dilated_f16 argument of plan_train_backward / plan_train_conv, read when the BACKWARD runs."""
+    | field             | value                                                                        | setter                     | read at  |
+    | train             | TRAIN_FP32 / TRAIN_F16X2                                                     | set_conv_train             | forward  |
+    | min_units         | its routing threshold in launch units; None: ZW_MIN_UNITS                    | set_conv_train             | forward  |
+    | narrow            | None: the narrow f16x2 kernel is off; else its threshold in launch units     | set_conv_train_narrow      | forward  |
+    | wgrad             | WGRAD_FP32 / WGRAD_F16X2                                                     | set_conv_wgrad             | backward |
+    | wgrad_narrow      | bool                                                                         | set_conv_wgrad_narrow      | backward |
+    | dilated           | DILATED_TORCH / DILATED_M3D                                                  | set_conv_dilated           | forward  |
+    | wgrad_narrow_f16  | None: the narrow f16x2 wgrad is off; else its threshold in products per tap  | set_conv_wgrad_narrow_f16  | backward |
+    | dilated_f16       | None: the dilation-2 f16x2 kernel is off; else its threshold in launch units | set_conv_dilated_f16       | forward  |
+    | wgrad_dilated_f16 | None: the dilation-2 f16x2 wgrad is off; else its threshold in products/tap  | set_conv_wgrad_dilated_f16 | backward |
+    "forward" (FORWARD_FIELDS): the value of the forward call - the conv Function keeps the forward's setting and its backward follows
+    it, whatever the setters were told in between.  "backward" (BACKWARD_FIELDS): the value when the backward runs - the Function puts
+    the current ones into the kept setting before it asks plan_train_backward."""
     __slots__ = ()
+
+
+FORWARD_FIELDS = ("train", "min_units", "narrow", "dilated", "dilated_f16")
+BACKWARD_FIELDS = ("wgrad", "wgrad_narrow", "wgrad_narrow_f16", "wgrad_dilated_f16")
 
 
 # forward: TRAIN_FP32 / TRAIN_F16X2 / TRAIN_F16X2_NARROW / TRAIN_DILATED / TRAIN_DILATED_F16X2; sweep: the forward sweeps x for its operand bound and keeps it
@@ -232,59 +237,57 @@ def _dilated_takes(batch, ci, co, D, H, W, min_units):
     return L.m3d_conv3d_zn_dilated_launch_units(batch, ci, co, D, H, W, 2) >= int(min_units)
 
 
-def _dilated_rule(direction, setting, xshape, wshape, dilated_f16):
-    """the forward / dgrad kind of a dilation-2 layer: TRAIN_DILATED_F16X2 where the switch is on (dilated_f16: its threshold in launch
-    units) under DILATED_M3D and the kernel takes the LAUNCHED conv (a dgrad swaps the channel roles, as train_conv_kernel does), else
-    TRAIN_DILATED.  With dilated_f16 None no library query is made."""
-    if dilated_f16 is None or setting.dilated != DILATED_M3D or int(wshape[2]) != 3:
+def _dilated_rule(direction, setting, xshape, wshape):
+    """the forward / dgrad kind of a dilation-2 layer: TRAIN_DILATED_F16X2 where the switch is on (setting.dilated_f16: its threshold in
+    launch units) under DILATED_M3D and the kernel takes the LAUNCHED conv (a dgrad swaps the channel roles, as train_conv_kernel does),
+    else TRAIN_DILATED.  With dilated_f16 None no library query is made."""
+    if setting.dilated_f16 is None or setting.dilated != DILATED_M3D or int(wshape[2]) != 3:
         return TRAIN_DILATED
     B, _, D, H, W = (int(v) for v in xshape)
     ci, co = (int(wshape[1]), int(wshape[0])) if direction == "forward" else (int(wshape[0]), int(wshape[1]))
-    return TRAIN_DILATED_F16X2 if _dilated_takes(B, ci, co, D, H, W, dilated_f16) else TRAIN_DILATED
+    return TRAIN_DILATED_F16X2 if _dilated_takes(B, ci, co, D, H, W, setting.dilated_f16) else TRAIN_DILATED
 
 
-def plan_train_forward(setting, xshape, wshape, dilation, dilated_f16=None):
-    """(forward, sweep) of plan_train_conv: what the forward of the call needs, and no library query beyond that.  dilated_f16: None (the
-    dilation-2 f16x2 kernel is off), else its routing threshold in launch units (compat.set_conv_dilated_f16)"""
+def plan_train_forward(setting, xshape, wshape, dilation):
+    """(forward, sweep) of plan_train_conv: what the forward of the call needs, and no library query beyond that"""
     if dilation == 2:
-        forward = _dilated_rule("forward", setting, xshape, wshape, dilated_f16)
+        forward = _dilated_rule("forward", setting, xshape, wshape)
         return forward, forward == TRAIN_DILATED_F16X2
     forward = _train_rule("forward", setting, xshape, wshape)
     return forward, forward != TRAIN_FP32
 
 
-def _wgrad_dilated_rule(setting, xshape, wshape, wgrad_dilated_f16):
-    """the wgrad kind of a dilation-2 layer: WGRAD_DILATED_F16X2 where the switch is on (wgrad_dilated_f16: its threshold in products per
-    tap) under DILATED_M3D, k = 3, m3d_conv3d_wgrad_narrow_dilated_f16x2_supported takes the shape at dilation 2 and the work reaches the
-    threshold, else WGRAD_DILATED.  With wgrad_dilated_f16 None no library query is made."""
-    if wgrad_dilated_f16 is None or setting.dilated != DILATED_M3D or int(wshape[2]) != 3:
+def _wgrad_dilated_rule(setting, xshape, wshape):
+    """the wgrad kind of a dilation-2 layer: WGRAD_DILATED_F16X2 where the switch is on (setting.wgrad_dilated_f16: its threshold in
+    products per tap) under DILATED_M3D, k = 3, m3d_conv3d_wgrad_narrow_dilated_f16x2_supported takes the shape at dilation 2 and the
+    work reaches the threshold, else WGRAD_DILATED.  With wgrad_dilated_f16 None no library query is made."""
+    if setting.wgrad_dilated_f16 is None or setting.dilated != DILATED_M3D or int(wshape[2]) != 3:
         return WGRAD_DILATED
     B, _, D, H, W = (int(v) for v in xshape)
     cout, cin = int(wshape[0]), int(wshape[1])
-    if ops.conv3d_wgrad_narrow_f16x2_supported(B, cin, cout, D, H, W, dilation=2) and B * D * H * W * cin * cout >= int(wgrad_dilated_f16):
+    if (ops.conv3d_wgrad_narrow_f16x2_supported(B, cin, cout, D, H, W, dilation=2)
+            and B * D * H * W * cin * cout >= int(setting.wgrad_dilated_f16)):
         return WGRAD_DILATED_F16X2
     return WGRAD_DILATED
 
 
-def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None, wgrad_dilated_f16=None):
-    """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs.  wgrad_narrow_f16: None (the narrow f16x2
-    wgrad kernel is off), else its routing threshold in products per tap (compat.set_conv_wgrad_narrow_f16); dilated_f16: as
-    plan_train_forward's; wgrad_dilated_f16: None (the dilation-2 f16x2 wgrad kernel is off: the result is what it was without the
-    argument, and no further library query is made), else its routing threshold in products per tap (compat.set_conv_wgrad_dilated_f16)"""
+def plan_train_backward(setting, xshape, wshape, dilation, needs):
+    """(dgrad, wgrad, gy_reduce, gb) of plan_train_conv: what the backward of the call needs.  A switch left at None changes nothing and
+    asks the library nothing."""
     gx, gw, gb = (bool(v) for v in needs)
     if dilation == 2:                                  # train, wgrad and wgrad_narrow_f16 do not reach these layers
-        dgrad = _dilated_rule("dgrad", setting, xshape, wshape, dilated_f16) if gx else None
+        dgrad = _dilated_rule("dgrad", setting, xshape, wshape) if gx else None
         gy_reduce = dgrad == TRAIN_DILATED_F16X2       # gy's bound, and then the bias gradient too: the rule of TRAIN_F16X2_NARROW
         # WGRAD_DILATED_F16X2 asks for nothing, as WGRAD_NARROW_F16X2 does not: it takes gy's bound where the pass ran and sweeps otherwise
-        wgrad = _wgrad_dilated_rule(setting, xshape, wshape, wgrad_dilated_f16) if gw else None
+        wgrad = _wgrad_dilated_rule(setting, xshape, wshape) if gw else None
         return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
     B, _, D, H, W = xshape
     cout, cin, k = wshape[:3]
     dgrad = None if not gx else DGRAD_STEM if k == 5 else _train_rule("dgrad", setting, xshape, wshape)
     # base: the wgrad kernel without the narrow f16x2 switch (the only one asked while that switch is off)
     base = wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow) if gw else None
-    wgrad = base if base is None or wgrad_narrow_f16 is None else \
-        wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow, narrow_f16=wgrad_narrow_f16)
+    wgrad = base if base is None or setting.wgrad_narrow_f16 is None else \
+        wgrad_kernel(B, cin, cout, D, H, W, setting.wgrad, k=k, narrow=setting.wgrad_narrow, narrow_f16=setting.wgrad_narrow_f16)
     # one pass over gy gives the bound both f16x2 kernels scale gy by, and the bias gradient.  In train mode f16x2 gb ALWAYS comes from
     # it, so that a change of route (another batch size, min_units) never changes gb; in mode fp32 only the narrow f16x2 dgrad asks for
     # it (the f16x2 wgrad then sweeps both operands itself).  WGRAD_NARROW_F16X2 asks for nothing: the pass runs where it would have run
@@ -294,18 +297,16 @@ def plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f
     return dgrad, wgrad, gy_reduce, ((GB_REDUCE if gy_reduce else GB_BIAS_GRAD) if gb else None)
 
 
-def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=None, dilated_f16=None, wgrad_dilated_f16=None):
+def plan_train_conv(setting, xshape, wshape, dilation, needs):
     """What a training conv that m3d.compat.conv3d routes to the library launches, forward and backward: a TrainConvPlan.  The only place
     that combines the rules (train_conv_kernel and wgrad_kernel are its rows); host queries of the library only, a function of its
     arguments only.  setting: a TrainSetting; xshape [B, cin, D, H, W]; wshape [cout, cin, k, k, k]; dilation: 1 (stride 1, padding
     k // 2, k in {1, 3} or the 5^3 / Cin = 1 stem) or 2 (k = 3, padding 2, only routed under DILATED_M3D); needs = (gx, gw, gb) of
-    needs_input_grad, gb already False for a layer without bias; wgrad_narrow_f16: None or the threshold of
-    compat.set_conv_wgrad_narrow_f16 (it moves the wgrad field only: gy_reduce and gb do not depend on it); dilated_f16: None or the
-    threshold in launch units of compat.set_conv_dilated_f16 (it moves dilation-2 layers under DILATED_M3D only).  "dilated f16x2
-    takes": dilated_f16 is a threshold, setting.dilated is DILATED_M3D, m3d_conv3d_zn_dilated_supported takes the LAUNCHED conv at
-    dilation 2 (a dgrad swaps the channel roles) and m3d_conv3d_zn_dilated_launch_units reaches the threshold.  wgrad_dilated_f16: None
-    or the threshold in products per tap of compat.set_conv_wgrad_dilated_f16 (it moves the wgrad field of dilation-2 layers under
-    DILATED_M3D only: gy_reduce and gb do not depend on it, and wgrad_narrow_f16 keeps not touching these layers).
+    needs_input_grad, gb already False for a layer without bias.  setting.wgrad_narrow_f16 moves the wgrad field of dilation-1 layers
+    only and setting.wgrad_dilated_f16 that of dilation-2 layers under DILATED_M3D only: gy_reduce and gb depend on neither.
+    setting.dilated_f16 moves dilation-2 layers under DILATED_M3D only.  "dilated f16x2 takes": setting.dilated_f16 is a threshold,
+    setting.dilated is DILATED_M3D, m3d_conv3d_zn_dilated_supported takes the LAUNCHED conv at dilation 2 (a dgrad swaps the channel
+    roles) and m3d_conv3d_zn_dilated_launch_units reaches the threshold.
 
     | field     | value              | condition                                                                                      |
     | forward   | TRAIN_DILATED_F16X2| dilation 2 and dilated f16x2 takes the forward conv                                            |
@@ -318,10 +319,11 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=N
     |           | DGRAD_STEM         | k = 5                                                                                          |
     |           | else               | train_conv_kernel("dgrad", ...)                                                                |
     | wgrad     | None               | gw not needed                                                                                  |
-    |           | WGRAD_DILATED_F16X2| dilation 2, wgrad_dilated_f16 is a threshold, DILATED_M3D, k = 3,                              |
+    |           | WGRAD_DILATED_F16X2| dilation 2, setting.wgrad_dilated_f16 is a threshold, DILATED_M3D, k = 3,                      |
     |           |                    | m3d_conv3d_wgrad_narrow_dilated_f16x2_supported at dilation 2, work >= it                      |
     |           | WGRAD_DILATED      | dilation 2 otherwise                                                                           |
-    |           | WGRAD_NARROW_F16X2 | wgrad_narrow_f16 is a threshold, k = 3, m3d_conv3d_wgrad_narrow_f16x2_supported, work >= it    |
+    |           | WGRAD_NARROW_F16X2 | setting.wgrad_narrow_f16 is a threshold, k = 3, m3d_conv3d_wgrad_narrow_f16x2_supported,       |
+    |           |                    | work >= it                                                                                     |
     |           | else               | wgrad_kernel(...) under setting.wgrad / wgrad_narrow                                           |
     | gy_reduce | True               | dilation 1 and: train is f16x2 and (dgrad or wgrad is f16x2, or gb needed); or dgrad is narrow |
     |           | True               | dilation 2 and dgrad is TRAIN_DILATED_F16X2                                                    |
@@ -331,9 +333,8 @@ def plan_train_conv(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16=N
 
     compat asks the two halves when it needs them (plan_train_forward in forward, plan_train_backward in backward): a call makes the
     library queries of the directions it runs and no others."""
-    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation, dilated_f16)
-                           + plan_train_backward(setting, xshape, wshape, dilation, needs, wgrad_narrow_f16, dilated_f16,
-                                                 wgrad_dilated_f16)))
+    return TrainConvPlan(*(plan_train_forward(setting, xshape, wshape, dilation)
+                           + plan_train_backward(setting, xshape, wshape, dilation, needs)))
 
 
 def plan_conv(layer, shape, argmax=False, f16=True, winograd=True, narrow_f16=False):

@@ -182,9 +182,9 @@ def test_the_switch_round_trips_and_install_leaves_it_off():
     import m3d.compat as c
     from m3d import conv_plan as P
     assert c.get_conv_dilated_f16() is False
-    assert c.set_conv_dilated_f16(True) is False and c.get_conv_dilated_f16() is True and c._dilated_f16 == P.ZN_DILATED_MIN_UNITS
+    assert c.set_conv_dilated_f16(True) is False and c.get_conv_dilated_f16() is True and c._setting.dilated_f16 == P.ZN_DILATED_MIN_UNITS
     assert c.get_conv_dilated() == "torch"                                  # it does not turn the dilated route on by itself
-    assert c.set_conv_dilated_f16(True, min_units=0) is True and c._dilated_f16 == 0
+    assert c.set_conv_dilated_f16(True, min_units=0) is True and c._setting.dilated_f16 == 0
     with pytest.raises(ValueError):
         c.set_conv_dilated_f16(True, min_units=-1)
     assert c.set_conv_dilated_f16(False) is True and c.get_conv_dilated_f16() is False

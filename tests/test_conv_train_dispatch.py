@@ -10,6 +10,8 @@ their arguments and their order must not move, and a call on a shape seen before
 
 The "flip" records turn every switch over between the forward and the backward of a call: they pin WHEN each switch is read (the train
 mode, its threshold, the narrow switch and the dilated mode at forward time; the two wgrad switches when the backward runs).
+test_each_field_is_read_when_its_table_says does the same for every field of conv_plan.TrainSetting, one at a time, against
+conv_plan.FORWARD_FIELDS / BACKWARD_FIELDS.
 """
 import gzip
 import inspect
@@ -21,7 +23,7 @@ import re
 import pytest
 import torch
 
-from conv_record import CudaMeta, install
+from conv_record import DEFAULT, DILATED, NEEDS, SETTINGS, WGRAD, CudaMeta, install, meta, setting_key, train_setting
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "conv_train_dispatch.json.gz")
@@ -52,26 +54,11 @@ LAYERS = {
 }
 FLIP_LAYERS = ("body 64-64", "roi R16 256-256", "dil2 32-32", "map W8 64-64", "work 2^27 128-256")
 
-TRAIN = (("fp32", None), ("f16x2", None), ("f16x2", 0))          # set_conv_train(mode, min_units)
-NARROW = ((False, None), (True, None), (True, 0))                # set_conv_train_narrow(on, min_units)
-WGRAD = ("fp32", "f16x2")
-WGRAD_NARROW = (False, True)
-DILATED = ("torch", "m3d")
-SETTINGS = tuple(itertools.product(TRAIN, NARROW, WGRAD, WGRAD_NARROW, DILATED))
-# (x, weight, bias) requires_grad; None: the layer has no bias
-NEEDS = {"xwb": (True, True, True), "-wb": (False, True, True), "x--": (True, False, False), "xw.": (True, True, None)}
-
-
 def flipped(setting):
     """every switch turned over"""
     (mode, _), (narrow, _), wgrad, wn, dil = setting
     return (("fp32", None) if mode == "f16x2" else ("f16x2", 0), (False, None) if narrow else (True, 0),
             WGRAD[wgrad == "fp32"], not wn, DILATED[dil == "torch"])
-
-
-def setting_key(setting):
-    (mode, mu), (narrow, nmu), wgrad, wn, dil = setting
-    return "train=%s/%s narrow=%s/%s wgrad=%s wn=%d dil=%s" % (mode, mu, int(narrow), nmu, wgrad, wn, dil)
 
 
 def case_key(layer, needs, setting, flip=False):
@@ -92,19 +79,6 @@ def apply_setting(compat, setting):
     compat.set_conv_wgrad(wgrad)
     compat.set_conv_wgrad_narrow(wn)
     compat.set_conv_dilated(dil)
-
-
-DEFAULT = (("fp32", None), (False, None), "fp32", False, "torch")
-
-
-def meta(shape, grad, contiguous=True):
-    if contiguous:
-        t = torch.empty(shape, device="meta")
-    else:                                                       # channels innermost
-        B, C, D, H, W = shape
-        t = torch.empty_strided(shape, (C * D * H * W, 1, H * W * C, W * C, C), device="meta")
-        assert not t.is_contiguous()
-    return t.as_subclass(CudaMeta).requires_grad_(bool(grad))
 
 
 def run_case(compat, rec, layer, needs, setting, flip):
@@ -202,12 +176,6 @@ def test_switches_are_left_at_their_defaults(recorded):
 
 
 # ----------------------------------------------------------------------------- the plan itself
-def train_setting(cp, setting):
-    (mode, mu), (narrow, nmu), wgrad, wn, dil = setting
-    return cp.TrainSetting(train=mode, min_units=mu, narrow=(cp.ZN_MIN_UNITS if nmu is None else nmu) if narrow else None,
-                           wgrad=wgrad, wgrad_narrow=wn, dilated=dil)
-
-
 def routed(layer, dil):
     """the dilation conv3d() routes this layer's call under: 1, 2 or None (torch)"""
     _, _, dilation, padding, _ = LAYERS[layer]
@@ -241,7 +209,8 @@ def test_plan_is_a_pure_function_of_its_arguments():
     s = cp.TrainSetting(train="f16x2", min_units=0, narrow=0, wgrad="f16x2", wgrad_narrow=True, dilated="m3d")
     args = (s, (2, 64, 17, 33, 63), (64, 64, 3, 3, 3), 1, (True, True, True))
     assert len({cp.plan_train_conv(*args) for _ in range(3)}) == 1
-    assert cp.TrainSetting()._asdict() == dict(train="fp32", min_units=None, narrow=None, wgrad="fp32", wgrad_narrow=False, dilated="torch")
+    assert cp.TrainSetting()._asdict() == dict(train="fp32", min_units=None, narrow=None, wgrad="fp32", wgrad_narrow=False, dilated="torch",
+                                               wgrad_narrow_f16=None, dilated_f16=None, wgrad_dilated_f16=None)
     with pytest.raises(AttributeError):
         s.train = "fp32"                                                    # immutable
 
@@ -287,10 +256,93 @@ def test_plan_agrees_with_the_rules_on_every_grid_point():
 
 
 def test_backward_has_no_routing_left():
-    """no branch of _Conv3dFn.backward tests a switch or a mode string: it runs the plan's fields"""
-    from m3d import compat
+    """no branch of _Conv3dFn.backward tests a switch or a mode string: it runs the plan's fields, the kernel kinds from two tables"""
+    from m3d import compat, conv_plan as cp
     branches = [line.strip() for line in inspect.getsource(compat._Conv3dFn.backward).splitlines() if line.strip().startswith(("if ", "elif "))]
-    assert len(branches) == 11
+    assert len(branches) == 2
     for line in branches:                                                   # each tests one field of the plan against one kind
         assert re.fullmatch(r"(if|elif) (gy_reduce|(dgrad|wgrad|gb_from) == conv_plan\.[A-Z0-9_]+):", line), line
     assert not hasattr(compat, "_Conv3dDilated2Fn")
+    for fn in (compat._Conv3dFn.forward, compat._Conv3dFn.backward):
+        lines = [line for line in inspect.getsource(fn).splitlines() if "BACKWARD_FIELDS" not in line]
+        assert not any("assert" in line or "_setting." in line for line in lines), fn.__name__
+    assert len([line for line in inspect.getsource(compat._Conv3dFn.backward).splitlines() if "BACKWARD_FIELDS" in line]) == 1
+    assert "BACKWARD_FIELDS" not in inspect.getsource(compat._Conv3dFn.forward)
+    assert set(compat._CONV_KINDS) == {cp.TRAIN_FP32, cp.TRAIN_F16X2, cp.TRAIN_F16X2_NARROW, cp.TRAIN_DILATED, cp.TRAIN_DILATED_F16X2,
+                                       cp.DGRAD_STEM}
+    assert set(compat._WGRAD_KINDS) == {cp.WGRAD_FP32, cp.WGRAD_F16X2, cp.WGRAD_NARROW, cp.WGRAD_NARROW_F16X2, cp.WGRAD_DILATED,
+                                        cp.WGRAD_DILATED_F16X2}
+    assert len(compat._CONV_KINDS) == len(compat._WGRAD_KINDS) == 6         # (kinds of the two families share strings: no key collapsed)
+
+
+# ----------------------------------------------------------------------------- when each field of the setting is read
+DIL2_ROI = ((4, 32, 7, 7, 7), (32, 32, 3), 2, 2, True)          # the mask head's 7^3 RoI grid at dilation 2: both dilated f16x2 kernels take it
+# field: (layer, base setting A as TrainSetting fields, value v): the smallest layer at which the field moves a launch; thresholds 0
+FIELD_CASES = {
+    "train": (LAYERS["body 64-64"], {}, "f16x2"),
+    "min_units": (LAYERS["body 64-64"], dict(train="f16x2", min_units=1 << 30), 0),
+    "narrow": (LAYERS["roi R16 256-256"], {}, 0),
+    "wgrad": (LAYERS["work 2^27 128-256"], {}, "f16x2"),
+    "wgrad_narrow": (LAYERS["roi R4 32-64"], {}, True),
+    "wgrad_narrow_f16": (LAYERS["roi R4 32-64"], {}, 0),
+    "dilated": (LAYERS["dil2 32-32"], dict(dilated="m3d"), "torch"),        # the backward of a library forward stays in the library
+    "dilated_f16": (DIL2_ROI, dict(dilated="m3d"), 0),
+    "wgrad_dilated_f16": (DIL2_ROI, dict(dilated="m3d"), 0),
+}
+
+
+def apply_train_setting(compat, s):
+    """a whole TrainSetting through the eight setters"""
+    compat.set_conv_train(s.train, s.min_units)
+    compat.set_conv_train_narrow(s.narrow is not None, s.narrow)
+    compat.set_conv_wgrad(s.wgrad)
+    compat.set_conv_wgrad_narrow(s.wgrad_narrow)
+    compat.set_conv_dilated(s.dilated)
+    compat.set_conv_wgrad_narrow_f16(s.wgrad_narrow_f16 is not None, s.wgrad_narrow_f16)
+    compat.set_conv_dilated_f16(s.dilated_f16 is not None, s.dilated_f16)
+    compat.set_conv_wgrad_dilated_f16(s.wgrad_dilated_f16 is not None, s.wgrad_dilated_f16)
+    assert compat._setting == s
+
+
+def run_fields(compat, rec, layer, at_forward, at_backward):
+    """-> {"forward": launches | "torch", "backward": launches}: the forward under the TrainSetting at_forward, the backward under at_backward"""
+    xshape, (cout, cin, k), dilation, padding, contiguous = layer
+    apply_train_setting(compat, at_forward)
+    x, w, b = meta(xshape, True, contiguous), meta((cout, cin, k, k, k), True), meta((cout,), True)
+    rec.take()
+    y = compat.conv3d(x, w, b, 1, padding, dilation, 1)
+    fwd, _ = rec.take()
+    if isinstance(y, str):                                      # the stand-in for torch's conv3d
+        return {"forward": "torch"}
+    apply_train_setting(compat, at_backward)
+    grads = torch.autograd.grad(y, [x, w, b], torch.empty(y.shape, device="meta").as_subclass(CudaMeta))
+    assert all(g is not None for g in grads)
+    return {"forward": fwd, "backward": rec.take()[0]}
+
+
+def test_each_field_is_read_when_its_table_says():
+    """one field at a time, in the form of the flip records: the forward under a base setting A, the field set to v before the backward.
+    A FORWARD_FIELDS field: the call launches what it launches under A throughout; a BACKWARD_FIELDS field: its backward is the
+    backward under "A with the field at v" throughout.  Each (A, v) moves a launch, so no field is tested vacuously."""
+    with pytest.MonkeyPatch.context() as mp:
+        rec = install(mp)
+        from m3d import compat, conv_plan as cp
+        mp.setattr(compat, "_orig_conv3d", lambda *a: "torch")
+        assert sorted(cp.FORWARD_FIELDS + cp.BACKWARD_FIELDS) == sorted(cp.TrainSetting._fields)
+        assert set(cp.FORWARD_FIELDS) == {"train", "min_units", "narrow", "dilated", "dilated_f16"}
+        assert set(cp.BACKWARD_FIELDS) == {"wgrad", "wgrad_narrow", "wgrad_narrow_f16", "wgrad_dilated_f16"}
+        assert sorted(FIELD_CASES) == sorted(cp.TrainSetting._fields)
+        try:
+            for field, (layer, base, v) in FIELD_CASES.items():
+                A = cp.TrainSetting(**base)
+                Av = A._replace(**{field: v})
+                under_a, under_v = run_fields(compat, rec, layer, A, A), run_fields(compat, rec, layer, Av, Av)
+                assert under_a != under_v and under_a["forward"] != "torch", field
+                got = run_fields(compat, rec, layer, A, Av)
+                if field in cp.FORWARD_FIELDS:
+                    assert got == under_a, field
+                else:
+                    assert got["forward"] == under_a["forward"] == under_v["forward"], field
+                    assert got["backward"] == under_v["backward"] != under_a["backward"], field
+        finally:
+            apply_train_setting(compat, cp.TrainSetting())

@@ -10,8 +10,8 @@ move are the mask head's on the 7^3 RoI grid, added below under "dil2 roi ...": 
 backward-data run on m3d_conv3d_zn_dilated_forward (dilation argument 2, a swept bound in front of the forward, m3d_conv3d_gy_reduce
 in front of the dgrad, which then also gives the bias gradient), the weight gradient stays on m3d_conv3d_wgrad_dilated with the
 arguments it had, and nothing else moves; a direction whose launched input channels are no multiple of 16 stays on the fp32 kernel.
-Under dil=torch nothing moves.  The flip records show that the switch is read at forward time.  plan_train_conv(dilated_f16=) agrees
-with the table of its docstring on every grid point, and with None it is the plan without the argument."""
+Under dil=torch nothing moves.  The flip records show that the switch is read at forward time.  plan_train_conv under a setting with
+dilated_f16 agrees with the table of its docstring on every grid point, and with None it is the plan of the setting without it."""
 import gzip
 import itertools
 import json
@@ -234,12 +234,13 @@ def test_the_plan_agrees_with_the_table_on_every_grid_point():
         gx, gw, gb = (bool(v) for v in G.NEEDS[needs])
         args = (s, xshape, (cout, cin, k, k, k), routed, (gx, gw, gb))
         base = cp.plan_train_conv(*args)
-        assert cp.plan_train_conv(*args, dilated_f16=None) == base                  # None: today's plan
-        assert cp.plan_train_forward(*args[:4]) == cp.plan_train_forward(*args[:4], None) == tuple(base[:2])
+        assert cp.plan_train_conv(s._replace(dilated_f16=None), *args[1:]) == base  # None: today's plan
+        assert cp.plan_train_forward(*args[:4]) == cp.plan_train_forward(s._replace(dilated_f16=None), *args[1:4]) == tuple(base[:2])
         for min_units in (0, cp.ZN_DILATED_MIN_UNITS, 1 << 40):
-            p = cp.plan_train_conv(*args, dilated_f16=min_units)
-            assert cp.plan_train_forward(*args[:4], dilated_f16=min_units) == tuple(p[:2])
-            assert cp.plan_train_backward(*args, dilated_f16=min_units) == tuple(p[2:])
+            on = s._replace(dilated_f16=min_units)
+            p = cp.plan_train_conv(on, *args[1:])
+            assert cp.plan_train_forward(on, *args[1:4]) == tuple(p[:2])
+            assert cp.plan_train_backward(on, *args[1:]) == tuple(p[2:])
             if routed == 1:
                 assert p == base, (layer, needs, setting)
                 continue
@@ -253,6 +254,6 @@ def test_the_plan_agrees_with_the_table_on_every_grid_point():
             new += f or d
         # without set_conv_dilated("m3d") in the setting the switch has no effect on the plan either
         if dilation == 2:
-            assert cp.plan_train_conv(s._replace(dilated="torch"), *args[1:], dilated_f16=0) == base == \
+            assert cp.plan_train_conv(s._replace(dilated="torch", dilated_f16=0), *args[1:]) == base == \
                 cp.plan_train_conv(s._replace(dilated="torch"), *args[1:])
     assert new > 0

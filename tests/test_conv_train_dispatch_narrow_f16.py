@@ -15,7 +15,7 @@ import os
 import pytest
 import torch
 
-from conv_record import CudaMeta, install
+from conv_record import DEFAULT, NEEDS, SETTINGS, CudaMeta, install, meta, setting_key, train_setting
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "conv_train_dispatch.json.gz")
@@ -34,24 +34,11 @@ LAYERS = {
 }
 TAKEN = ("roi R4 32-64", "roi R16 256-256", "roi R15 256-256", "roi R70 256-32", "map W8 64-64")     # W <= 8, channels multiples of 32, k = 3
 
-TRAIN = (("fp32", None), ("f16x2", None), ("f16x2", 0))          # set_conv_train(mode, min_units)
-NARROW = ((False, None), (True, None), (True, 0))                # set_conv_train_narrow(on, min_units)
-WGRAD = ("fp32", "f16x2")
-WGRAD_NARROW = (False, True)
-DILATED = ("torch", "m3d")
-SETTINGS = tuple(itertools.product(TRAIN, NARROW, WGRAD, WGRAD_NARROW, DILATED))
-DEFAULT = (("fp32", None), (False, None), "fp32", False, "torch")
-NEEDS = {"xwb": (True, True, True), "-wb": (False, True, True), "x--": (True, False, False), "xw.": (True, True, None)}
 OFF, ON0, ON = (False, None), (True, 0), (True, None)            # set_conv_wgrad_narrow_f16(on, min_work)
 
 OLD_WGRADS = ("m3d_conv3d_wgrad", "m3d_conv3d_wgrad_f16x2", "m3d_conv3d_wgrad_narrow")
 NEW = "m3d_conv3d_wgrad_narrow_f16x2"
 SWEEP = "m3d_conv3d_zw_bound_of"
-
-
-def setting_key(setting):
-    (mode, mu), (narrow, nmu), wgrad, wn, dil = setting
-    return "train=%s/%s narrow=%s/%s wgrad=%s wn=%d dil=%s" % (mode, mu, int(narrow), nmu, wgrad, wn, dil)
 
 
 def apply_setting(compat, setting, nf):
@@ -62,10 +49,6 @@ def apply_setting(compat, setting, nf):
     compat.set_conv_wgrad_narrow(wn)
     compat.set_conv_dilated(dil)
     compat.set_conv_wgrad_narrow_f16(*nf)
-
-
-def meta(shape, grad):
-    return torch.empty(shape, device="meta").as_subclass(CudaMeta).requires_grad_(bool(grad))
 
 
 def run_case(compat, rec, layer, needs, setting, nf, nf_backward=None):
@@ -131,12 +114,6 @@ def wgrad_span(backward, names):
     return a, at[0] + 1
 
 
-def train_setting(cp, setting):
-    (mode, mu), (narrow, nmu), wgrad, wn, dil = setting
-    return cp.TrainSetting(train=mode, min_units=mu, narrow=(cp.ZN_MIN_UNITS if nmu is None else nmu) if narrow else None,
-                           wgrad=wgrad, wgrad_narrow=wn, dilated=dil)
-
-
 def test_switch_off_is_the_golden_record(recorded):
     with gzip.open(FIXTURE, "rt") as f:
         fixture = json.load(f)
@@ -171,8 +148,8 @@ def test_min_work_0_moves_the_wgrad_launch_of_every_taken_layer_and_nothing_else
         assert launch[10] == "ptr" and launch[11] == "ptr" and launch[12] == "ptr", key                          # x_max, gy_max, workspace
         assert launch[13] == cp.ops.conv3d_wgrad_narrow_f16x2_plan(B, cin, cout, D, H, W)["slots"] * 27 * cin * cout * 4, key
         # a sweep exactly for each bound the plan did not hold: x's from the forward's sweep, gy's from gy_reduce
-        p = cp.plan_train_conv(train_setting(cp, setting), xshape, (cout, cin, k, k, k), dilation,
-                               tuple(bool(v) for v in NEEDS[needs]), wgrad_narrow_f16=0)
+        p = cp.plan_train_conv(train_setting(cp, setting)._replace(wgrad_narrow_f16=0), xshape, (cout, cin, k, k, k), dilation,
+                               tuple(bool(v) for v in NEEDS[needs]))
         assert p.wgrad == cp.WGRAD_NARROW_F16X2, key
         assert d - 1 - c == (not p.sweep) + (not p.gy_reduce), key
         assert any(launch[0] == "m3d_conv3d_gy_reduce" for launch in on["backward"]) == p.gy_reduce, key

@@ -226,7 +226,7 @@ def test_routing_through_compat(ops, compat):
     assert torch.equal(gw0, ops.conv3d_wgrad(x, r, 3, dilation=2))
     assert compat.set_conv_wgrad_dilated_f16(True, min_work=0) is False
     s = cp.TrainSetting(dilated="m3d")
-    assert cp.plan_train_conv(s, x.shape, conv.weight.shape, 2, (True, True, True), wgrad_dilated_f16=0).wgrad == cp.WGRAD_DILATED_F16X2
+    assert cp.plan_train_conv(s._replace(wgrad_dilated_f16=0), x.shape, conv.weight.shape, 2, (True, True, True)).wgrad == cp.WGRAD_DILATED_F16X2
     y1, gx1, gw1, gb1 = _step(conv, x, r)
     assert torch.equal(gw1, d2(ops, x, r))                                                  # this kernel's dW bit for bit
     assert float((gw1 - gw0).abs().max()) <= 1e-5 * float(gw0.abs().max())
@@ -243,7 +243,7 @@ def test_routing_through_compat(ops, compat):
     compat.set_conv_dilated_f16(False)
     # the default threshold is the constant
     compat.set_conv_wgrad_dilated_f16(True)
-    want = cp.plan_train_conv(s, x.shape, conv.weight.shape, 2, (True, True, True), wgrad_dilated_f16=cp.WGRAD_DILATED_F16X2_MIN_WORK).wgrad
+    want = cp.plan_train_conv(s._replace(wgrad_dilated_f16=cp.WGRAD_DILATED_F16X2_MIN_WORK), x.shape, conv.weight.shape, 2, (True, True, True)).wgrad
     assert torch.equal(_step(conv, x, r)[2], gw1 if want == cp.WGRAD_DILATED_F16X2 else gw0)
     compat.set_conv_wgrad_dilated_f16(True, 0)
     # a W = 12 dilation-2 layer and every dilation-1 layer are unchanged

@@ -327,10 +327,11 @@ def test_the_plan_without_the_keyword_is_todays(L):
             for dilation in (1, 2):
                 for needs in (NEEDS, (True, False, True), (False, True, False)):
                     for nf, df in ((None, None), (0, None), (None, 0), (0, 0)):
-                        today = cp.plan_train_conv(s, x, w, dilation, needs, wgrad_narrow_f16=nf, dilated_f16=df)
-                        assert cp.plan_train_conv(s, x, w, dilation, needs, wgrad_narrow_f16=nf, dilated_f16=df, wgrad_dilated_f16=None) == today
+                        t = s._replace(wgrad_narrow_f16=nf, dilated_f16=df)
+                        today = cp.plan_train_conv(t, x, w, dilation, needs)
+                        assert cp.plan_train_conv(t._replace(wgrad_dilated_f16=None), x, w, dilation, needs) == today
                         assert today.wgrad != cp.WGRAD_DILATED_F16X2
-                        assert cp.plan_train_backward(s, x, w, dilation, needs, nf, df, None) == tuple(today)[2:]
+                        assert cp.plan_train_backward(t._replace(wgrad_dilated_f16=None), x, w, dilation, needs) == tuple(today)[2:]
 
 
 def test_none_makes_no_further_library_query(L):
@@ -341,18 +342,18 @@ def test_none_makes_no_further_library_query(L):
         s = cp.TrainSetting(dilated="m3d")
         for df in (None, 0):
             rec.take()
-            cp.plan_train_conv(s, X7, W7, 2, NEEDS, dilated_f16=df)
+            cp.plan_train_conv(s._replace(dilated_f16=df), X7, W7, 2, NEEDS)
             q0 = rec.take()[1]
-            cp.plan_train_conv(s, X7, W7, 2, NEEDS, dilated_f16=df, wgrad_dilated_f16=None)
+            cp.plan_train_conv(s._replace(dilated_f16=df, wgrad_dilated_f16=None), X7, W7, 2, NEEDS)
             assert rec.take()[1] == q0
-            cp.plan_train_conv(s, X7, W7, 2, NEEDS, dilated_f16=df, wgrad_dilated_f16=0)
+            cp.plan_train_conv(s._replace(dilated_f16=df, wgrad_dilated_f16=0), X7, W7, 2, NEEDS)
             assert rec.take()[1] == q0 + 1                                              # the one _supported query
-            cp.plan_train_conv(s, X7, W7, 2, (True, False, True), dilated_f16=df, wgrad_dilated_f16=0)
+            cp.plan_train_conv(s._replace(dilated_f16=df, wgrad_dilated_f16=0), X7, W7, 2, (True, False, True))
             assert rec.take()[1] == q0                                                  # gw not needed: not asked
         rec.take()
         cp.plan_train_conv(cp.TrainSetting(), X7, W7, 1, NEEDS)
         q1 = rec.take()[1]
-        cp.plan_train_conv(cp.TrainSetting(), X7, W7, 1, NEEDS, wgrad_dilated_f16=0)
+        cp.plan_train_conv(cp.TrainSetting()._replace(wgrad_dilated_f16=0), X7, W7, 1, NEEDS)
         assert rec.take()[1] == q1                                                      # dilation 1: not asked either
 
 
@@ -368,50 +369,51 @@ def test_a_threshold_moves_exactly_the_wgrad_field_of_supported_dilation_2_layer
             takes = bool(L.m3d_conv3d_wgrad_narrow_dilated_f16x2_supported(B, cin, cout, D, H, W, 2))
             assert takes == (W <= 8 and cin % 32 == 0 and cout % 32 == 0), (x, w)
             for nf, df in ((None, None), (0, None), (None, 0), (0, 0)):
-                kw = dict(wgrad_narrow_f16=nf, dilated_f16=df)
-                off = cp.plan_train_conv(s, x, w, 2, NEEDS, **kw)
+                t = s._replace(wgrad_narrow_f16=nf, dilated_f16=df)
+                off = cp.plan_train_conv(t, x, w, 2, NEEDS)
                 assert off.wgrad == cp.WGRAD_DILATED                                    # wgrad_narrow_f16 keeps not touching dilation 2
                 for thr in (0, work):                                                   # at or above the threshold
-                    on = cp.plan_train_conv(s, x, w, 2, NEEDS, wgrad_dilated_f16=thr, **kw)
+                    on = cp.plan_train_conv(t._replace(wgrad_dilated_f16=thr), x, w, 2, NEEDS)
                     want = cp.WGRAD_DILATED_F16X2 if takes and s.dilated == "m3d" else cp.WGRAD_DILATED
                     assert on.wgrad == want, (s, x, w, thr)
                     assert on._replace(wgrad=off.wgrad) == off                          # forward, sweep, dgrad, gy_reduce, gb
                     moved += on.wgrad != off.wgrad
-                    assert cp.plan_train_backward(s, x, w, 2, NEEDS, nf, df, thr) == tuple(on)[2:]
-                    assert cp.plan_train_backward(s, x, w, 2, NEEDS, nf, df, wgrad_dilated_f16=thr) == tuple(on)[2:]
-                assert cp.plan_train_conv(s, x, w, 2, NEEDS, wgrad_dilated_f16=work + 1, **kw) == off        # one product below it
-                assert cp.plan_train_conv(s, x, w, 2, (True, False, True), wgrad_dilated_f16=0, **kw).wgrad is None
-                # dilation-1 plans ignore the new keyword
-                assert cp.plan_train_conv(s, x, w, 1, NEEDS, wgrad_dilated_f16=0, **kw) == cp.plan_train_conv(s, x, w, 1, NEEDS, **kw)
+                    assert cp.plan_train_backward(t._replace(wgrad_dilated_f16=thr), x, w, 2, NEEDS) == tuple(on)[2:]
+                    assert cp.plan_train_backward(s._replace(wgrad_narrow_f16=nf, dilated_f16=df, wgrad_dilated_f16=thr), x, w, 2, NEEDS) == tuple(on)[2:]
+                assert cp.plan_train_conv(t._replace(wgrad_dilated_f16=work + 1), x, w, 2, NEEDS) == off        # one product below it
+                assert cp.plan_train_conv(t._replace(wgrad_dilated_f16=0), x, w, 2, (True, False, True)).wgrad is None
+                # dilation-1 plans ignore the dilated field
+                assert cp.plan_train_conv(t._replace(wgrad_dilated_f16=0), x, w, 1, NEEDS) == cp.plan_train_conv(t, x, w, 1, NEEDS)
     assert moved
     d2 = cp.TrainSetting(dilated="m3d")
-    assert cp.plan_train_conv(d2, X7, W7, 2, NEEDS, wgrad_narrow_f16=0).wgrad == cp.WGRAD_DILATED
-    assert cp.plan_train_conv(d2, X7, W7, 2, NEEDS, wgrad_dilated_f16=0).wgrad == cp.WGRAD_DILATED_F16X2
-    assert cp.plan_train_conv(d2, X7, W7, 1, NEEDS, wgrad_narrow_f16=0, wgrad_dilated_f16=0).wgrad == cp.WGRAD_NARROW_F16X2
+    assert cp.plan_train_conv(d2._replace(wgrad_narrow_f16=0), X7, W7, 2, NEEDS).wgrad == cp.WGRAD_DILATED
+    assert cp.plan_train_conv(d2._replace(wgrad_dilated_f16=0), X7, W7, 2, NEEDS).wgrad == cp.WGRAD_DILATED_F16X2
+    assert cp.plan_train_conv(d2._replace(wgrad_narrow_f16=0, wgrad_dilated_f16=0), X7, W7, 1, NEEDS).wgrad == cp.WGRAD_NARROW_F16X2
     # the default threshold: the constant, in products per tap
     w = cp.WGRAD_DILATED_F16X2_MIN_WORK
     R = -(-w // (343 * 256 * 256))
     big = (256, 256, 3, 3, 3)
-    assert cp.plan_train_conv(d2, (R, 256, 7, 7, 7), big, 2, NEEDS, wgrad_dilated_f16=w).wgrad == cp.WGRAD_DILATED_F16X2
+    assert cp.plan_train_conv(d2._replace(wgrad_dilated_f16=w), (R, 256, 7, 7, 7), big, 2, NEEDS).wgrad == cp.WGRAD_DILATED_F16X2
     if R > 1:
-        assert cp.plan_train_conv(d2, (R - 1, 256, 7, 7, 7), big, 2, NEEDS, wgrad_dilated_f16=w).wgrad == cp.WGRAD_DILATED
-    # the pinned field lists
-    assert cp.TrainSetting._fields == ("train", "min_units", "narrow", "wgrad", "wgrad_narrow", "dilated")
+        assert cp.plan_train_conv(d2._replace(wgrad_dilated_f16=w), (R - 1, 256, 7, 7, 7), big, 2, NEEDS).wgrad == cp.WGRAD_DILATED
+    # the field lists: the six older switches in their order, then the three thresholds the setting now carries itself
+    assert cp.TrainSetting._fields == ("train", "min_units", "narrow", "wgrad", "wgrad_narrow", "dilated",
+                                       "wgrad_narrow_f16", "dilated_f16", "wgrad_dilated_f16")
     assert cp.TrainConvPlan._fields == ("forward", "sweep", "dgrad", "wgrad", "gy_reduce", "gb")
 
 
 def test_the_switch_round_trips_and_install_leaves_it_off(L):
     import m3d.compat as c
     from m3d import conv_plan as cp
-    assert c.get_conv_wgrad_dilated_f16() is False and c._wgrad_dilated_f16 is None          # default off
+    assert c.get_conv_wgrad_dilated_f16() is False and c._setting.wgrad_dilated_f16 is None          # default off
     try:
         assert c.set_conv_wgrad_dilated_f16(True) is False and c.get_conv_wgrad_dilated_f16() is True
-        assert c._wgrad_dilated_f16 == cp.WGRAD_DILATED_F16X2_MIN_WORK                       # min_work=None: the constant
+        assert c._setting.wgrad_dilated_f16 == cp.WGRAD_DILATED_F16X2_MIN_WORK                       # min_work=None: the constant
         assert c.get_conv_wgrad_narrow_f16() is False and c.get_conv_dilated_f16() is False and c.get_conv_dilated() == "torch"
         c.install_conv3d(), c.install_linear()                  # what install() does to F.conv3d / F.linear leaves it alone
         assert c.get_conv_wgrad_dilated_f16() is True
-        assert c.set_conv_wgrad_dilated_f16(True, 0) is True and c._wgrad_dilated_f16 == 0   # 0 routes every supported layer
-        assert c.set_conv_wgrad_dilated_f16(True) is True and c._wgrad_dilated_f16 == cp.WGRAD_DILATED_F16X2_MIN_WORK
+        assert c.set_conv_wgrad_dilated_f16(True, 0) is True and c._setting.wgrad_dilated_f16 == 0   # 0 routes every supported layer
+        assert c.set_conv_wgrad_dilated_f16(True) is True and c._setting.wgrad_dilated_f16 == cp.WGRAD_DILATED_F16X2_MIN_WORK
         assert c.set_conv_wgrad_dilated_f16(False) is True and c.get_conv_wgrad_dilated_f16() is False
         with pytest.raises(ValueError):
             c.set_conv_wgrad_dilated_f16(True, -1)

@@ -243,29 +243,29 @@ def test_the_plan_passes_the_threshold_on_and_leaves_gy_reduce_and_gb_alone(L):
                 for wn in (False, True):
                     s = cp.TrainSetting(train=train, min_units=0, narrow=narrow, wgrad=wg, wgrad_narrow=wn)
                     off = cp.plan_train_conv(s, x, w, 1, (True, True, True))
-                    assert cp.plan_train_conv(s, x, w, 1, (True, True, True), wgrad_narrow_f16=None) == off
-                    on = cp.plan_train_conv(s, x, w, 1, (True, True, True), wgrad_narrow_f16=0)
+                    assert cp.plan_train_conv(s._replace(wgrad_narrow_f16=None), x, w, 1, (True, True, True)) == off
+                    on = cp.plan_train_conv(s._replace(wgrad_narrow_f16=0), x, w, 1, (True, True, True))
                     assert on.wgrad == cp.WGRAD_NARROW_F16X2 and off.wgrad != cp.WGRAD_NARROW_F16X2
                     assert on._replace(wgrad=off.wgrad) == off                          # forward, sweep, dgrad, gy_reduce, gb
-                    assert cp.plan_train_conv(s, x, w, 1, (True, True, True), wgrad_narrow_f16=4 * 32 * 64 * 343 + 1) == off
-                    assert cp.plan_train_conv(s, x, w, 1, (True, False, True), wgrad_narrow_f16=0).wgrad is None
-                    assert cp.plan_train_backward(s, x, w, 1, (True, True, True), 0) == tuple(on)[2:]
+                    assert cp.plan_train_conv(s._replace(wgrad_narrow_f16=4 * 32 * 64 * 343 + 1), x, w, 1, (True, True, True)) == off
+                    assert cp.plan_train_conv(s._replace(wgrad_narrow_f16=0), x, w, 1, (True, False, True)).wgrad is None
+                    assert cp.plan_train_backward(s._replace(wgrad_narrow_f16=0), x, w, 1, (True, True, True)) == tuple(on)[2:]
     d2 = cp.TrainSetting(dilated="m3d")
-    assert cp.plan_train_conv(d2, x, w, 2, (True, True, True), wgrad_narrow_f16=0).wgrad == cp.WGRAD_DILATED
+    assert cp.plan_train_conv(d2._replace(wgrad_narrow_f16=0), x, w, 2, (True, True, True)).wgrad == cp.WGRAD_DILATED
 
 
 def test_the_switch_round_trips_and_install_leaves_it_off(L):
     import m3d.compat as c
     from m3d import conv_plan as cp
-    assert c.get_conv_wgrad_narrow_f16() is False and c._wgrad_narrow_f16 is None          # default off
+    assert c.get_conv_wgrad_narrow_f16() is False and c._setting.wgrad_narrow_f16 is None          # default off
     try:
         assert c.set_conv_wgrad_narrow_f16(True) is False and c.get_conv_wgrad_narrow_f16() is True
-        assert c._wgrad_narrow_f16 == cp.WGRAD_NARROW_F16X2_MIN_WORK                       # min_work=None: the constant
+        assert c._setting.wgrad_narrow_f16 == cp.WGRAD_NARROW_F16X2_MIN_WORK                       # min_work=None: the constant
         assert c.get_conv_wgrad_narrow() is False and c.get_conv_wgrad() == "fp32" and c.get_conv_train_narrow() is False
         c.install_conv3d(), c.install_linear()                  # what install() does to F.conv3d / F.linear leaves it alone
         assert c.get_conv_wgrad_narrow_f16() is True
-        assert c.set_conv_wgrad_narrow_f16(True, 0) is True and c._wgrad_narrow_f16 == 0   # 0 routes every supported layer
-        assert c.set_conv_wgrad_narrow_f16(True) is True and c._wgrad_narrow_f16 == cp.WGRAD_NARROW_F16X2_MIN_WORK
+        assert c.set_conv_wgrad_narrow_f16(True, 0) is True and c._setting.wgrad_narrow_f16 == 0   # 0 routes every supported layer
+        assert c.set_conv_wgrad_narrow_f16(True) is True and c._setting.wgrad_narrow_f16 == cp.WGRAD_NARROW_F16X2_MIN_WORK
         assert c.set_conv_wgrad_narrow_f16(False) is True and c.get_conv_wgrad_narrow_f16() is False
         with pytest.raises(ValueError):
             c.set_conv_wgrad_narrow_f16(True, -1)

@@ -102,8 +102,8 @@ def main():
                 gy = torch.randn(R, cout, 7, 7, 7, device="cuda")
                 w = torch.randn(cout, cin, 3, 3, 3, device="cuda") * (2.0 / (27 * cin)) ** 0.5
                 b = torch.randn(cout, device="cuda")
-                plan = conv_plan.plan_train_conv(setting, tuple(x.shape), tuple(w.shape), 2, (True, True, True),
-                                                 dilated_f16=conv_plan.ZN_DILATED_MIN_UNITS)
+                plan = conv_plan.plan_train_conv(setting._replace(dilated_f16=conv_plan.ZN_DILATED_MIN_UNITS), tuple(x.shape), tuple(w.shape), 2,
+                                                 (True, True, True))
                 for direction in ("forward", "dgrad"):
                     ci, co = (cin, cout) if direction == "forward" else (cout, cin)
                     units = int(ops.lib().m3d_conv3d_zn_dilated_launch_units(R, ci, co, 7, 7, 7, 2))
