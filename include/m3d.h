@@ -1548,6 +1548,44 @@ int m3d_mask_tail_f16x2(const float* d_x, const void* d_packed, const float* d_u
                         float* d_out, int R, int Cin, int Cout, int K, int D, int H, int W, int sigmoid, const float* d_in_max,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The up-conv's BACKWARD on the f16 matrix cores at fp32 accuracy (upconv3d_bwd_f16.hip; DESIGN, "Up-conv backward on the f16 pipe"):
+ * what m3d_upconv3d_2x_dgrad / _wgrad compute, on the same tensors as PyTorch stores them (d_gy, d_y_mask [R,Cout,2D,2H,2W], d_x
+ * [R,Cin,D,H,W], d_weight [Cin,Cout,2,2,2]; no transposed, shuffled or packed copy of any of them).  With g = d_gy where d_y_mask > 0
+ * (d_y_mask NULL: g = d_gy; a select applied before the cut, so a masked-out Inf / NaN contributes exactly 0), n = 8 co + 4a + 2b + c
+ * and col = (r, z, y, x):
+ *   m3d_upconv3d_2x_dgrad_f16x2   d_gx[col, ci] = sum_n g[col, n] W[ci, n]                       (reduction 8 Cout, never split)
+ *   m3d_upconv3d_2x_wgrad_f16x2   d_gw[ci, n] = sum_col x[col, ci] g[col, n]                     (reduction R D H W, split-K into d_ws)
+ *                                 d_gb[co] (or NULL) = sum g, from the UNCUT fp32 values in a fixed order, out of the same launch
+ * The f16x2 cut of f16x2.h: each operand times the power of two of its tensor bound, cut into hi + lo fp16 once while it is staged,
+ * three v_mfma_f32_32x32x16_f16 per fp32 product, fp32 accumulation, exact un-scaling.  d_gy_max / d_w_max / d_x_max: the
+ * [m3d_conv3d_zw_slots()] device floats whose largest bounds the operand (for g: the UNMASKED d_gy), or NULL: the call sweeps that
+ * operand into d_ws (no host read).  d_ws: _workspace_bytes(...) bytes (0: the shape is refused), 16-byte aligned; every byte of it
+ * the call reads it has written.  No atomics, every output element written by the call, bit-identical run to run and on any stream,
+ * no scratch; an Inf / NaN in an unmasked operand gives NaN, never a finite number.
+ * Error bounds per element: tests/upconv_backward_f16_cases.py - the formula of tests/f16x2_contract.py with c1 = 3.01 (no operand is
+ * rounded before the cut) and n_acc = chain * max(folds, 1) + folds + slices + 2 from the _plan calls (host only): `slices` partial
+ * sums the reduce launch adds (dgrad: always 1), `chain` the most MFMAs one accumulator chains between two fp32 folds (<= 384), `folds`
+ * the folds of a slice (0: the chain is never folded); + 2: the two scale multiplies.  d_gb: the fp32 bound of upconv_reference.bound
+ * with n = 8 R D H W + gb_partials.
+ * m3d_upconv3d_2x_backward_f16x2_supported (host only): R, D, H, W >= 1, Cin % 32 == 0, Cout % 32 == 0, every tensor below 2^31
+ * elements.  Refusals, all before a pointer is followed: M3D_EINVAL for R < 0 or Cin, Cout, D, H or W < 1, a NULL required pointer
+ * (d_ws included), a pointer that is not 4-byte aligned, a workspace that is too small; M3D_EUNSUPPORTED for a shape _supported
+ * refuses and for d_gy, d_y_mask, d_weight, d_gw or d_ws not 16-byte aligned.  R == 0: dgrad does nothing (no pointer is looked at),
+ * wgrad writes zeros to d_gw and d_gb.
+ * ------------------------------------------------------------------------------------------------------- */
+int m3d_upconv3d_2x_backward_f16x2_supported(int R, int Cin, int Cout, int D, int H, int W);
+int m3d_upconv3d_2x_dgrad_f16x2_plan(int R, int Cin, int Cout, int D, int H, int W, int* slices, int* chain, int* folds);
+int m3d_upconv3d_2x_wgrad_f16x2_plan(int R, int Cin, int Cout, int D, int H, int W, int* slices, int* chain, int* folds, int* gb_partials);
+size_t m3d_upconv3d_2x_dgrad_f16x2_workspace_bytes(int R, int Cin, int Cout, int D, int H, int W);
+size_t m3d_upconv3d_2x_wgrad_f16x2_workspace_bytes(int R, int Cin, int Cout, int D, int H, int W);
+int m3d_upconv3d_2x_dgrad_f16x2(const float* d_gy, const float* d_y_mask, const float* d_weight, float* d_gx, int R, int Cin, int Cout,
+                                int D, int H, int W, const float* d_gy_max, const float* d_w_max, void* d_ws, size_t ws_bytes,
+                                void* stream);
+int m3d_upconv3d_2x_wgrad_f16x2(const float* d_gy, const float* d_y_mask, const float* d_x, float* d_gw, float* d_gb, int R, int Cin,
+                                int Cout, int D, int H, int W, const float* d_gy_max, const float* d_x_max, void* d_ws, size_t ws_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

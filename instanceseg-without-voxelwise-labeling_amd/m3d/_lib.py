@@ -58,6 +58,9 @@ SYMBOLS = [
     "m3d_mask_tail_f16x2",
     "m3d_linear_backward_f16x2_supported", "m3d_linear_dgrad_f16x2_plan", "m3d_linear_wgrad_f16x2_plan",
     "m3d_linear_dgrad_f16x2_workspace_bytes", "m3d_linear_wgrad_f16x2_workspace_bytes", "m3d_linear_dgrad_f16x2", "m3d_linear_wgrad_f16x2",
+    "m3d_upconv3d_2x_backward_f16x2_supported", "m3d_upconv3d_2x_dgrad_f16x2_plan", "m3d_upconv3d_2x_wgrad_f16x2_plan",
+    "m3d_upconv3d_2x_dgrad_f16x2_workspace_bytes", "m3d_upconv3d_2x_wgrad_f16x2_workspace_bytes", "m3d_upconv3d_2x_dgrad_f16x2",
+    "m3d_upconv3d_2x_wgrad_f16x2",
 ]
 
 
@@ -138,7 +141,8 @@ def _load(path):
               "m3d_upconv3d_2x_dgrad_workspace_bytes", "m3d_upconv3d_2x_wgrad_workspace_bytes",
               "m3d_conv3d_wgrad_dilated_workspace_bytes", "m3d_conv3d_wgrad_narrow_workspace_bytes", "m3d_conv3d_zn_packed_bytes",
               "m3d_conv3d_wgrad_narrow_f16x2_workspace_bytes", "m3d_conv3d_wgrad_narrow_dilated_f16x2_workspace_bytes",
-              "m3d_upconv3d_2x_f16x2_packed_bytes", "m3d_linear_dgrad_f16x2_workspace_bytes", "m3d_linear_wgrad_f16x2_workspace_bytes"):
+              "m3d_upconv3d_2x_f16x2_packed_bytes", "m3d_linear_dgrad_f16x2_workspace_bytes", "m3d_linear_wgrad_f16x2_workspace_bytes",
+              "m3d_upconv3d_2x_dgrad_f16x2_workspace_bytes", "m3d_upconv3d_2x_wgrad_f16x2_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     return L
 

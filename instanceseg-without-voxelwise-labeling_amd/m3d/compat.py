@@ -591,6 +591,7 @@ def invalidate_packs():
     _pack_cache.clear()
     _lin_cache.clear()
     _wmax_cache.clear()
+    _upconv_wmax_cache.clear()
 
 
 def install_linear():
@@ -680,7 +681,7 @@ _upconv_f16 = False
 def set_upconv_f16(on):
     """The FORWARD of m3d.upconv3d_2x (train.MaskHead under set_upconv("m3d")) on the f16 matrix cores (ops.UpConvF16, csrc/upconv3d_f16.hip:
     the f16x2 cut at fp32 accuracy, one bound sweep of x per call, the pack served through the pack cache) where the kernel takes the
-    shape (Cin % 16 == 0); the backward stays on m3d_upconv3d_2x_dgrad / _wgrad, which take the ReLU mask from the saved output whichever
+    shape (Cin % 16 == 0); the backward follows set_upconv_backward (fp32 by default), and takes the ReLU mask from the saved output whichever
     kernel wrote it.  Off by default, install() does not touch it, and it has no effect without set_upconv("m3d").  Returns the
     previous setting."""
     global _upconv_f16
@@ -690,6 +691,46 @@ def set_upconv_f16(on):
 
 def get_upconv_f16():
     return _upconv_f16
+
+
+_upconv_backward = (conv_plan.UPCONV_BACKWARD_FP32, None)     # set_upconv_backward: (mode, min_work or None = the planner's constants)
+_upconv_wmax_cache = {}   # id(parameter) -> (weakref, _version, data_ptr, max|W| as [ZwConv3d.SLOTS] device floats)
+
+
+def set_upconv_backward(mode, min_work=None):
+    """The BACKWARD of m3d.upconv3d_2x (train.MaskHead under set_upconv("m3d")): "fp32" (the default; install() does not touch it) keeps
+    m3d_upconv3d_2x_dgrad / _wgrad; "f16x2" takes m3d_upconv3d_2x_dgrad_f16x2 / _wgrad_f16x2 (csrc/upconv3d_bwd_f16.hip: the f16 matrix
+    cores at fp32 accuracy, gy, the ReLU mask, x and the weight read as they are and cut while they are staged) for each direction
+    conv_plan.upconv_backward_kernel routes to them.  gy is swept once per backward and its bound shared by both passes, max|W| is
+    cached per parameter like the packs (invalidate_packs() drops it, so Solver.step() does), x's bound is the one the f16x2 forward
+    held where it ran, else the wgrad call sweeps x.  The forward keeps its kernel and its bits.  min_work: the routing threshold of
+    both directions in multiply-adds R D H W Cin 8 Cout (None: conv_plan.UPCONV_BWD_F16_MIN_DGRAD / _WGRAD; 0 routes every supported
+    shape - tests and A/B runs).  No effect without set_upconv("m3d").  Read when the backward runs.  Returns the previous mode."""
+    global _upconv_backward
+    if mode not in (conv_plan.UPCONV_BACKWARD_FP32, conv_plan.UPCONV_BACKWARD_F16X2):
+        raise ValueError("set_upconv_backward(%r): 'fp32' or 'f16x2'" % (mode,))
+    prev, _upconv_backward = _upconv_backward[0], (mode, _threshold("set_upconv_backward", "min_work", min_work))
+    return prev
+
+
+def get_upconv_backward():
+    return _upconv_backward[0]
+
+
+def _upconv_weight_max(weight):
+    """max|W| of the up-conv's weight as [ZwConv3d.SLOTS] device floats, cached like _weight_max: only for live nn.Parameters at the
+    same version / address"""
+    if not isinstance(weight, torch.nn.Parameter):
+        return ops.ZwConv3d.bound_of(weight.detach())
+    ent = _upconv_wmax_cache.get(id(weight))
+    if ent is not None:
+        ref, ver, ptr, wmax = ent
+        if ref() is weight and ver == weight._version and ptr == weight.data_ptr():
+            return wmax
+    wmax = ops.ZwConv3d.bound_of(weight.detach())
+    _upconv_wmax_cache[id(weight)] = (weakref.ref(weight, lambda _r, k=id(weight): _upconv_wmax_cache.pop(k, None)), weight._version,
+                                      weight.data_ptr(), wmax)
+    return wmax
 
 
 def _upconv_qualifies(x, weight, bias, stride, padding, output_padding, groups, dilation):

@@ -106,6 +106,44 @@ def linear_backward_kernel(M, N, K, mode, min_work=None):
     return LINEAR_BACKWARD_FP32
 
 
+UPCONV_BACKWARD_FP32, UPCONV_BACKWARD_F16X2 = "fp32", "f16x2"    # up-conv backward: csrc/upconv3d.hip / csrc/upconv3d_bwd_f16.hip
+# Routing thresholds of the up-conv's f16x2 backward per direction, in multiply-adds of the GEMM, R D H W x Cin x 8 Cout: the work of
+# the smallest row of profiles/upconv_backward_f16.txt (256 -> 256 channels, 7^3 -> 14^3, ReLU mask, the gy sweep inside the window,
+# max|W| cached) at which the f16x2 call beat m3d_upconv3d_2x_dgrad / _wgrad by more than the sum of the two spreads.  None: the
+# direction was never measured to win and does not route by default.  Nothing smaller than a measured win routes.
+#   dgrad: wins at R = 64 (0.239 against 0.327 ms, x1.37) and R = 300 (0.908 against 1.274 ms, x1.40); LOSES at R = 16 (0.133 against
+#          0.085 ms: 86 workgroups on 256 CUs, and the sweep is a launch of its own) and R = 4 (0.130 against 0.039 ms).
+#   wgrad: LOSES at every measured count (R = 4, 16, 64, 300: x0.76, x0.84, x0.73, x0.58 - the 4- and 8-byte gathers of x and gy along
+#          the reduction bound it at 0.8 - 0.9 TB/s of gy + y): it never routes by default.
+UPCONV_BWD_F16_MIN_DGRAD = 64 * 343 * 256 * 8 * 256
+UPCONV_BWD_F16_MIN_WGRAD = None
+UPCONV_BWD_F16_MIN = {"dgrad": UPCONV_BWD_F16_MIN_DGRAD, "wgrad": UPCONV_BWD_F16_MIN_WGRAD}
+
+
+def upconv_backward_kernel(direction, R, Cin, Cout, D, H, W, setting):
+    """Which kernel computes the "dgrad" or the "wgrad" (+ bias gradient) of the mask head's ConvTranspose3d(2, 2) with x [R,Cin,D,H,W]
+    and weight [Cin,Cout,2,2,2]: UPCONV_BACKWARD_FP32 (m3d_upconv3d_2x_dgrad / _wgrad) or UPCONV_BACKWARD_F16X2
+    (m3d_upconv3d_2x_dgrad_f16x2 / _wgrad_f16x2).  The one place that says so.  setting: (mode, min_work) as compat.set_upconv_backward
+    keeps it - mode "fp32" keeps both directions where they are; "f16x2" moves a direction whose shape
+    m3d_upconv3d_2x_backward_f16x2_supported takes (Cin and Cout multiples of 32) and whose work R D H W Cin 8 Cout reaches min_work
+    (None: the direction's UPCONV_BWD_F16_MIN_* constant, and no routing where that is None; 0: every supported shape).  A function of
+    the shape only."""
+    if direction not in UPCONV_BWD_F16_MIN:
+        raise ValueError("direction %r: 'dgrad' or 'wgrad'" % (direction,))
+    mode, min_work = setting
+    if mode not in (UPCONV_BACKWARD_FP32, UPCONV_BACKWARD_F16X2):
+        raise ValueError("up-conv backward mode %r: 'fp32' or 'f16x2'" % (mode,))
+    if mode == UPCONV_BACKWARD_FP32:
+        return UPCONV_BACKWARD_FP32
+    floor = UPCONV_BWD_F16_MIN[direction] if min_work is None else int(min_work)
+    if floor is None:
+        return UPCONV_BACKWARD_FP32
+    R, Cin, Cout, D, H, W = (int(v) for v in (R, Cin, Cout, D, H, W))
+    if R * D * H * W * Cin * 8 * Cout >= floor and ops.upconv3d_2x_backward_f16x2_supported((R, Cin, D, H, W), Cout):
+        return UPCONV_BACKWARD_F16X2
+    return UPCONV_BACKWARD_FP32
+
+
 TRAIN_FP32, TRAIN_F16X2 = "fp32", "f16x2"            # forward / dgrad kernels of a training conv: the direct fp32 MFMA kernel / conv3d_zw.hip
 TRAIN_F16X2_NARROW = "f16x2 narrow"                  # conv3d_zn.hip (ops.ZnConv3d): maps at most 8 wide, opt-in (compat.set_conv_train_narrow)
 # Output channels of the launched conv (forward: cout; dgrad: the forward cin) from which a direction routes to the f16x2 kernel.  Its

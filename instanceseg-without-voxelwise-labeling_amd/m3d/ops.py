@@ -12,7 +12,7 @@ from ._lib import lib, check, M3DError, SgdTensor, AdamTensor, GradTensor, BoxHe
 BBOX_XFORM_CLIP = float(np.log(1000. / 16.))   # lib/core/config.py:947
 
 __all__ = ["compact_rows", "compact_rows2", "box_head_outputs", "roi_align3d_forward", "roi_align3d_backward", "roi_align3d_backward_ordered", "nms3d", "bbox_overlaps3d", "bbox_transform3d",
-           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "linear_dgrad_f16x2", "linear_wgrad_f16x2", "linear_backward_f16x2_supported", "linear_dgrad_f16x2_plan", "linear_wgrad_f16x2_plan", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "UpConvF16", "SplitLinear", "linear_roi_fused", "mask_paste3d",
+           "generate_proposals3d", "generate_proposals3d_batched", "box_results3d_batched", "nms3d_batched", "fused_max_boxes", "PackedConv3d", "maxpool3d_2x", "maxpool3d_2x_backward", "reduce_min", "reduce_min_multi", "norm1", "norm1_batched", "norm1_stats", "train_sample", "linear", "linear_plan", "linear_dgrad", "linear_wgrad", "linear_dgrad_f16x2", "linear_wgrad_f16x2", "linear_backward_f16x2_supported", "linear_dgrad_f16x2_plan", "linear_wgrad_f16x2_plan", "upconv3d_2x_forward", "upconv3d_2x_dgrad", "upconv3d_2x_wgrad", "upconv3d_2x_slices", "UPCONV_KINDS", "UpConvF16", "upconv3d_2x_dgrad_f16x2", "upconv3d_2x_wgrad_f16x2", "upconv3d_2x_backward_f16x2_supported", "upconv3d_2x_backward_f16x2_plan", "SplitLinear", "linear_roi_fused", "mask_paste3d",
            "otsu2d_batch", "prm_quantize_u8", "prm_quantize_windows_u8", "prm_quantize_windows_compact_u8", "roi_normalize", "conv3d_wgrad", "conv3d_wgrad_f16x2", "conv3d_wgrad_f16x2_supported", "conv3d_wgrad_f16x2_plan", "conv3d_wgrad_narrow_f16x2", "conv3d_wgrad_narrow_f16x2_supported", "conv3d_wgrad_narrow_f16x2_plan", "conv3d_direct_plan", "conv3d_bias_grad", "conv3d_gy_reduce", "WinoConv3d", "ZwConv3d", "ZnConv3d", "X3Conv3d", "StemWinoConv3d", "gaussian_filter_u16", "median_filter3_u16", "cc_largest_batch", "binary_closing6_batch", "paint_instances", "paint_instances_into", "paint_finish", "paint_begin", "crop_offsets", "upload_packed", "conv3d_windowed", "prm_seed", "strip_geometry", "prm_prepare_plan", "prm_stem_dgrad_plan", "PRM_PREPARE_KERNELS", "PRM_STEM_DGRAD_LAYOUTS", "prm_select_peaks", "PinnedPool", "upload", "prm_prepare", "prm_stem_dgrad", "prm_stem_prepare_weights", "SmallWindowDgrad", "prm_den_pool", "prm_stem_mfma_weights", "prm_stem_dgrad_fused", "prm_stem_dgrad_fused_supported", "prm_scatter", "conv3d_stem5_dgrad", "conv3d_stem5_dgrad_weights", "label_overlap", "label_iou_best", "box_union_overlap_counts", "Overlap", "IouBest", "LABEL_LIMIT", "label_components", "label_counts", "paint_spheres", "rpn_target_sets", "rpn_target_blobs", "rpn_loss_grad", "box_head_target_sets", "box_head_target_blobs", "box_head_loss_grad", "mask_target_sets", "mask_loss_grad", "bn_stats", "bn_invstd", "bn_apply", "bn_backward", "sgd_step", "sgd_chunk", "sgd_step_scaled", "adam_step", "grad_clip_coef", "M3DError", "BBOX_XFORM_CLIP", "W_PLAIN", "W_RELU", "W_DGRAD", "W_DGRAD_RELU"]
 
 W_PLAIN, W_RELU, W_DGRAD, W_DGRAD_RELU = 0, 1, 2, 3
@@ -825,6 +825,112 @@ def upconv3d_2x_wgrad(gy, x, y=None, bias=True, out=None):
     ws = _workspace(wsb, gy.device, "upconv") if wsb else None
     check(lib().m3d_upconv3d_2x_wgrad(_ptr(gy), _ptr(y), _ptr(x), _ptr(out), _ptr(gb), R, cin, cout, D, H, W, _ptr(ws), C.c_size_t(wsb),
                                       _stream()), "upconv3d_2x_wgrad")
+    return out, gb
+
+
+def upconv3d_2x_backward_f16x2_supported(shape_x, Cout):
+    """m3d_upconv3d_2x_backward_f16x2_supported (host only): upconv3d_2x_dgrad_f16x2 / upconv3d_2x_wgrad_f16x2 take x of shape_x =
+    (R, Cin, D, H, W) against Cout output channels: R, D, H, W >= 1, Cin % 32 == 0, Cout % 32 == 0, every tensor below 2^31 elements"""
+    if len(shape_x) != 5:
+        return False
+    R, cin, D, H, W = (int(v) for v in shape_x)
+    return bool(lib().m3d_upconv3d_2x_backward_f16x2_supported(R, cin, int(Cout), D, H, W))
+
+
+def upconv3d_2x_backward_f16x2_plan(direction, R, Cin, Cout, D, H, W):
+    """What upconv3d_2x_dgrad_f16x2 / _wgrad_f16x2 (direction "dgrad" / "wgrad") run at the shape (m3d_upconv3d_2x_*_f16x2_plan, host
+    only): dict(slices, chain, folds) - the partial sums the reduce launch adds (dgrad: 1), the most MFMAs one accumulator chains
+    (<= 384) and the folds of a slice's accumulator into fp32 registers - and for "wgrad" also gb_partials, the partial sums of a bias
+    gradient; None where the shape is not supported."""
+    if direction not in ("dgrad", "wgrad"):
+        raise ValueError("upconv3d_2x_backward_f16x2_plan(%r): 'dgrad' or 'wgrad'" % (direction,))
+    keys = ("slices", "chain", "folds") + (("gb_partials",) if direction == "wgrad" else ())
+    v = [C.c_int(0) for _ in keys]
+    fn = lib().m3d_upconv3d_2x_dgrad_f16x2_plan if direction == "dgrad" else lib().m3d_upconv3d_2x_wgrad_f16x2_plan
+    rc = fn(int(R), int(Cin), int(Cout), int(D), int(H), int(W), *[C.byref(a) for a in v])
+    if rc == -4:
+        return None
+    check(rc, "upconv3d_2x_%s_f16x2_plan" % direction)
+    return dict(zip(keys, (a.value for a in v)))
+
+
+def _slots_arg(what, b):
+    """an operand bound for the up-conv's f16x2 backward: None (the library sweeps), or ZwConv3d.SLOTS contiguous device floats whose
+    largest is the bound; a 1-element bound (ops.absmax) is widened with zeros"""
+    if b is None:
+        return None
+    _need_gpu(b)
+    if not (b.dtype == torch.float32 and b.is_contiguous() and b.numel() in (1, ZwConv3d.SLOTS)):
+        raise ValueError("%s: a bound is 1 or %d contiguous float32 device values" % (what, ZwConv3d.SLOTS))
+    if b.numel() == 1:
+        b = torch.nn.functional.pad(b.reshape(1), (0, ZwConv3d.SLOTS - 1))
+    return b
+
+
+def _upconv_mask(what, gy, y):
+    if y is None:
+        return None
+    _need_gpu(y)
+    y = _f32c(y)
+    if y.shape != gy.shape:
+        raise ValueError("%s: y is %s but gy is %s" % (what, tuple(y.shape), tuple(gy.shape)))
+    return y
+
+
+def upconv3d_2x_dgrad_f16x2(gy, weight, y=None, gy_max=None, w_max=None, out=None):
+    """upconv3d_2x_dgrad on the f16 matrix cores at fp32 accuracy (m3d_upconv3d_2x_dgrad_f16x2; csrc/upconv3d_bwd_f16.hip): gy
+    [R,Cout,2D,2H,2W], weight [Cin,Cout,2,2,2] -> [R,Cin,D,H,W], both read as fp32 and cut while they are staged - no pack, no shuffled
+    copy.  y: the output of a relu forward (gy counts only where y > 0, selected before the cut).  gy_max / w_max: [ZwConv3d.SLOTS]
+    device floats whose largest bounds the UNMASKED |gy| / |weight| (ZwConv3d.bound_of; a 1-element ops.absmax result is taken too);
+    None: the library sweeps that operand.  An unsupported shape is an error: ask upconv3d_2x_backward_f16x2_supported (or
+    conv_plan.upconv_backward_kernel).  R == 0 returns zeros without a launch."""
+    what = "upconv3d_2x_dgrad_f16x2"
+    _need_gpu(gy, weight)
+    gy, weight = _f32c(gy), _f32c(weight)
+    R, cin, cout, D, H, W = _upconv_dims(what, weight, g=gy)
+    y = _upconv_mask(what, gy, y)
+    gm, wm = _slots_arg(what, gy_max), _slots_arg(what, w_max)
+    _claim(out)
+    if out is None:
+        out = torch.empty((R, cin, D, H, W), dtype=torch.float32, device=gy.device)
+    if tuple(out.shape) != (R, cin, D, H, W) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("%s: out must be a contiguous float32 %s" % (what, (R, cin, D, H, W)))
+    if R == 0:
+        return out.zero_()
+    wsb = lib().m3d_upconv3d_2x_dgrad_f16x2_workspace_bytes(R, cin, cout, D, H, W)
+    ws = _workspace(max(wsb, 16), gy.device, "upconv-f16")
+    check(lib().m3d_upconv3d_2x_dgrad_f16x2(_ptr(gy), _ptr(y), _ptr(weight), _ptr(out), R, cin, cout, D, H, W, _ptr(gm), _ptr(wm),
+                                            _ptr(ws), C.c_size_t(wsb), _stream()), what)
+    return out
+
+
+def upconv3d_2x_wgrad_f16x2(gy, x, y=None, gy_max=None, x_max=None, bias=True, out=None):
+    """upconv3d_2x_wgrad on the f16 matrix cores at fp32 accuracy (m3d_upconv3d_2x_wgrad_f16x2): gy [R,Cout,2D,2H,2W], x [R,Cin,D,H,W]
+    -> ([Cin,Cout,2,2,2], [Cout] or None without `bias`); the bias gradient is summed from the uncut masked fp32 values.  y and the
+    bounds as upconv3d_2x_dgrad_f16x2 (x_max: what the conv before left on x, or a sweep).  R == 0 returns zeros without a launch."""
+    what = "upconv3d_2x_wgrad_f16x2"
+    _need_gpu(gy, x)
+    gy, x = _f32c(gy), _f32c(x)
+    if gy.dim() != 5 or x.dim() != 5:
+        raise ValueError("%s: gy is %s, x is %s" % (what, tuple(gy.shape), tuple(x.shape)))
+    cin, cout = int(x.shape[1]), int(gy.shape[1])
+    R, D, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), int(x.shape[4])
+    if tuple(gy.shape) != (R, cout, 2 * D, 2 * H, 2 * W):
+        raise ValueError("%s: gy is %s, expected %s" % (what, tuple(gy.shape), (R, cout, 2 * D, 2 * H, 2 * W)))
+    y = _upconv_mask(what, gy, y)
+    gm, xm = _slots_arg(what, gy_max), _slots_arg(what, x_max)
+    _claim(out)
+    if out is None:
+        out = torch.empty((cin, cout, 2, 2, 2), dtype=torch.float32, device=gy.device)
+    if tuple(out.shape) != (cin, cout, 2, 2, 2) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("%s: out must be a contiguous float32 %s" % (what, (cin, cout, 2, 2, 2)))
+    gb = torch.empty((cout,), dtype=torch.float32, device=gy.device) if bias else None
+    if R == 0:
+        return out.zero_(), (gb.zero_() if bias else None)
+    wsb = lib().m3d_upconv3d_2x_wgrad_f16x2_workspace_bytes(R, cin, cout, D, H, W)
+    ws = _workspace(max(wsb, 16), gy.device, "upconv-f16")
+    check(lib().m3d_upconv3d_2x_wgrad_f16x2(_ptr(gy), _ptr(y), _ptr(x), _ptr(out), _ptr(gb), R, cin, cout, D, H, W, _ptr(gm), _ptr(xm),
+                                            _ptr(ws), C.c_size_t(wsb), _stream()), what)
     return out, gb
 
 

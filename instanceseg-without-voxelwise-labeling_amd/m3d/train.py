@@ -515,17 +515,20 @@ def mask_losses(mask_pred, targets):
 class _UpConv3d2x(torch.autograd.Function):
     """ConvTranspose3d(kernel 2, stride 2, padding 0) (+ ReLU) on csrc/upconv3d.hip.  With relu the forward's own output is saved and
     handed to both backward kernels as the mask: no ReLU-backward pass over the 2x tensor.  Only the gradients autograd asks for are
-    computed; the bias gradient comes out of the wgrad launch."""
+    computed; the bias gradient comes out of the wgrad launch.  Each backward direction runs where conv_plan.upconv_backward_kernel says
+    (compat.set_upconv_backward: csrc/upconv3d_bwd_f16.hip for the directions it routes, gy swept once for both)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu, f16=False):
         b = None if bias is None else bias.detach()
         up = None
-        if f16 and ops.UpConvF16.supported(weight):          # compat.set_upconv_f16: the forward alone; the backward below does not change
+        if f16 and ops.UpConvF16.supported(weight):          # compat.set_upconv_f16: the forward alone
             from . import compat
             up = compat._packed(weight, "upconv-f16")
+        ctx.x_bound = None
         if up is not None and x.shape[0] > 0 and up.supports(tuple(x.shape)):
-            y = up(x, None, bias=b, relu=relu)
+            ctx.x_bound = ops.ZwConv3d.bound_of(x)               # the sweep UpConvF16 makes for in_max=None, kept for an f16x2 wgrad
+            y = up(x, ctx.x_bound, bias=b, relu=relu)
         else:
             y = ops.upconv3d_2x_forward(x, weight.detach(), b, relu=relu)
         ctx.relu, ctx.has_bias = bool(relu), bias is not None
@@ -537,13 +540,23 @@ class _UpConv3d2x(torch.autograd.Function):
         x, weight, y = ctx.saved_tensors
         gy = gy.contiguous()
         gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = ops.upconv3d_2x_dgrad(gy, weight.detach(), y=y)
+        from . import compat, conv_plan
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or want_gb:
+        want = {"dgrad": ctx.needs_input_grad[0], "wgrad": ctx.needs_input_grad[1] or want_gb}
+        dims = (x.shape[0], x.shape[1], weight.shape[1]) + tuple(x.shape[2:])
+        f16 = {d: want[d] and x.shape[0] > 0 and conv_plan.upconv_backward_kernel(d, *dims, compat._upconv_backward)
+               == conv_plan.UPCONV_BACKWARD_F16X2 for d in want}
+        gy_max = ops.ZwConv3d.bound_of(gy) if (f16["dgrad"] or f16["wgrad"]) else None      # one sweep, both passes
+        if f16["dgrad"]:
+            gx = ops.upconv3d_2x_dgrad_f16x2(gy, weight.detach(), y=y, gy_max=gy_max, w_max=compat._upconv_weight_max(weight))
+        elif want["dgrad"]:
+            gx = ops.upconv3d_2x_dgrad(gy, weight.detach(), y=y)
+        if f16["wgrad"]:
+            gw, gb = ops.upconv3d_2x_wgrad_f16x2(gy, x.detach(), y=y, gy_max=gy_max, x_max=ctx.x_bound, bias=want_gb)
+        elif want["wgrad"]:
             gw, gb = ops.upconv3d_2x_wgrad(gy, x.detach(), y=y, bias=want_gb)
-            if not ctx.needs_input_grad[1]:
-                gw = None
+        if not ctx.needs_input_grad[1]:
+            gw = None
         return gx, gw, gb, None, None
 
 

@@ -27,7 +27,11 @@ conv_plan.WGRAD_DILATED_F16X2_MIN_WORK products per tap).
 conv_plan.WGRAD_NARROW_F16X2_MIN_WORK products per tap, whatever --wgrad and --wgrad-narrow say).  They compose.
 
 --linear-backward f16x2 (default fp32) runs the backward of the FC layers on the f16 matrix cores at fp32 accuracy
-(m3d.compat.set_linear_backward, csrc/fc_backward_f16.hip: layers of at least conv_plan.LINEAR_BACKWARD_F16X2_MIN_WORK M N K)."""
+(m3d.compat.set_linear_backward, csrc/fc_backward_f16.hip: layers of at least conv_plan.LINEAR_BACKWARD_F16X2_MIN_WORK M N K).
+
+--upconv-backward f16x2 (default fp32; with --mask and --upconv m3d) runs the backward of the mask head's up-conv on the f16 matrix
+cores at fp32 accuracy for the directions conv_plan.upconv_backward_kernel routes (m3d.compat.set_upconv_backward,
+csrc/upconv3d_bwd_f16.hip: the dgrad from conv_plan.UPCONV_BWD_F16_MIN_DGRAD multiply-adds up; the wgrad does not route by default)."""
 import argparse
 import os
 import sys
@@ -87,7 +91,10 @@ def main():
                          "backward, bias and ReLU fused")
     ap.add_argument("--upconv-f16", action="store_true",
                     help="with --upconv m3d: the up-conv's FORWARD on the f16 matrix cores at fp32 accuracy (m3d.compat.set_upconv_f16, "
-                         "csrc/upconv3d_f16.hip); the backward stays on the fp32 kernels")
+                         "csrc/upconv3d_f16.hip); the backward follows --upconv-backward")
+    ap.add_argument("--upconv-backward", choices=("fp32", "f16x2"), default="fp32",
+                    help="with --upconv m3d: the up-conv's BACKWARD (m3d.compat.set_upconv_backward): f16x2 = csrc/upconv3d_bwd_f16.hip for "
+                         "the directions conv_plan.upconv_backward_kernel routes to it")
     ap.add_argument("--mask-dilation", type=int, choices=(1, 2), default=1,
                     help="with --mask: MRCNN.DILATION of the mask head's 3^3 convs (MaskTrainCfg.dilation)")
     ap.add_argument("--conv-dilated", choices=("torch", "m3d"), default="torch",
@@ -120,6 +127,8 @@ def main():
         ap.error("--mask-dilation needs --mask")
     if a.upconv_f16 and a.upconv != "m3d":
         ap.error("--upconv-f16 needs --upconv m3d")
+    if a.upconv_backward != "fp32" and a.upconv != "m3d":
+        ap.error("--upconv-backward f16x2 needs --upconv m3d")
     if a.conv_dilated_f16 and a.conv_dilated != "m3d":
         ap.error("--conv-dilated-f16 needs --conv-dilated m3d")
     if a.wgrad_dilated_f16 and not (a.mask == "spot" and a.mask_dilation == 2 and a.conv_dilated == "m3d"):
@@ -139,6 +148,7 @@ def main():
     m3d.compat.set_roi_align_backward(a.roi_backward)
     m3d.compat.set_upconv(a.upconv)
     m3d.compat.set_upconv_f16(a.upconv_f16)
+    m3d.compat.set_upconv_backward(a.upconv_backward)
     m3d.compat.set_conv_dilated(a.conv_dilated)
     m3d.compat.set_conv_dilated_f16(a.conv_dilated_f16)
     m3d.compat.set_conv_wgrad_dilated_f16(a.wgrad_dilated_f16)
